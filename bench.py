@@ -10,6 +10,7 @@ between barriers, continuing the same solve trajectory.
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rows M --cols NS --seed S]
                   [--price tree|seq|wave] [--no-cpu-baseline] [--no-pmc-traffic] [--no-secondary]
                   [--no-late] [--late-pivots N] [--warm-k K] [--cpu-size-pivots N]
+                  [--dump-outputs DIR]
 
 `value` is the rate of the K pivots that follow the warm-up (an almost empty basis inverse); the
 "late", "deep" and "end" blocks time K more pivots of the same solve after 20 000, 150 000 and
@@ -22,6 +23,10 @@ at the same size by its blocked twin on 16 threads, the literal one-core loop be
 
 The default invocation also measures config 5 (32768 x 65536, the LP the multi-GPU target is quoted
 on) and reports it under "secondary"; `value` is always the 8192 x 16384 LP.
+
+--dump-outputs DIR (one GPU): right after the timed pivots, what dzg_solver_result hands the caller
+of the timed path is written to DIR/<name>.npy in float64 -- see dump_outputs().  The LP is seeded,
+so the same arguments give the same inputs on every run and two builds can be compared file by file.
 
 Prints ONE JSON line on rank 0.
 """
@@ -473,14 +478,53 @@ def _late_regime(solver, r1, steps: int, late_pivots: int, kernel: str) -> dict:
     return out
 
 
+DUMP_BYTES_MAX = 64 << 20  # --dump-outputs: every file together
+
+
+def dump_outputs(path: str, res, first_pivot: int, budget: int = DUMP_BYTES_MAX) -> dict:
+    """--dump-outputs: the CoreResult a caller of the timed path receives after its last step --
+    primal and dual state (x, xbar, z, zbar), basis and nonbasis, the objective, and the timed
+    steps' pivots (rows of kind, entering, leaving, mu) with their decision margins -- written as
+    `path`/<name>.npy, all float64 (the indices are exact in it).  When the arrays together exceed
+    `budget` bytes, every array above an equal share of half of it keeps a fixed sample of its rows
+    (seed 0, ascending), their positions in `path`/<name>_index.npy."""
+    import numpy as np
+
+    log = np.asarray(res.pivots[first_pivot:], dtype=np.float64).reshape(-1, 4)
+    margins = res.margins[first_pivot:] if res.margins is not None else np.zeros(0)
+    arrays = {"x": res.x, "xbar": res.xbar, "z": res.z, "zbar": res.zbar, "basis": res.basis,
+              "nonbasis": res.nonbasis, "objective": np.array([res.objective]), "pivots": log,
+              "margins": margins}
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    share = budget // (2 * len(arrays))
+    sampled = {}
+    if sum(v.nbytes for v in arrays.values()) > budget:
+        for name, v in list(arrays.items()):
+            row = max(v.nbytes // max(len(v), 1), 1)
+            if v.nbytes > share:
+                keep = max(share // (row + 8), 1)
+                idx = np.sort(np.random.default_rng(0).choice(len(v), size=keep, replace=False))
+                arrays[name] = v[idx]
+                sampled[name] = {"rows": len(v), "kept": keep}
+                arrays[name + "_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), v)
+    return {"dir": os.path.abspath(path), "files": sorted(n + ".npy" for n in arrays),
+            "bytes": sum(v.nbytes for v in arrays.values()), "iterations": res.iterations,
+            "timed_pivots": len(log), "sampled": sampled or None}
+
+
 SEVEN_LAUNCHES = False  # --seven-launches: the FAST iteration as seven kernels instead of three
 
 
 def measure(rows, cols, seed, sparse_per_col, price_name, numerics_name, steps, warmup,
             late_pivots: int = 0, deep_pivots: int = 0, whole_solve: bool = False,
-            mfma_block: bool = False, end_pivots: int = 0, warm_k: int = 0) -> dict:
+            mfma_block: bool = False, end_pivots: int = 0, warm_k: int = 0,
+            dump_dir: str | None = None) -> dict:
     """One workload on one GPU: generate, upload (untimed), `warmup` pivots, then `steps` timed;
-    with late_pivots > 0 a second timed region deep in the same solve (see _late_regime)."""
+    with late_pivots > 0 a second timed region deep in the same solve (see _late_regime); with
+    `dump_dir` the result after the timed steps goes there (dump_outputs)."""
     from dantzig_amd import _ffi, core
 
     t_gen = time.perf_counter()
@@ -524,6 +568,8 @@ def measure(rows, cols, seed, sparse_per_col, price_name, numerics_name, steps, 
             status = solver.run(steps)
         t1 = time.perf_counter()
         r1 = solver.result(log=False)
+        if dump_dir is not None:
+            dumped = dump_outputs(dump_dir, solver.result(log_cap=r1.iterations), r0.iterations)
         if late_pivots > 0 and status == "iter_limit" and numerics_name == "fast":
             late = _late_regime(solver, r1, steps, late_pivots, kernel)
             if deep_pivots > late_pivots and "skipped" not in late:
@@ -635,6 +681,8 @@ def measure(rows, cols, seed, sparse_per_col, price_name, numerics_name, steps, 
     if whole is not None:
         out["whole_solve_remainder"] = whole
         out["whole_solve"] = whole["whole_solve"]  # (the same figure where a reader looks first)
+    if dump_dir is not None:
+        out["dump_outputs"] = dumped
     return out
 
 
@@ -690,7 +738,13 @@ def main() -> int:
     ap.add_argument("--cpu-size-pivots", type=int, default=6,
                     help="CPU baseline: real pivots of the benchmark's own LP at its own size by the oracle's "
                          "blocked twin on 16 threads (3.4 s each at 8192 rows on a GPU box); 0 = skip")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="one GPU: after the timed steps write the solver's result (x, xbar, z, zbar, basis, "
+                         "nonbasis, objective, the timed pivots and their margins) to DIR/<name>.npy, float64, "
+                         "at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")  # (a budget of 0 pivots = no limit)
 
     if args.refactor_child > 0:
         return refactor_child(args)
@@ -700,6 +754,11 @@ def main() -> int:
     if args.gpus != world and world > 1:
         print(f"--gpus {args.gpus} != WORLD_SIZE {world}", file=sys.stderr)
         return 2
+    if args.dump_outputs is not None and (args.gpus > 1 or world > 1 or args.force_sharded):
+        print("--dump-outputs: one GPU only (the sharded path does not write outputs)", file=sys.stderr)
+        return 2
+    if args.dump_outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)  # (a bad path fails before any GPU work)
     if args.gpus > 1 and world == 1 and "RANK" not in os.environ:
         # asked for several GPUs without a launcher: start one rank per GPU ourselves (this process
         # has not touched the GPU yet) and pass the child's JSON line through
@@ -747,7 +806,8 @@ def main() -> int:
     out = measure(args.rows, args.cols, args.seed, args.sparse_per_col, args.price, args.numerics,
                   args.steps, args.warmup, late_pivots, deep_pivots, whole,
                   mfma_block=late_pivots > 0 and not args.no_mfma,
-                  end_pivots=args.end_pivots if (whole and deep_pivots > 0) else 0, warm_k=args.warm_k)
+                  end_pivots=args.end_pivots if (whole and deep_pivots > 0) else 0, warm_k=args.warm_k,
+                  dump_dir=args.dump_outputs)
     if "mfma" in out and mfma_wanted:
         # config 3 is named after this: the refactorisation of the FULL basis (k = m = 8192), timed
         # unprofiled, and its MFMA utilisation from the counters of the child run above

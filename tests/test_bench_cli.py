@@ -1,10 +1,13 @@
 """bench.py host logic that needs no GPU: what rides along with which invocation, profiler
-detection, and the loud failure when there is no device."""
+detection, the loud failure when there is no device, and what --dump-outputs writes; one gpu-marked
+test runs --dump-outputs end to end."""
 import argparse
 import importlib.util
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -117,3 +120,100 @@ def test_event_stride_rides_in_the_profile_word():
 
     bench.EVENT_STRIDE = 8
     assert bench.price_profile() == (1 << _ffi.K_PRICE) | (8 << 16)
+
+
+def _fake_result(m, q, iterations, seed=0):
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    pivots = [(int(rng.integers(0, 3)), int(rng.integers(0, m + q)), int(rng.integers(0, m)), float(rng.normal()))
+              for _ in range(iterations)]
+    return argparse.Namespace(x=rng.normal(size=m), xbar=rng.normal(size=m), z=rng.normal(size=q),
+                              zbar=rng.normal(size=q), basis=rng.permutation(m + q)[:m].astype(np.int64),
+                              nonbasis=rng.permutation(m + q)[:q].astype(np.int64), objective=float(rng.normal()),
+                              pivots=pivots, margins=rng.uniform(size=iterations), iterations=iterations)
+
+
+def test_dump_outputs_writes_the_timed_steps_result_in_float64(tmp_path):
+    """--dump-outputs: every array a caller of the timed path receives, float64, the pivot log cut to
+    the timed steps; indices exact."""
+    import numpy as np
+
+    bench = _bench()
+    res = _fake_result(m=40, q=70, iterations=25)
+    info = bench.dump_outputs(str(tmp_path), res, first_pivot=10)
+    names = {"x", "xbar", "z", "zbar", "basis", "nonbasis", "objective", "pivots", "margins"}
+    assert set(info["files"]) == {n + ".npy" for n in names} and info["sampled"] is None
+    assert {p.name for p in tmp_path.iterdir()} == set(info["files"])
+    got = {n: np.load(tmp_path / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float64 for v in got.values())
+    for n in ("x", "xbar", "z", "zbar", "margins"):
+        want = getattr(res, n)[10:] if n == "margins" else getattr(res, n)
+        assert np.array_equal(got[n], want), n
+    assert np.array_equal(got["basis"].astype(np.int64), res.basis)
+    assert np.array_equal(got["nonbasis"].astype(np.int64), res.nonbasis)
+    assert got["objective"].tolist() == [res.objective]
+    assert got["pivots"].shape == (15, 4) and got["pivots"].tolist() == [list(p) for p in res.pivots[10:]]
+    assert info["timed_pivots"] == 15 and info["bytes"] == sum(v.nbytes for v in got.values())
+
+
+def test_dump_outputs_samples_a_large_result_into_its_budget(tmp_path):
+    """Above the budget every array over its share keeps a fixed, seeded sample of its rows in
+    ascending order, positions beside it; the same result gives the same files."""
+    import numpy as np
+
+    bench = _bench()
+    res = _fake_result(m=3000, q=5000, iterations=2000, seed=1)
+    budget = 64 << 10
+    a = bench.dump_outputs(str(tmp_path / "a"), res, 0, budget=budget)
+    b = bench.dump_outputs(str(tmp_path / "b"), res, 0, budget=budget)
+    assert a["files"] == b["files"] and a["bytes"] == b["bytes"] <= budget
+    assert sum((tmp_path / "a" / f).stat().st_size for f in a["files"]) <= budget
+    assert set(a["sampled"]) >= {"x", "z", "zbar", "pivots"} and "objective" not in a["sampled"]
+    for f in a["files"]:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    for name in a["sampled"]:
+        idx = np.load(tmp_path / "a" / f"{name}_index.npy").astype(np.int64)
+        assert np.all(np.diff(idx) > 0) and idx[-1] < a["sampled"][name]["rows"]
+        full = np.asarray(res.pivots if name == "pivots" else getattr(res, name), dtype=np.float64)
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), full[idx]), name
+
+
+@pytest.mark.gpu
+def test_bench_dumps_the_timed_paths_outputs_the_same_on_every_run(tmp_path):
+    """bench.py --steps K --dump-outputs DIR: exactly K timed pivots, `ms_per_step` in the line, and
+    the files are what a Solver on the same seeded LP returns after the same warm-up + K pivots --
+    bit for bit, and the same from one run to the next."""
+    import json
+
+    import numpy as np
+
+    from dantzig_amd import core
+
+    rows, cols, seed, steps, warmup = 256, 512, 1003, 40, 10
+    lines = []
+    for run_dir in ("a", "b"):
+        run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps),
+                              "--warmup", str(warmup), "--rows", str(rows), "--cols", str(cols), "--seed", str(seed),
+                              "--no-pmc-traffic", "--no-cpu-baseline", "--no-secondary", "--no-late",
+                              "--dump-outputs", str(tmp_path / run_dir)],
+                             capture_output=True, text=True, timeout=300)
+        assert run.returncode == 0, run.stderr[-2000:]
+        lines.append(json.loads(run.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == steps and line["warmup"] == warmup and line["ms_per_step"] > 0
+        assert line["dump_outputs"]["timed_pivots"] == steps and line["dump_outputs"]["sampled"] is None
+    files = lines[0]["dump_outputs"]["files"]
+    assert files == lines[1]["dump_outputs"]["files"]
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f), equal_nan=True), f
+
+    a, b, c = core.gen_dense_lp(seed=seed, m=rows, n_struct=cols)
+    with core.Solver(core.CoreLP.from_inequality_form(a, b, c), numerics=core.FAST, poll_interval=50) as s:
+        assert s.run(warmup) == "iter_limit" and s.run(steps) == "iter_limit"
+        want = s.result()
+    assert want.iterations == warmup + steps
+    for name in ("x", "xbar", "z", "zbar", "basis", "nonbasis"):
+        assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), getattr(want, name).astype(np.float64)), name
+    assert np.load(tmp_path / "a" / "objective.npy").tolist() == [want.objective]
+    assert np.load(tmp_path / "a" / "pivots.npy").tolist() == [list(map(float, p)) for p in want.pivots[warmup:]]
