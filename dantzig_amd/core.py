@@ -254,6 +254,17 @@ class Solver:
         """FAST: rebuild the basis inverse from scratch now (blocked LU + MFMA GEMMs)."""
         _ffi.check(_ffi.lib().dzg_solver_refactor(self._h), "dzg_solver_refactor")
 
+    def debug_inverse(self, row0: int, row1: int) -> tuple[np.ndarray, dict]:
+        """Test hook (dzg_debug_basis_inverse): rows [row0, row1) of the basis inverse FAST keeps --
+        row i is basis position row0 + i, column r constraint row r -- and
+        {k, neta, rows: the (first, end) rows this solver keeps}."""
+        m = self._lp.m
+        out = np.zeros((max(int(row1) - int(row0), 0), m))
+        info = np.zeros(4, np.int64)
+        _ffi.check(_ffi.lib().dzg_debug_basis_inverse(self._h, int(row0), int(row1), ptr(out), ptr(info)),
+                   "dzg_debug_basis_inverse")
+        return out, dict(k=int(info[0]), neta=int(info[1]), rows=(int(info[2]), int(info[3])))
+
     def close(self) -> None:
         if self._h:
             _ffi.lib().dzg_solver_destroy(self._h)

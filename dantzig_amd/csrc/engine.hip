@@ -1945,6 +1945,125 @@ extern "C" int64_t dzg_debug_rl_listed(dzg_solver *s)
     return s->h_ctl->rl_listed;
 }
 
+// Test hook: rows [row0, row1) of the basis inverse FAST keeps, assembled on the host from device
+// copies of what the kernels read -- dense: Binv0 (compact columns drow / dslot, unit columns of the
+// basic slacks by bcode) minus U W^T; sparse basis: X - Ub^T Wc on the structural positions and
+// e_r - A[r, S] (X - Ub^T Wc) on the basic slack of row r (the device's lists bcnt / bcol / bval).
+// Row p is basis position p, column r constraint row r; out is row-major (row1 - row0) x m.
+extern "C" int dzg_debug_basis_inverse(dzg_solver *s, int64_t row0, int64_t row1, double *out,
+                                       int64_t info[4])
+{
+    if (!s || !info || (row1 > row0 && !out)) return fail(DZG_E_ARG, "NULL argument");
+    if (s->numerics != DZG_NUMERICS_FAST) return fail(DZG_E_ARG, "basis inverse: FAST numerics only");
+    const DzgDev &d = s->d;
+    const int m = d.m;
+    const int lo = d.rs ? d.rs_r0 : 0, hi = d.rs ? d.rs_r1 : m;
+    if (row0 < lo || row1 > hi || row0 > row1)
+        return fail(DZG_E_ARG, "basis inverse: rows outside [" + std::to_string(lo) + ", " +
+                                   std::to_string(hi) + ")");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    const int k = s->h_ctl->ncompact, neta = s->h_ctl->neta;
+    info[0] = k;
+    info[1] = neta;
+    info[2] = lo;
+    info[3] = hi;
+    const size_t nr = (size_t)(row1 - row0), mm = (size_t)m;
+    if (nr == 0) return 0;
+    if (k < 0 || k > m || neta < 0 || neta > DZG_RMAX)
+        return fail(DZG_E_DEVICE, "basis inverse: control block out of range");
+    const size_t ldb = (size_t)d.ldb, ldw = (size_t)d.ldw;
+    std::vector<int> drow(mm), dslot(mm);
+    std::vector<double> U((size_t)neta * ldw + 1), W((size_t)neta * ldw + 1);
+    HIP_OK(hipMemcpy(drow.data(), d.drow, sizeof(int) * mm, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(dslot.data(), d.dslot, sizeof(int) * mm, hipMemcpyDeviceToHost));
+    for (int c = 0; c < k; ++c)
+        if (drow[(size_t)c] < 0 || drow[(size_t)c] >= m) return fail(DZG_E_DEVICE, "basis inverse: drow out of range");
+    if (neta) {
+        HIP_OK(hipMemcpy(U.data(), d.U, sizeof(double) * (size_t)neta * ldw, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(W.data(), d.W, sizeof(double) * (size_t)neta * ldw, hipMemcpyDeviceToHost));
+    }
+    std::fill(out, out + nr * mm, 0.0);
+    if (!d.spb) {
+        std::vector<int> bcode(mm);
+        HIP_OK(hipMemcpy(bcode.data(), d.bcode, sizeof(int) * mm, hipMemcpyDeviceToHost));
+        // (a row-sharded rank's allocation starts at its first row: d.binv points rs_r0 rows before it)
+        const double *base = d.binv + (d.rs ? (long long)d.rs_r0 * d.ldb : 0);
+        std::vector<double> b0(nr * ldb);
+        HIP_OK(hipMemcpy(b0.data(), base + (size_t)(row0 - lo) * ldb, sizeof(double) * nr * ldb,
+                         hipMemcpyDeviceToHost));
+        for (size_t i = 0; i < nr; ++i) {
+            const size_t p = (size_t)row0 + i;
+            double *o = out + i * mm;
+            for (int c = 0; c < k; ++c) o[drow[(size_t)c]] = b0[i * ldb + (size_t)c];
+            if (bcode[p] < 0) o[(size_t)(-1 - bcode[p])] = 1.0;
+            for (size_t r = 0; r < mm; ++r) {
+                double acc = 0.0;
+                for (int t = 0; t < neta; ++t) acc += U[(size_t)t * ldw + p] * W[(size_t)t * ldw + r];
+                o[r] -= acc;
+            }
+        }
+        return 0;
+    }
+    // sparse basis: X (k x k, row b = basis position spos[b], column c = constraint row drow[c])
+    std::vector<int> sslot(mm), rowpos(mm), bcnt(mm), bslot((size_t)(d.ns ? d.ns : 1));
+    std::vector<long long> rptr(mm + 1);
+    HIP_OK(hipMemcpy(sslot.data(), d.sslot, sizeof(int) * mm, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rowpos.data(), d.rowpos, sizeof(int) * mm, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(bcnt.data(), d.bcnt, sizeof(int) * mm, hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(bslot.data(), d.bslot, sizeof(int) * (size_t)(d.ns ? d.ns : 1), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(rptr.data(), d.rptr, sizeof(long long) * (mm + 1), hipMemcpyDeviceToHost));
+    const size_t nnz = (size_t)rptr[mm];
+    std::vector<int> bcol(nnz + 1);
+    std::vector<double> bval(nnz + 1), X((size_t)k * ldb + 1);
+    if (nnz) {
+        HIP_OK(hipMemcpy(bcol.data(), d.bcol, sizeof(int) * nnz, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(bval.data(), d.bval, sizeof(double) * nnz, hipMemcpyDeviceToHost));
+    }
+    if (k) HIP_OK(hipMemcpy(X.data(), d.binv, sizeof(double) * (size_t)k * ldb, hipMemcpyDeviceToHost));
+    // the effective X row by row, on first need
+    std::vector<double> Xe((size_t)k * (size_t)k);
+    std::vector<char> done((size_t)k, 0);
+    auto xrow = [&](int b) -> const double * {
+        double *e = Xe.data() + (size_t)b * (size_t)k;
+        if (!done[(size_t)b]) {
+            for (int c = 0; c < k; ++c) {
+                double acc = 0.0;
+                for (int t = 0; t < neta; ++t)
+                    acc += U[(size_t)t * ldw + (size_t)b] * W[(size_t)t * ldw + (size_t)c];
+                e[c] = X[(size_t)b * ldb + (size_t)c] - acc;
+            }
+            done[(size_t)b] = 1;
+        }
+        return e;
+    };
+    std::vector<int> slack_row(mm, -1); // basis position -> the constraint row of its basic slack
+    for (size_t r = 0; r < mm; ++r)
+        if (rowpos[r] >= 0 && rowpos[r] < m) slack_row[(size_t)rowpos[r]] = (int)r;
+    for (size_t i = 0; i < nr; ++i) {
+        const size_t p = (size_t)row0 + i;
+        double *o = out + i * mm;
+        const int b = sslot[p];
+        if (b >= 0) {
+            if (b >= k) return fail(DZG_E_DEVICE, "basis inverse: sslot out of range");
+            const double *e = xrow(b);
+            for (int c = 0; c < k; ++c) o[drow[(size_t)c]] = e[c];
+            continue;
+        }
+        const int r = slack_row[p];
+        if (r < 0) return fail(DZG_E_DEVICE, "basis inverse: position without a variable");
+        o[(size_t)r] = 1.0;
+        for (int j = 0; j < bcnt[(size_t)r]; ++j) {
+            const size_t at = (size_t)rptr[(size_t)r] + (size_t)j;
+            const int bb = bslot[(size_t)bcol[at]];
+            if (bb < 0 || bb >= k) return fail(DZG_E_DEVICE, "basis inverse: bslot out of range");
+            const double *e = xrow(bb);
+            for (int c = 0; c < k; ++c) o[drow[(size_t)c]] -= bval[at] * e[c];
+        }
+    }
+    return 0;
+}
+
 extern "C" int dzg_solver_result(dzg_solver *s, dzg_result *res)
 {
     if (!s || !res) return fail(DZG_E_ARG, "NULL argument");

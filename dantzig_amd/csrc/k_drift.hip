@@ -3,8 +3,10 @@
 //
 // FAST numerics carries x, xbar, z, zbar from pivot to pivot (src/simplex.rs:262-265 does the same:
 // the reference never recomputes them either, but its rounding is not FAST's).  The health monitor
-// (max_pivot_error) watches the INVERSE -- dx_p from FTRAN against -dz_r from BTRAN + pricing --
-// and a fresh inverse resets it; the carried vectors keep whatever rounding they have accumulated
+// (max_pivot_error) compares dx_p from FTRAN with -dz_r from BTRAN + pricing: two evaluation orders
+// of the same bilinear form e_p^T Binv a_q, so it measures their disagreement -- rounding growth in
+// the inverse's use -- and agrees for any matrix in Binv; that Binv is B^-1 is checked by the
+// residual test (tests/test_gpu_inverse.py).  A fresh inverse resets it; the carried vectors keep whatever rounding they have accumulated
 // (mu of FAST and STRICT differ by 5e-12 after 1 750 pivots at 8192 rows while the
 // monitor reads 8e-14).  Right after a refactorisation the eta file is empty and the inverse is as
 // good as it gets, so the state can be recomputed from the data:

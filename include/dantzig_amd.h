@@ -505,6 +505,13 @@ int64_t dzg_debug_live_lists(dzg_solver *s, int64_t *entries);
  * been executed yet (a run that stopped between BTRAN and the pivot, DZG_NEAR_TIE in a dual step's
  * ratio test), -1 if none; < -1 on error.  dzg_debug_live_lists counts that row as listed. */
 int64_t dzg_debug_rl_listed(dzg_solver *s);
+/* Test hook (tests/test_gpu_inverse.py): rows [row0, row1) of the basis inverse a FAST solver keeps,
+ * B^-1 = Binv0 - U W^T (dense) or its sparse-basis form, assembled on the host from device copies of
+ * the buffers the kernels read.  Row i of `out` is basis position row0 + i, column r constraint row
+ * r; row-major, (row1 - row0) x m.  info = {ncompact (k), pending etas, first and end row this
+ * solver keeps (a row-sharded rank: its slice; rows outside it are DZG_E_ARG)}.  STRICT: DZG_E_ARG.
+ * No solve path calls it. */
+int dzg_debug_basis_inverse(dzg_solver *s, int64_t row0, int64_t row1, double *out, int64_t info[4]);
 
 /* Deterministic max-loc merge: largest ratio wins, lowest global position on ties --
  * the sequential first-wins rule of src/simplex.rs:432-435,456-459.  Returns the index

@@ -400,11 +400,13 @@ def test_fast_refactor_keeps_pivot_sequence(core, seed, m, ns, interval):
 def test_refactorisation_at_every_panel_shape(core, m, k):
     """The factorisation of a basis with exactly k structural columns -- one narrow panel, full
     panels, a pair with a narrow second panel, pairs followed by a single panel (k_refactor.hip) --
-    checked on what it is for: 48 pivots on the fresh inverse with the pivot element computed
-    twice, by FTRAN (rows of the inverse times the entering column) and by BTRAN + pricing (row p of
-    the inverse against the matrix); they agree to rounding only if the inverse is the inverse.
-    x and z are arbitrary (x > 0 > z: the method has work to do); the refactorisation does not
-    look at them."""
+    then 48 pivots on the fresh inverse with the pivot element computed twice, by FTRAN (rows of the
+    inverse times the entering column) and by BTRAN + pricing (row p of the inverse against the
+    matrix).  The two are evaluation orders of the same bilinear form e_p^T Binv a_q and agree to
+    rounding for ANY matrix in the inverse's storage: this watches rounding growth, not whether the
+    inverse is B^-1.  That is checked by the residual B^-1 B - I in tests/test_gpu_inverse.py (the same
+    panel shapes on scattered bases).  x and z are arbitrary (x > 0 > z: the method has work to do);
+    the refactorisation does not look at them."""
     ns = 2 * m
     a, b, c = core.gen_dense_lp(seed=300 + k, m=m, n_struct=ns)
     basis = np.concatenate([np.arange(k), ns + np.arange(k, m)]).astype(np.int64)
