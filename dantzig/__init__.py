@@ -11,7 +11,7 @@ import sys as _sys
 
 import dantzig_amd as _impl
 from dantzig_amd import (Max, Maximize, Min, Minimize, Var, Variable, exceptions, model,  # noqa: F401
-                         optimize, rust)
+                         optimize, rust, solve_many)
 
 # submodules under the reference's names: `import dantzig.rust`, `from dantzig.model import ...`
 for _name in ("rust", "model", "optimize", "exceptions"):

@@ -38,8 +38,10 @@ EXPORTS = [
     "dzg_gen_dense_lp_block", "dzg_solver_set_profile", "dzg_kernel_neg_t_dot_csc",
     "dzg_shard_comm_size", "dzg_solver_upload_columns", "dzg_debug_hold_cus", "dzg_debug_hold_wait",
     "dzg_core_solve_full_csc", "dzg_debug_live_lists", "dzg_debug_rl_listed",
-    "dzg_debug_basis_inverse",
+    "dzg_debug_basis_inverse", "dzg_batch_solve", "dzg_model_solve_batch",
 ]
+
+BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
 
 
 class Lp(C.Structure):
@@ -171,6 +173,8 @@ def lib() -> C.CDLL:
         _lib.dzg_debug_live_lists.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_debug_basis_inverse.restype = C.c_int
         _lib.dzg_debug_basis_inverse.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_solve.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.dzg_model_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.dzg_solver_upload_columns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                    C.c_int64]
     return _lib

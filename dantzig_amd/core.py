@@ -165,6 +165,32 @@ def _counters(r) -> dict:
                 price_rows_copy=int(r.price_rows_copy), state_drift=float(r.state_drift))
 
 
+def _c_lp(lp: CoreLP):
+    """The dzg_lp of a CoreLP, and the arrays its pointers refer to (keep them alive)."""
+    m, ns, n = lp.m, lp.n_struct, lp.n
+    # column-major m x ns == C-contiguous (ns, m)
+    a_cm = None if lp.a is None else np.ascontiguousarray(np.asarray(lp.a, dtype=np.float64).T)
+    k = dict(a=a_cm, c=f64(lp.c), basis=i64(lp.basis), nonbasis=i64(lp.nonbasis),
+             x=f64(lp.x), z=f64(lp.z),
+             var_col=None if lp.var_col is None else i64(lp.var_col),
+             col_ptr=None if lp.col_ptr is None else i64(lp.col_ptr),
+             row_idx=None if lp.row_idx is None
+             else np.ascontiguousarray(lp.row_idx, dtype=np.int32),
+             val=None if lp.val is None else f64(lp.val),
+             xbar=None if lp.xbar is None else f64(lp.xbar),
+             zbar=None if lp.zbar is None else f64(lp.zbar))
+    if len(k["basis"]) != m or len(k["x"]) != m or len(k["nonbasis"]) != n - m \
+            or len(k["z"]) != n - m \
+            or (k["xbar"] is not None and len(k["xbar"]) != m) \
+            or (k["zbar"] is not None and len(k["zbar"]) != n - m):
+        raise ValueError("CoreLP vectors do not match (m, n)")
+    c_lp = _ffi.Lp(m, n, ns, ptr(a_cm), max(m, 1), ptr(k["var_col"]), ptr(k["c"]),
+                   float(lp.constant), ptr(k["basis"]), ptr(k["nonbasis"]),
+                   ptr(k["x"]), ptr(k["z"]), ptr(k["col_ptr"]), ptr(k["row_idx"]),
+                   ptr(k["val"]), ptr(k["xbar"]), ptr(k["zbar"]))
+    return c_lp, k
+
+
 class Solver:
     """One LP resident on one GPU.  create -> run (repeatable, budgeted) -> result."""
 
@@ -178,28 +204,7 @@ class Solver:
         """Marshals the LP and the options into their C structs (no device work)."""
         _ffi.require_gpu()
         self._lp = lp
-        m, ns, n = lp.m, lp.n_struct, lp.n
-        # column-major m x ns == C-contiguous (ns, m)
-        a_cm = None if lp.a is None else np.ascontiguousarray(np.asarray(lp.a, dtype=np.float64).T)
-        self._keep = dict(a=a_cm, c=f64(lp.c), basis=i64(lp.basis), nonbasis=i64(lp.nonbasis),
-                          x=f64(lp.x), z=f64(lp.z),
-                          var_col=None if lp.var_col is None else i64(lp.var_col),
-                          col_ptr=None if lp.col_ptr is None else i64(lp.col_ptr),
-                          row_idx=None if lp.row_idx is None
-                          else np.ascontiguousarray(lp.row_idx, dtype=np.int32),
-                          val=None if lp.val is None else f64(lp.val),
-                          xbar=None if lp.xbar is None else f64(lp.xbar),
-                          zbar=None if lp.zbar is None else f64(lp.zbar))
-        k = self._keep
-        if len(k["basis"]) != m or len(k["x"]) != m or len(k["nonbasis"]) != n - m \
-                or len(k["z"]) != n - m \
-                or (k["xbar"] is not None and len(k["xbar"]) != m) \
-                or (k["zbar"] is not None and len(k["zbar"]) != n - m):
-            raise ValueError("CoreLP vectors do not match (m, n)")
-        self._c_lp = _ffi.Lp(m, n, ns, ptr(a_cm), max(m, 1), ptr(k["var_col"]), ptr(k["c"]),
-                             float(lp.constant), ptr(k["basis"]), ptr(k["nonbasis"]),
-                             ptr(k["x"]), ptr(k["z"]), ptr(k["col_ptr"]), ptr(k["row_idx"]),
-                             ptr(k["val"]), ptr(k["xbar"]), ptr(k["zbar"]))
+        self._c_lp, self._keep = _c_lp(lp)
         if lp.block is not None:
             if (opts.get("col_begin"), opts.get("col_end")) != tuple(lp.block):
                 raise ValueError("a column-block LP needs a sharded solver on exactly that block")
@@ -317,6 +322,77 @@ def core_solve(lp: CoreLP, log_cap: int = 1 << 20, **opts) -> CoreResult:
             basis=basis[:m].copy(), nonbasis=nonbasis[:q].copy(), x=x[:m].copy(),
             xbar=xbar[:m].copy(), z=z[:q].copy(), zbar=zbar[:q].copy(), pivots=pivots,
             margins=margins[:cnt].copy(), **_counters(r))
+
+
+_PIVOT_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("entering", "<i8"),
+                         ("leaving", "<i8"), ("mu", "<f8")])
+
+
+def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
+                **opts) -> list:
+    """dzg_batch_solve: every LP of `lps` in STRICT numerics, one workgroup per LP, in one call.
+
+    The whole batch is checked on the host first (ValueError: more than 128 rows, CSC input, FAST
+    numerics, a column-block LP, vectors that do not match (m, n)); nothing reaches the device
+    before that.  Result i is LP i's CoreResult, as `solve(lp, numerics=STRICT)` reports it; its
+    solve_ms is the wall time of the whole batch call.  A result resumes through resumed_from, in a
+    batch or in a single Solver."""
+    import time
+
+    lps = list(lps)
+    numerics = opts.get("numerics", AUTO)
+    if numerics not in (STRICT, AUTO):
+        raise ValueError("solve_batch runs STRICT numerics only (numerics=STRICT or AUTO)")
+    for i, lp in enumerate(lps):
+        if lp.block is not None:
+            raise ValueError(f"lps[{i}]: a column-block LP cannot be batched")
+        if lp.a is None and lp.n_struct > 0:
+            raise ValueError(f"lps[{i}]: CSC input cannot be batched (dense `a` only)")
+        if lp.m > _ffi.BATCH_MAX_ROWS:
+            raise ValueError(f"lps[{i}]: {lp.m} rows; the batch takes at most {_ffi.BATCH_MAX_ROWS}")
+    marshalled = [_c_lp(lp) for lp in lps]
+    count = len(lps)
+    c_lps = (_ffi.Lp * max(count, 1))(*[c for c, _ in marshalled])
+    ms = [lp.m for lp in lps]
+    qs = [lp.n - lp.m for lp in lps]
+    mo = np.concatenate([[0], np.cumsum(ms)]).astype(np.int64)
+    qo = np.concatenate([[0], np.cumsum(qs)]).astype(np.int64)
+    basis, x, xbar = np.zeros(mo[-1] + 1, np.int64), np.zeros(mo[-1] + 1), np.zeros(mo[-1] + 1)
+    nonbasis, z, zbar = np.zeros(qo[-1] + 1, np.int64), np.zeros(qo[-1] + 1), np.zeros(qo[-1] + 1)
+    cap = int(log_cap) if log else 0
+    logs = np.zeros((count, max(cap, 1)), dtype=_PIVOT_DTYPE)
+    res = (_ffi.Result * max(count, 1))()
+    for i in range(count):
+        r = res[i]
+        r.basis = basis.ctypes.data + 8 * int(mo[i])
+        r.x = x.ctypes.data + 8 * int(mo[i])
+        r.xbar = xbar.ctypes.data + 8 * int(mo[i])
+        r.nonbasis = nonbasis.ctypes.data + 8 * int(qo[i])
+        r.z = z.ctypes.data + 8 * int(qo[i])
+        r.zbar = zbar.ctypes.data + 8 * int(qo[i])
+        r.log = logs.ctypes.data + logs.strides[0] * i if cap > 0 else None
+        r.log_cap = cap
+    o = _ffi.default_opts(**opts)
+    t0 = time.perf_counter()
+    rc = _ffi.lib().dzg_batch_solve(c_lps, C.c_int64(count), C.byref(o),
+                                    C.c_int64(int(pivots_per_launch)), res)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    _ffi.check(rc, "dzg_batch_solve")
+    out = []
+    for i in range(count):
+        r = res[i]
+        cnt = int(min(r.iterations, cap))
+        arr = logs[i, :cnt]
+        pivots = list(zip(arr["kind"].tolist(), arr["entering"].tolist(), arr["leaving"].tolist(),
+                          arr["mu"].tolist()))
+        a0, a1, b0, b1 = int(mo[i]), int(mo[i + 1]), int(qo[i]), int(qo[i + 1])
+        out.append(CoreResult(
+            status=STATUS_NAMES.get(r.status, str(r.status)), status_code=r.status,
+            numerics="strict", iterations=int(r.iterations), objective=float(r.objective),
+            basis=basis[a0:a1].copy(), nonbasis=nonbasis[b0:b1].copy(), x=x[a0:a1].copy(),
+            xbar=xbar[a0:a1].copy(), z=z[b0:b1].copy(), zbar=zbar[b0:b1].copy(), pivots=pivots,
+            solve_ms=wall_ms, **_counters(r)))
+    return out
 
 
 def core_solve_full_csc(m: int, n: int, col_ptr, row_idx, val, c, constant, basis, nonbasis, x, z,

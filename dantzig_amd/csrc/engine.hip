@@ -203,6 +203,11 @@ static int validate(const dzg_lp *lp, std::string &why)
     return 1;
 }
 
+// For the other translation units of the library (k_batch.hip, model.cpp): the same checks and
+// the same error slot as the entry points here.
+int dzg_set_error(int code, const std::string &msg) { return fail(code, msg); }
+int dzg_lp_valid(const dzg_lp *lp, std::string &why) { return validate(lp, why); }
+
 // ---- RCCL, loaded lazily: single-GPU users never need librccl ------------------------
 namespace {
 struct NcclUniqueId { char internal[128]; };

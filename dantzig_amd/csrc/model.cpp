@@ -203,6 +203,25 @@ void build(const dzg_model *md, Built &out, bool allow_sparse)
         }
 }
 
+// Simplex::solution, src/simplex.rs:354-371: x+ - x- per user variable from the final basis
+void solution_values(const dzg_model *md, const Built &b, const int64_t *basis, const double *x,
+                     double *values)
+{
+    std::vector<int64_t> pos_of((size_t)(b.n ? b.n : 1), -1);
+    for (int64_t p = 0; p < b.m; ++p) pos_of[(size_t)basis[p]] = p;
+    for (int64_t u = 0; u < md->nvars; ++u) {
+        if (b.pos_var[(size_t)u] < 0) {
+            values[u] = 0.0; // unknown variable, src/pyobjs.rs:163-165
+            continue;
+        }
+        const int64_t pp = pos_of[(size_t)b.pos_var[(size_t)u]];
+        const int64_t pn = pos_of[(size_t)b.neg_var[(size_t)u]];
+        const double pos = pp >= 0 ? x[(size_t)pp] : 0.0;
+        const double neg = pn >= 0 ? x[(size_t)pn] : 0.0;
+        values[u] = pos - neg;
+    }
+}
+
 } // namespace
 
 extern "C" int dzg_build_standard_form(const dzg_model *md, dzg_stdform *out)
@@ -279,20 +298,88 @@ extern "C" int dzg_model_solve(const dzg_model *md, const dzg_opts *opts, dzg_mo
     res->near_ties = r.near_ties;
     res->first_near_tie = r.first_near_tie;
     if (rc < 0) return rc;
-    if (res->values) { // Simplex::solution, src/simplex.rs:354-371
-        std::vector<int64_t> pos_of((size_t)(b.n ? b.n : 1), -1);
-        for (int64_t p = 0; p < b.m; ++p) pos_of[(size_t)basis[(size_t)p]] = p;
-        for (int64_t u = 0; u < md->nvars; ++u) {
-            if (b.pos_var[(size_t)u] < 0) {
-                res->values[u] = 0.0; // unknown variable, src/pyobjs.rs:163-165
-                continue;
-            }
-            const int64_t pp = pos_of[(size_t)b.pos_var[(size_t)u]];
-            const int64_t pn = pos_of[(size_t)b.neg_var[(size_t)u]];
-            const double pos = pp >= 0 ? x[(size_t)pp] : 0.0;
-            const double neg = pn >= 0 ? x[(size_t)pn] : 0.0;
-            res->values[u] = pos - neg;
-        }
-    }
+    if (res->values) solution_values(md, b, basis.data(), x.data(), res->values);
     return r.status;
+}
+
+int dzg_set_error(int code, const std::string &msg); // engine.hip
+
+// The batch form of dzg_model_solve.  The routing rule lives here and only here: a model that
+// dzg_model_solve would solve in STRICT numerics (STRICT asked for, or AUTO at m <= auto_strict_rows)
+// on a dense block of at most DZG_BATCH_MAX_ROWS rows goes into one dzg_batch_solve call; every
+// other model goes through dzg_model_solve by itself.  The standard form and the values are
+// extracted exactly as dzg_model_solve extracts them.
+extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                     dzg_model_result *res)
+{
+    if (count < 0) return dzg_set_error(DZG_E_ARG, "model batch: count < 0");
+    if (count > 0 && (!models || !res)) return dzg_set_error(DZG_E_ARG, "model batch: models or res is NULL");
+    for (int64_t i = 0; i < count; ++i)
+        if (!valid(&models[i]))
+            return dzg_set_error(DZG_E_ARG, "model batch: models[" + std::to_string(i) + "] is malformed");
+    dzg_opts o;
+    if (opts) o = *opts; else dzg_opts_default(&o);
+    const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
+    std::vector<Built> built((size_t)count);
+    std::vector<int64_t> batched;
+    for (int64_t i = 0; i < count; ++i) {
+        Built &b = built[(size_t)i];
+        build(&models[i], b, true);
+        const bool strict = o.numerics == DZG_NUMERICS_STRICT ||
+                            (o.numerics == DZG_NUMERICS_AUTO && b.m <= strict_rows);
+        if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS) batched.push_back(i);
+    }
+    const size_t nb = batched.size();
+    std::vector<dzg_lp> lps(nb);
+    std::vector<dzg_result> rs(nb);
+    std::vector<std::vector<int64_t>> basis(nb);
+    std::vector<std::vector<double>> x(nb);
+    for (size_t k = 0; k < nb; ++k) {
+        const Built &b = built[(size_t)batched[k]];
+        dzg_lp &lp = lps[k];
+        std::memset(&lp, 0, sizeof(lp));
+        lp.m = b.m;
+        lp.n = b.n;
+        lp.n_struct = b.ns;
+        lp.a = b.a.data();
+        lp.lda = b.m > 0 ? b.m : 1;
+        lp.var_col = b.var_col.data();
+        lp.c = b.c.data();
+        lp.constant = b.constant;
+        lp.basis = b.basis.data();
+        lp.nonbasis = b.nonbasis.data();
+        lp.x = b.x.data();
+        lp.z = b.z.data();
+        basis[k].assign((size_t)(b.m ? b.m : 1), 0);
+        x[k].assign((size_t)(b.m ? b.m : 1), 0.0);
+        std::memset(&rs[k], 0, sizeof(dzg_result));
+        rs[k].basis = basis[k].data();
+        rs[k].x = x[k].data();
+    }
+    if (nb > 0) {
+        const int rc = dzg_batch_solve(lps.data(), (int64_t)nb, &o, 0, rs.data());
+        if (rc < 0) return rc;
+    }
+    size_t k = 0;
+    for (int64_t i = 0; i < count; ++i) {
+        dzg_model_result &out = res[i];
+        if (k < nb && batched[k] == i) {
+            const Built &b = built[(size_t)i];
+            const dzg_result &r = rs[k];
+            out.status = r.status;
+            out.numerics_used = r.numerics_used;
+            out.iterations = r.iterations;
+            out.objective = r.objective;
+            out.m = b.m;
+            out.n = b.n;
+            out.near_ties = r.near_ties;
+            out.first_near_tie = r.first_near_tie;
+            if (out.values) solution_values(&models[i], b, basis[k].data(), x[k].data(), out.values);
+            ++k;
+            continue;
+        }
+        const int rc = dzg_model_solve(&models[i], opts, &out);
+        if (rc < 0) return rc;
+    }
+    return 0;
 }

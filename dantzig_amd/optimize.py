@@ -59,11 +59,12 @@ class Optimize(abc.ABC):
     def _core_objective(self) -> AffExpr:
         return -self.objective if self.sense == "minimize" else self.objective
 
+    def _rust_problem(self):
+        return self._core_objective().to_rust_affexpr(), list(self.yield_rust_inequalities())
+
     def solve(self) -> Solution:
         """Solve on the GPU.  Raises exceptions.UnboundedError / InfeasibleError."""
-        objective = self._core_objective().to_rust_affexpr()
-        inequalities = list(self.yield_rust_inequalities())
-        return Solution(solution=rs.solve(objective, inequalities), sense=self.sense)
+        return Solution(solution=rs.solve(*self._rust_problem()), sense=self.sense)
 
 
 class Minimize(Optimize):
@@ -80,3 +81,18 @@ class Maximize(Optimize):
     """max objective  s.t. constraints."""
 
     sense = property(lambda self: "maximize")
+
+
+def solve_many(problems, *, return_exceptions: bool = False) -> list:
+    """[p.solve() for p in problems] in one batched call (rust.solve_many): the small models share
+    one launch on the GPU, one workgroup per model, bit for bit what p.solve() returns.  A model
+    that is unbounded or infeasible raises the exception p.solve() raises, with the model's index
+    in the message, after the whole batch is done; with return_exceptions=True the exception
+    instance stands in that model's place."""
+    problems = list(problems)
+    for i, p in enumerate(problems):
+        if not isinstance(p, Optimize):
+            raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
+    raw = rs.solve_many([p._rust_problem() for p in problems], return_exceptions=return_exceptions)
+    return [r if isinstance(r, Exception) else Solution(solution=r, sense=p.sense)
+            for p, r in zip(problems, raw)]

@@ -198,6 +198,29 @@ def _c_model(a: dict) -> _ffi.Model:
                       a["ncons"], p(a["con_ptr"]), p(a["con_var"]), p(a["con_coef"]), p(a["con_b"]))
 
 
+def _outcome(res, values, order, where: str = "", stacklevel: int = 4):
+    """The PySolution of one dzg_model_result, or the exception the reference raises for it."""
+    rc = int(res.status)
+    if rc == _ffi.UNBOUNDED:
+        return UnboundedError("The objective is unbounded" + where)      # src/lib.rs:24
+    if rc == _ffi.INFEASIBLE:
+        return InfeasibleError("The model is infeasible" + where)        # src/lib.rs:25
+    if rc != _ffi.OPTIMAL:
+        # PANIC / ITER_LIMIT / SINGULAR: the reference would panic (PanicException) or recurse
+        return RuntimeError(f"simplex terminated with status {_ffi.status_str(rc)!r} after "
+                            f"{res.iterations} iterations{where}")
+    if res.near_ties > 0 and res.numerics_used != _ffi.STRICT:
+        warnings.warn(
+            f"{res.near_ties} of {res.iterations} pivots (the first: pivot {res.first_near_tie}) were "
+            "decided within rounding distance of a tie and the model is too large to be re-solved "
+            "in the reference's own arithmetic: the optimum is valid, but the vertex may differ "
+            f"from the one the reference implementation reports when the optimum is not unique{where}",
+            NearTieWarning, stacklevel=stacklevel)
+    return PySolution(float(res.objective), {v.id: float(values[i]) for i, v in enumerate(order)},
+                      int(res.iterations), "strict" if res.numerics_used == _ffi.STRICT else "fast",
+                      (int(res.m), int(res.n)))
+
+
 def solve(objective: PyAffExpr, constraints) -> PySolution:
     """Maximise `objective` subject to `constraints` on the GPU (src/lib.rs:16-27)."""
     if not isinstance(objective, PyAffExpr):
@@ -211,21 +234,37 @@ def solve(objective: PyAffExpr, constraints) -> PySolution:
     md = _c_model(arrays)
     rc = _ffi.lib().dzg_model_solve(C.byref(md), C.byref(opts), C.byref(res))
     _ffi.check(rc, "dzg_model_solve")
-    if rc == _ffi.UNBOUNDED:
-        raise UnboundedError("The objective is unbounded")      # src/lib.rs:24
-    if rc == _ffi.INFEASIBLE:
-        raise InfeasibleError("The model is infeasible")        # src/lib.rs:25
-    if rc != _ffi.OPTIMAL:
-        # PANIC / ITER_LIMIT / SINGULAR: the reference would panic (PanicException) or recurse
-        raise RuntimeError(f"simplex terminated with status {_ffi.status_str(rc)!r} after "
-                           f"{res.iterations} iterations")
-    if res.near_ties > 0 and res.numerics_used != _ffi.STRICT:
-        warnings.warn(
-            f"{res.near_ties} of {res.iterations} pivots (the first: pivot {res.first_near_tie}) were "
-            "decided within rounding distance of a tie and the model is too large to be re-solved "
-            "in the reference's own arithmetic: the optimum is valid, but the vertex may differ "
-            "from the one the reference implementation reports when the optimum is not unique",
-            NearTieWarning, stacklevel=3)
-    return PySolution(float(res.objective), {v.id: float(values[i]) for i, v in enumerate(order)},
-                      int(res.iterations), "strict" if res.numerics_used == _ffi.STRICT else "fast",
-                      (int(res.m), int(res.n)))
+    out = _outcome(res, values, order)
+    if isinstance(out, Exception):
+        raise out
+    return out
+
+
+def solve_many(problems, *, return_exceptions: bool = False) -> list:
+    """solve() for every (objective, constraints) pair of `problems`, in one dzg_model_solve_batch
+    call: the models that solve() would run in STRICT numerics on at most 128 rows share one batch
+    on the GPU (one workgroup per model), the others are solved one at a time.  Results keep the
+    order of `problems` and equal solve()'s one for one.  A model that ends unbounded or infeasible
+    raises solve()'s exception, its index in the message, once the whole batch is done; with
+    return_exceptions=True the exception instance stands in that model's place instead."""
+    lowered = []
+    for i, (objective, constraints) in enumerate(problems):
+        if not isinstance(objective, PyAffExpr):
+            raise TypeError(f"problems[{i}]: objective must be a PyAffExpr")
+        lowered.append(lower(objective, list(constraints)))
+    count = len(lowered)
+    keep = [(_c_model(arrays), np.zeros(max(len(order), 1))) for arrays, order in lowered]
+    models = (_ffi.Model * max(count, 1))(*[md for md, _ in keep])
+    results = (_ffi.ModelResult * max(count, 1))()
+    for i, (_, values) in enumerate(keep):
+        results[i].values = _ffi.ptr(values)
+    opts = _ffi.default_opts(**_options)
+    rc = _ffi.lib().dzg_model_solve_batch(models, C.c_int64(count), C.byref(opts), results)
+    _ffi.check(rc, "dzg_model_solve_batch")
+    out = [_outcome(results[i], keep[i][1], lowered[i][1], f" (model {i})", stacklevel=3)
+           for i in range(count)]
+    if not return_exceptions:
+        for o in out:
+            if isinstance(o, Exception):
+                raise o
+    return out

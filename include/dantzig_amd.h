@@ -360,6 +360,24 @@ typedef struct {
 
 int dzg_model_solve(const dzg_model *model, const dzg_opts *opts, dzg_model_result *res);
 
+/* ---- Batches of small LPs: one workgroup per LP (csrc/k_batch.hip) ------------------ */
+
+/* Largest LP (rows) the batched solver takes: its m x (m+1) factor buffer lives in LDS. */
+#define DZG_BATCH_MAX_ROWS 128
+/* Solves lps[0..count) in STRICT numerics, one workgroup per LP.  Dense `a` only, m <= 128;
+ * var_col, constant, resume state (xbar / zbar) as in dzg_lp.  opts: max_iter (per LP), epsilon;
+ * numerics STRICT or AUTO (= STRICT here); FAST is DZG_E_ARG.  pivots_per_launch 0 = default.
+ * res[i] is filled like dzg_solver_result fills it (its optional buffers may be NULL, log / log_cap
+ * per LP); res[i].status is LP i's outcome.  Returns 0 when every LP was processed, a negative
+ * code (nothing run, dzg_last_error names the offending index) otherwise. */
+int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                    int64_t pivots_per_launch, dzg_result *res);
+/* The same as calling dzg_model_solve(&models[i], opts, &res[i]) for every i -- result for result,
+ * bit for bit -- with every model that call would solve in STRICT on <= 128 dense rows solved in
+ * one batch; the others go through dzg_model_solve one at a time. */
+int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                          dzg_model_result *res);
+
 /* Host-only: the standard-form builder alone (Simplex::new, src/simplex.rs:123-224).
  * Two-call protocol: first call with out->a == NULL fills m, n, n_struct and lda;
  * the caller allocates a[lda*n_struct], var_col[n], c[n], basis[m], nonbasis[n-m],

@@ -1,0 +1,145 @@
+"""Host side of the batched STRICT solver (dzg_batch_solve / dzg_model_solve_batch): the ABI, the
+argument checks that run before any device call, and the Python surface.  No GPU needed."""
+import ctypes as C
+import os
+
+import numpy as np
+import pytest
+
+import dantzig
+import dantzig_amd
+from dantzig_amd import _ffi, core
+from dantzig_amd import rust as rs
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_header_declares_the_batch_entry_points():
+    with open(os.path.join(ROOT, "include", "dantzig_amd.h")) as f:
+        h = f.read()
+    assert "#define DZG_BATCH_MAX_ROWS 128" in h
+    assert "int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts," in h
+    assert "int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts," in h
+    assert "#define DZG_ABI_VERSION 4" in h
+
+
+def test_library_exports_the_batch_entry_points():
+    lib = _ffi.lib()
+    for name in ("dzg_batch_solve", "dzg_model_solve_batch"):
+        assert name in _ffi.EXPORTS
+        assert hasattr(lib, name)
+
+
+def _lp(m=3, ns=4, seed=0):
+    rng = np.random.default_rng(seed)
+    return core.CoreLP.from_inequality_form(rng.uniform(-1, 1, (m, ns)), rng.uniform(0, 1, m),
+                                            rng.uniform(-1, 1, ns))
+
+
+def _call(lps, res=True, **opts):
+    """dzg_batch_solve on CoreLPs through ctypes; returns (rc, last error)."""
+    marshalled = [core._c_lp(lp) for lp in lps]
+    arr = (_ffi.Lp * max(len(lps), 1))(*[c for c, _ in marshalled])
+    out = (_ffi.Result * max(len(lps), 1))() if res else None
+    o = _ffi.default_opts(**opts)
+    rc = _ffi.lib().dzg_batch_solve(arr, C.c_int64(len(lps)), C.byref(o), C.c_int64(0), out)
+    return rc, _ffi.lib().dzg_last_error().decode()
+
+
+def _csc_lp(m=3, ns=4):
+    cp = np.arange(ns + 1, dtype=np.int64)
+    ri = np.arange(ns, dtype=np.int32) % m
+    return core.CoreLP.from_csc(m, cp, ri, np.ones(ns), np.ones(m), np.ones(ns))
+
+
+@pytest.mark.parametrize("case", ["m129", "csc", "fast", "res_null", "bad_var_col"])
+def test_batch_solve_rejects_malformed_input_on_any_machine(case):
+    good = [_lp(seed=1), _lp(seed=2)]
+    opts = {}
+    res = True
+    if case == "m129":
+        lps, bad = good + [_lp(m=129, ns=3)], 2
+    elif case == "csc":
+        lps, bad = [good[0], _csc_lp()], 1
+    elif case == "fast":
+        lps, bad, opts = good, None, dict(numerics=_ffi.FAST)
+    elif case == "res_null":
+        lps, bad, res = good, None, False
+    else:
+        lp = _lp(seed=3)
+        lp.var_col = np.array([0, 1, 2, 99, -1, -2, -3], dtype=np.int64)  # column 99 does not exist
+        lps, bad = [good[0], good[1], lp], 2
+    rc, msg = _call(lps, res=res, **opts)
+    assert rc == _ffi.E_ARG, (rc, msg)
+    if bad is not None:
+        assert f"lps[{bad}]" in msg
+
+
+def test_batch_solve_without_a_gpu_is_a_device_error():
+    if _ffi.lib().dzg_device_count() > 0:
+        pytest.skip("a GPU is visible: the device path is covered by tests/test_gpu_batch.py")
+    rc, msg = _call([_lp(seed=1), _lp(m=0, ns=2, seed=2)])
+    assert rc == _ffi.E_DEVICE and "no CPU path" in msg
+
+
+def _model_batch(models, res=True):
+    keep = [rs._c_model(a) for a in models]
+    arr = (_ffi.Model * max(len(keep), 1))(*keep)
+    out = (_ffi.ModelResult * max(len(keep), 1))() if res else None
+    return _ffi.lib().dzg_model_solve_batch(arr, C.c_int64(len(keep)), None, out)
+
+
+def _arrays(seed):
+    x, y = rs.Variable(lb=0.0, ub=None), rs.Variable(lb=None, ub=2.0)
+    obj = rs.PyAffExpr(linexpr=rs.PyLinExpr([1.0, float(seed)], [x, y]), constant=0.0)
+    con = rs.PyInequality(linexpr=rs.PyLinExpr([1.0, 1.0], [x, y]), b=3.0)
+    return rs.lower(obj, [con])[0]
+
+
+def test_model_batch_checks_its_arguments():
+    assert _model_batch([_arrays(1), _arrays(2)], res=False) == _ffi.E_ARG
+    bad = _arrays(3)
+    bad["obj_var"] = np.array([0, 7, 0], dtype=np.int64)  # variable 7 of a two-variable model
+    assert _model_batch([_arrays(1), bad]) == _ffi.E_ARG
+    assert "models[1]" in _ffi.lib().dzg_last_error().decode()
+    assert _model_batch([]) == 0
+
+
+def test_model_batch_without_a_gpu_is_a_device_error():
+    if _ffi.lib().dzg_device_count() > 0:
+        pytest.skip("a GPU is visible: the device path is covered by tests/test_gpu_batch.py")
+    assert _model_batch([_arrays(1), _arrays(2)]) == _ffi.E_DEVICE
+    assert "no CPU path" in _ffi.lib().dzg_last_error().decode()
+
+
+def test_solve_batch_checks_the_whole_batch_before_the_device(monkeypatch):
+    def no_device(*a, **k):
+        raise AssertionError("the device was reached")
+
+    lib = _ffi.lib()
+    monkeypatch.setattr(_ffi, "lib", lambda: type("L", (), {"dzg_batch_solve": no_device,
+                                                            "dzg_opts_default": lib.dzg_opts_default,
+                                                            "dzg_device_count": no_device})())
+    good = _lp()
+    with pytest.raises(ValueError, match="129 rows"):
+        core.solve_batch([good, _lp(m=129, ns=2)])
+    with pytest.raises(ValueError, match="CSC"):
+        core.solve_batch([good, _csc_lp()])
+    with pytest.raises(ValueError, match="STRICT"):
+        core.solve_batch([good], numerics=core.FAST)
+    a, b, c = np.ones((3, 4)), np.ones(3), np.ones(4)
+    with pytest.raises(ValueError, match="column-block"):
+        core.solve_batch([good, core.CoreLP.from_inequality_block(a[:, :2], b, c, 0, 2)])
+    broken = _lp()
+    broken.x = np.ones(5)
+    with pytest.raises(ValueError, match="do not match"):
+        core.solve_batch([good, broken])
+
+
+def test_solve_many_is_reachable_without_changing_all():
+    assert dantzig.__all__ == ["Variable", "Var", "Minimize", "Min", "Maximize", "Max", "exceptions"]
+    assert dantzig_amd.__all__ == dantzig.__all__
+    assert dantzig.solve_many is dantzig_amd.solve_many
+    assert callable(rs.solve_many)
+    with pytest.raises(TypeError, match="Minimize"):
+        dantzig_amd.solve_many([object()])
