@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdantzig_amd.so")
 
 # dzg_status
-OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT, SINGULAR, PANIC, RUNNING, NEAR_TIE = range(8)
+OPTIMAL, UNBOUNDED, INFEASIBLE, ITER_LIMIT, SINGULAR, PANIC, RUNNING, NEAR_TIE, NODE_LIMIT = range(9)
 E_DEVICE, E_ARG, E_NOMEM = -1, -2, -3
 STRICT, FAST, AUTO = 0, 1, 2
 PRICE_AUTO, PRICE_SEQ, PRICE_WAVE, PRICE_TREE = 0, 1, 2, 3
@@ -38,7 +38,8 @@ EXPORTS = [
     "dzg_gen_dense_lp_block", "dzg_solver_set_profile", "dzg_kernel_neg_t_dot_csc",
     "dzg_shard_comm_size", "dzg_solver_upload_columns", "dzg_debug_hold_cus", "dzg_debug_hold_wait",
     "dzg_core_solve_full_csc", "dzg_debug_live_lists", "dzg_debug_rl_listed",
-    "dzg_debug_basis_inverse", "dzg_batch_solve", "dzg_model_solve_batch",
+    "dzg_debug_basis_inverse", "dzg_batch_solve", "dzg_model_solve_batch", "dzg_mip_opts_default",
+    "dzg_mip_solve",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -115,6 +116,27 @@ class StdForm(C.Structure):
     ]
 
 
+class MipOpts(C.Structure):
+    _fields_ = [("node_limit", C.c_int64), ("nodes_per_round", C.c_int32), ("reserved0", C.c_int32),
+                ("pivots_per_launch", C.c_int64), ("int_tol", C.c_double), ("abs_gap", C.c_double),
+                ("rel_gap", C.c_double)]
+
+
+class MipNode(C.Structure):
+    _fields_ = [("id", C.c_int64), ("parent", C.c_int64), ("branch_var", C.c_int64),
+                ("direction", C.c_int32), ("status", C.c_int32), ("bound", C.c_double),
+                ("iterations", C.c_int64), ("objective", C.c_double)]
+
+
+class MipResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("has_incumbent", C.c_int32), ("objective", C.c_double),
+                ("values", C.c_void_p), ("best_bound", C.c_double), ("nodes_solved", C.c_int64),
+                ("nodes_batched", C.c_int64), ("nodes_sequential", C.c_int64), ("nodes_fast", C.c_int64),
+                ("nodes_pruned", C.c_int64), ("nodes_dropped", C.c_int64), ("rounds", C.c_int64),
+                ("lp_iterations", C.c_int64), ("incumbent_node", C.c_int64), ("failed_node", C.c_int64),
+                ("log", C.c_void_p), ("log_cap", C.c_int64), ("log_count", C.c_int64)]
+
+
 class Candidate(C.Structure):
     _fields_ = [("ratio", C.c_double), ("pos", C.c_int64), ("y", C.c_double),
                 ("ybar", C.c_double), ("dy", C.c_double)]
@@ -175,6 +197,9 @@ def lib() -> C.CDLL:
         _lib.dzg_debug_basis_inverse.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.dzg_batch_solve.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.dzg_model_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_mip_opts_default.restype = None
+        _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
+        _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_solver_upload_columns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                    C.c_int64]
     return _lib
@@ -210,6 +235,16 @@ def default_opts(**kw) -> Opts:
     for k, v in kw.items():
         if not hasattr(o, k):
             raise TypeError(f"unknown option {k!r}")
+        setattr(o, k, v)
+    return o
+
+
+def default_mip_opts(**kw) -> MipOpts:
+    o = MipOpts()
+    lib().dzg_mip_opts_default(C.byref(o))
+    for k, v in kw.items():
+        if k == "reserved0" or not hasattr(o, k):
+            raise TypeError(f"unknown MIP option {k!r}")
         setattr(o, k, v)
     return o
 

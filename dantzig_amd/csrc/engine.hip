@@ -50,6 +50,7 @@ extern "C" const char *dzg_status_str(int s)
     case DZG_PANIC: return "panic";
     case DZG_RUNNING: return "running";
     case DZG_NEAR_TIE: return "near_tie";
+    case DZG_NODE_LIMIT: return "node_limit";
     case DZG_E_DEVICE: return "device_error";
     case DZG_E_ARG: return "bad_argument";
     case DZG_E_NOMEM: return "out_of_memory";

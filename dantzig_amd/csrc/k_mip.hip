@@ -1,0 +1,442 @@
+// k_mip.hip -- the node LPs of a branch-and-bound round, one workgroup per node, STRICT numerics.
+//
+// The simplex loop is k_batch.hip's (batch_strict.h): the same row buckets, LDS carve-up and
+// pivots_per_launch slicing, so a node LP ends exactly where dzg_batch_solve (and hence
+// dzg_model_solve) would end it.  What is new here:
+//
+//   * shared structures.  A node's standard form differs from its structure's only in the
+//     right-hand side of the bound rows of integer variables (model.cpp: a finite bound is a row
+//     x+ - x- <= ub / -x+ + x- <= -lb, so tightening it moves b only).  A, var_col, c, the initial
+//     nonbasis, z0 = -c and the row table live once per structure in one device arena; every node of
+//     the structure reads that copy.
+//   * device-side initialisation.  Per node the host uploads a structure id and two doubles per
+//     integer variable.  On its first slice (iter < 0) the workgroup builds x = rhs from the row
+//     table, x̄ = z̄ = 1, the slack basis and the structure's nonbasis and z0.
+//   * device epilogue on OPTIMAL.  The objective is one sequential sum in basis-position order
+//     (k_batch.hip's host loop, unfused); the user values are x+ - x- found through a copy of the
+//     basis in LDS; the integrality test and the branching choice are mip_branch_choice
+//     (mip_internal.h), the host's own code.  The node's compact record is written; values stay on
+//     the device unless the node is integral.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "batch_strict.h"
+#include "common.h"
+#include "mip_internal.h"
+
+int dzg_set_error(int code, const std::string &msg); // engine.hip
+
+using dzg_internal::MipNodeRecord;
+using dzg_internal::MipStructure;
+
+namespace {
+
+using dzg_bs::bucket_of;
+using dzg_bs::kBuckets;
+using dzg_bs::kMaxGrid;
+using dzg_bs::lds_bytes;
+
+// One structure: offsets into the double / int pools (elements).
+struct SDesc {
+    long long a_off, b0_off, c_off, z0_off;          // dpool
+    long long vc_off, ri_off, bs_off, nb_off, pv_off; // ipool (pv: pos_var then neg_var)
+    int m, n;
+    double constant;
+};
+
+// One node of the round: its structure and its state offsets (elements).
+struct NDesc {
+    long long m_off, q_off;
+    int sid, pad;
+};
+
+struct MArgs {
+    const SDesc *sd;
+    const double *dpool;
+    const int *ipool;
+    const int *int_vars;
+    int nint, nvars;
+    const NDesc *nd;
+    const double *bnd; // 2 * nint per node
+    int *basis, *nonbasis;
+    double *x, *xbar, *z, *zbar, *dz;
+    long long *iter; // < 0: not initialised yet
+    int *status;
+    MipNodeRecord *rec;
+    double *values; // nvars per node
+    long long max_iter;
+    double eps, int_tol;
+    int ppl, mmax;
+};
+
+template <int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restrict__ list,
+                                                    int *__restrict__ next_list,
+                                                    int *__restrict__ next_count)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_mem[];
+    const int id = list[blockIdx.x];
+    const NDesc N = g.nd[id];
+    const SDesc D = g.sd[N.sid];
+    const int m = D.m, q = D.n - D.m;
+    dzg_bs::LpState S;
+    S.A = g.dpool + D.a_off;
+    S.var_col = g.ipool + D.vc_off;
+    S.m = m;
+    S.q = q;
+    S.basis = g.basis + N.m_off;
+    S.nonbasis = g.nonbasis + N.q_off;
+    S.x = g.x + N.m_off;
+    S.xbar = g.xbar + N.m_off;
+    S.z = g.z + N.q_off;
+    S.zbar = g.zbar + N.q_off;
+    S.dz = g.dz + N.q_off;
+    S.log_kind = S.log_enter = S.log_leave = nullptr;
+    S.log_mu = nullptr;
+    S.log_cap = 0;
+    long long it = g.iter[id];
+    if (it < 0) { // first slice: the node's initial state (model.cpp build(), Simplex::new)
+        const double *b0 = g.dpool + D.b0_off, *bnd = g.bnd + (long long)id * 2 * g.nint;
+        const int *ri = g.ipool + D.ri_off, *bs = g.ipool + D.bs_off, *nb = g.ipool + D.nb_off;
+        const double *z0 = g.dpool + D.z0_off;
+        for (int r = threadIdx.x; r < m; r += BLOCK) {
+            const int code = ri[r];
+            S.x[r] = code < 0 ? b0[r] : ((code & 1) ? bnd[code] : -bnd[code]);
+            S.xbar[r] = 1.0;
+            S.basis[r] = bs[r];
+        }
+        for (int k = threadIdx.x; k < q; k += BLOCK) {
+            S.nonbasis[k] = nb[k];
+            S.z[k] = z0[k];
+            S.zbar[k] = 1.0;
+        }
+        it = 0;
+        __syncthreads();
+    }
+    const int status = dzg_bs::strict_steps<BLOCK>(S, s_mem, g.mmax, it, g.max_iter, g.eps, g.ppl);
+    if (status == DZG_RUNNING) {
+        if (threadIdx.x == 0) {
+            g.iter[id] = it;
+            next_list[atomicAdd(next_count, 1)] = id;
+        }
+        return;
+    }
+    MipNodeRecord rec;
+    rec.status = status;
+    rec.iterations = it;
+    rec.branch = -1;
+    rec.objective = 0.0;
+    rec.value = 0.0;
+    rec.integral = 0;
+    rec.pad = 0;
+    if (status == DZG_OPTIMAL) {
+        const double *c = g.dpool + D.c_off;
+        const int *pv = g.ipool + D.pv_off, *nv = pv + g.nvars;
+        double *vals = g.values + (long long)id * g.nvars;
+        int *sb = (int *)s_mem; // the final basis, m entries (W is free after the loop)
+        __syncthreads();
+        for (int p = threadIdx.x; p < m; p += BLOCK) sb[p] = S.basis[p];
+        __syncthreads();
+        // Simplex::solution (model.cpp solution_values): x+ - x-, 0.0 for a nonbasic part
+        for (int u = threadIdx.x; u < g.nvars; u += BLOCK) {
+            double val = 0.0;
+            const int jp = pv[u], jn = nv[u];
+            if (jp >= 0) {
+                double pos = 0.0, neg = 0.0;
+                for (int p = 0; p < m; ++p) {
+                    if (sb[p] == jp) pos = S.x[p];
+                    if (sb[p] == jn) neg = S.x[p];
+                }
+                val = pos - neg;
+            }
+            vals[u] = val;
+        }
+        __syncthreads(); // vals is read by thread 0 below
+        if (threadIdx.x == 0) {
+            double sum = 0.0; // objective_value, src/simplex.rs:345-352, basis-position order
+            for (int p = 0; p < m; ++p) {
+                const double prod = c[sb[p]] * S.x[p];
+                sum = sum + prod;
+            }
+            rec.objective = D.constant + sum;
+            dzg_internal::mip_branch_choice(vals, g.int_vars, g.nint, g.int_tol, &rec.branch,
+                                            &rec.value, &rec.integral);
+        }
+    }
+    if (threadIdx.x == 0) {
+        g.rec[id] = rec;
+        g.status[id] = status;
+        g.iter[id] = it;
+    }
+}
+
+void launch_bucket(int b, const MArgs &g, const int *list, int n, int *next_list, int *next_count,
+                   hipStream_t st)
+{
+    const size_t lds = lds_bytes(g.mmax);
+    for (int c0 = 0; c0 < n; c0 += kMaxGrid[b]) {
+        const int grid = std::min(kMaxGrid[b], n - c0);
+        if (b <= 1)
+            hipLaunchKernelGGL(k_mip_node<64>, dim3(grid), dim3(64), lds, st, g, list + c0,
+                               next_list, next_count);
+        else if (b == 2)
+            hipLaunchKernelGGL(k_mip_node<128>, dim3(grid), dim3(128), lds, st, g, list + c0,
+                               next_list, next_count);
+        else
+            hipLaunchKernelGGL(k_mip_node<256>, dim3(grid), dim3(256), lds, st, g, list + c0,
+                               next_list, next_count);
+    }
+}
+
+#define MHIP(expr)                                                                              \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return dzg_set_error(DZG_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+
+} // namespace
+
+namespace dzg_internal {
+
+struct MipGpu {
+    int device = 0, nvars = 0, nint = 0;
+    hipStream_t st = nullptr;
+    // structures: host copies, and the device arena [SDesc | int_vars | ipool | dpool]
+    std::vector<MipStructure> structs;
+    bool dirty = true;
+    unsigned char *sdev = nullptr;
+    MArgs base{};
+    // the round arena, grown on demand and reused
+    unsigned char *rdev = nullptr;
+    size_t rcap = 0;
+    std::vector<int> int_vars;
+};
+
+int mip_gpu_create(MipGpu **out, int device, int nvars, const std::vector<int> &int_vars)
+{
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return dzg_set_error(DZG_E_DEVICE, "no HIP device visible: dantzig_amd has no CPU path");
+    if (device < 0 || device >= ndev) return dzg_set_error(DZG_E_ARG, "opts.device out of range");
+    MHIP(hipSetDevice(device));
+    MipGpu *g = new MipGpu;
+    g->device = device;
+    g->nvars = nvars;
+    g->nint = (int)int_vars.size();
+    g->int_vars = int_vars;
+    hipError_t e = hipStreamCreateWithFlags(&g->st, hipStreamNonBlocking);
+    if (e != hipSuccess) {
+        delete g;
+        return dzg_set_error(DZG_E_DEVICE, std::string("hipStreamCreateWithFlags: ") + hipGetErrorString(e));
+    }
+    *out = g;
+    return 0;
+}
+
+void mip_gpu_destroy(MipGpu *g)
+{
+    if (!g) return;
+    if (g->sdev) (void)hipFree(g->sdev);
+    if (g->rdev) (void)hipFree(g->rdev);
+    if (g->st) (void)hipStreamDestroy(g->st);
+    delete g;
+}
+
+int mip_gpu_add_structure(MipGpu *g, MipStructure &&s)
+{
+    g->structs.push_back(std::move(s));
+    g->dirty = true;
+    return (int)g->structs.size() - 1;
+}
+
+static int upload_structures(MipGpu *g)
+{
+    const size_t ns = g->structs.size();
+    std::vector<SDesc> sd(ns);
+    std::vector<double> dpool;
+    std::vector<int> ipool;
+    for (size_t i = 0; i < ns; ++i) {
+        const MipStructure &s = g->structs[i];
+        SDesc &d = sd[i];
+        d.m = s.m;
+        d.n = s.n;
+        d.constant = s.constant;
+        auto put_d = [&](const std::vector<double> &v) {
+            const long long off = (long long)dpool.size();
+            dpool.insert(dpool.end(), v.begin(), v.end());
+            return off;
+        };
+        auto put_i = [&](const std::vector<int> &v) {
+            const long long off = (long long)ipool.size();
+            ipool.insert(ipool.end(), v.begin(), v.end());
+            return off;
+        };
+        d.a_off = put_d(s.a);
+        d.b0_off = put_d(s.b0);
+        d.c_off = put_d(s.c);
+        d.z0_off = put_d(s.z0);
+        d.vc_off = put_i(s.var_col);
+        d.ri_off = put_i(s.row_int);
+        d.bs_off = put_i(s.basis0);
+        d.nb_off = put_i(s.nonbasis0);
+        d.pv_off = put_i(s.pos_var);
+        put_i(s.neg_var); // directly after pos_var
+    }
+    const size_t o_sd = 0, o_iv = align16(o_sd + sizeof(SDesc) * ns),
+                 o_ip = align16(o_iv + sizeof(int) * (g->int_vars.size() + 1)),
+                 o_dp = align16(o_ip + sizeof(int) * (ipool.size() + 1)),
+                 total = align16(o_dp + sizeof(double) * (dpool.size() + 1));
+    std::vector<unsigned char> host(total, 0);
+    std::memcpy(host.data() + o_sd, sd.data(), sizeof(SDesc) * ns);
+    if (!g->int_vars.empty())
+        std::memcpy(host.data() + o_iv, g->int_vars.data(), sizeof(int) * g->int_vars.size());
+    if (!ipool.empty()) std::memcpy(host.data() + o_ip, ipool.data(), sizeof(int) * ipool.size());
+    if (!dpool.empty()) std::memcpy(host.data() + o_dp, dpool.data(), sizeof(double) * dpool.size());
+    if (g->sdev) {
+        MHIP(hipStreamSynchronize(g->st));
+        MHIP(hipFree(g->sdev));
+        g->sdev = nullptr;
+    }
+    MHIP(hipMalloc((void **)&g->sdev, total));
+    MHIP(hipMemcpyAsync(g->sdev, host.data(), total, hipMemcpyHostToDevice, g->st));
+    MHIP(hipStreamSynchronize(g->st));
+    g->base.sd = (const SDesc *)(g->sdev + o_sd);
+    g->base.int_vars = (const int *)(g->sdev + o_iv);
+    g->base.ipool = (const int *)(g->sdev + o_ip);
+    g->base.dpool = (const double *)(g->sdev + o_dp);
+    g->base.nint = g->nint;
+    g->base.nvars = g->nvars;
+    g->dirty = false;
+    return 0;
+}
+
+int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count, long long max_iter,
+                        double eps, int ppl, double int_tol, MipNodeRecord *rec, double *values)
+{
+    if (count <= 0) return 0;
+    MHIP(hipSetDevice(g->device));
+    if (g->dirty) {
+        const int rc = upload_structures(g);
+        if (rc < 0) return rc;
+    }
+    // ---- layout of the round arena
+    std::vector<NDesc> nd((size_t)count);
+    long long nm = 0, nq = 0;
+    int mmax[kBuckets] = {0, 0, 0, 0};
+    std::vector<int> bucket_n(kBuckets, 0);
+    for (int i = 0; i < count; ++i) {
+        const MipStructure &s = g->structs[(size_t)sid[i]];
+        nd[(size_t)i].sid = sid[i];
+        nd[(size_t)i].pad = 0;
+        nd[(size_t)i].m_off = nm;
+        nd[(size_t)i].q_off = nq;
+        nm += s.m;
+        nq += s.n - s.m;
+        const int b = bucket_of(s.m);
+        mmax[b] = std::max(mmax[b], s.m);
+        bucket_n[(size_t)b]++;
+    }
+    const size_t nb2 = (size_t)count * 2 * (size_t)g->nint;
+    size_t top = 0;
+    auto sec = [&](size_t bytes) {
+        const size_t off = top;
+        top = align16(top + bytes);
+        return off;
+    };
+    // uploaded: descriptors, bounds, the first list; then device-only state and results
+    const size_t o_nd = sec(sizeof(NDesc) * count), o_bnd = sec(sizeof(double) * (nb2 + 1)),
+                 o_list = sec(sizeof(int) * count);
+    const size_t upload_end = top;
+    const size_t o_iter = sec(sizeof(long long) * count), o_rec = sec(sizeof(MipNodeRecord) * count),
+                 o_status = sec(sizeof(int) * count), o_list2 = sec(sizeof(int) * count),
+                 o_counts = sec(sizeof(int) * kBuckets), o_basis = sec(sizeof(int) * (nm + 1)),
+                 o_nonbasis = sec(sizeof(int) * (nq + 1)), o_x = sec(sizeof(double) * (nm + 1)),
+                 o_xbar = sec(sizeof(double) * (nm + 1)), o_z = sec(sizeof(double) * (nq + 1)),
+                 o_zbar = sec(sizeof(double) * (nq + 1)), o_dz = sec(sizeof(double) * (nq + 1)),
+                 o_vals = sec(sizeof(double) * ((size_t)count * g->nvars + 1));
+    if (top > g->rcap) { // one allocation, grown by half again so that few rounds reallocate
+        if (g->rdev) {
+            MHIP(hipStreamSynchronize(g->st));
+            MHIP(hipFree(g->rdev));
+            g->rdev = nullptr;
+            g->rcap = 0;
+        }
+        const size_t cap = top + top / 2;
+        MHIP(hipMalloc((void **)&g->rdev, cap));
+        g->rcap = cap;
+    }
+    std::vector<unsigned char> host(upload_end, 0);
+    std::memcpy(host.data() + o_nd, nd.data(), sizeof(NDesc) * count);
+    if (nb2) std::memcpy(host.data() + o_bnd, bnd, sizeof(double) * nb2);
+    std::vector<int> seg(kBuckets, 0);
+    for (int b = 1; b < kBuckets; ++b) seg[(size_t)b] = seg[(size_t)b - 1] + bucket_n[(size_t)b - 1];
+    {
+        int *list = (int *)(host.data() + o_list);
+        std::vector<int> fill(seg);
+        for (int i = 0; i < count; ++i) list[fill[(size_t)bucket_of(g->structs[(size_t)sid[i]].m)]++] = i;
+    }
+    unsigned char *dev = g->rdev;
+    hipStream_t st = g->st;
+    MHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
+    MHIP(hipMemsetAsync(dev + o_iter, 0xff, sizeof(long long) * count, st)); // -1: not initialised
+
+    MArgs a = g->base;
+    a.nd = (const NDesc *)(dev + o_nd);
+    a.bnd = (const double *)(dev + o_bnd);
+    a.basis = (int *)(dev + o_basis);
+    a.nonbasis = (int *)(dev + o_nonbasis);
+    a.x = (double *)(dev + o_x);
+    a.xbar = (double *)(dev + o_xbar);
+    a.z = (double *)(dev + o_z);
+    a.zbar = (double *)(dev + o_zbar);
+    a.dz = (double *)(dev + o_dz);
+    a.iter = (long long *)(dev + o_iter);
+    a.status = (int *)(dev + o_status);
+    a.rec = (MipNodeRecord *)(dev + o_rec);
+    a.values = (double *)(dev + o_vals);
+    a.max_iter = max_iter;
+    a.eps = eps;
+    a.int_tol = int_tol;
+    a.ppl = ppl;
+
+    int *cur = (int *)(dev + o_list), *nxt = (int *)(dev + o_list2);
+    int *counts = (int *)(dev + o_counts);
+    std::vector<int> live(bucket_n);
+    for (;;) {
+        bool any = false;
+        MHIP(hipMemsetAsync(counts, 0, sizeof(int) * kBuckets, st));
+        for (int b = 0; b < kBuckets; ++b) {
+            if (live[(size_t)b] == 0) continue;
+            any = true;
+            MArgs ab = a;
+            ab.mmax = mmax[b];
+            launch_bucket(b, ab, cur + seg[(size_t)b], live[(size_t)b], nxt + seg[(size_t)b],
+                          counts + b, st);
+            MHIP(hipGetLastError());
+        }
+        if (!any) break;
+        int h_counts[kBuckets];
+        MHIP(hipMemcpyAsync(h_counts, counts, sizeof(h_counts), hipMemcpyDeviceToHost, st));
+        MHIP(hipStreamSynchronize(st));
+        for (int b = 0; b < kBuckets; ++b) live[(size_t)b] = h_counts[b];
+        std::swap(cur, nxt);
+    }
+    MHIP(hipMemcpyAsync(rec, dev + o_rec, sizeof(MipNodeRecord) * count, hipMemcpyDeviceToHost, st));
+    MHIP(hipStreamSynchronize(st));
+    if (g->nvars > 0)
+        for (int i = 0; i < count; ++i)
+            if (rec[i].status == DZG_OPTIMAL && rec[i].integral)
+                MHIP(hipMemcpyAsync(values + (size_t)i * g->nvars,
+                                    dev + o_vals + sizeof(double) * (size_t)i * g->nvars,
+                                    sizeof(double) * g->nvars, hipMemcpyDeviceToHost, st));
+    MHIP(hipStreamSynchronize(st));
+    return 0;
+}
+
+} // namespace dzg_internal

@@ -1,0 +1,383 @@
+// mip.cpp -- dzg_mip_solve: branch and bound over node LPs (include/dantzig_amd.h).
+//
+// A node LP is the user's model with each integer variable's lb / ub replaced by the node's; its
+// result is what dzg_model_solve returns for that model.  Nodes whose integer variables have the same
+// set of finite bounds share one standard form (a "structure", keyed by that mask): bound values only
+// move right-hand sides (model.cpp).  Structures are built once, with model.cpp's builder, the first
+// time a mask is seen.  Nodes that dzg_model_solve would run in STRICT on <= 128 dense rows are solved
+// in rounds on the GPU (k_mip.hip); the rest go through dzg_model_solve one at a time.
+//
+// Search: each round takes up to nodes_per_round open nodes, best parent bound first (ties: lower
+// id), pruning on selection those whose bound is <= incumbent + tol.  The round's results are then
+// processed in ascending node id: infeasible -> dropped; objective <= incumbent + tol -> pruned;
+// integral -> new incumbent; otherwise branched on the most fractional integer variable (down child
+// first).  A child whose bounds cross is never created.  Node ids follow creation order.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <map>
+#include <set>
+#include <string>
+#include <vector>
+
+#include "../../include/dantzig_amd.h"
+#include "mip_internal.h"
+
+int dzg_set_error(int code, const std::string &msg); // engine.hip
+
+using namespace dzg_internal;
+
+namespace {
+
+struct Node {
+    int64_t id, parent, branch_var;
+    int32_t direction;
+    double bound;              // the new bound of branch_var
+    double parent_obj;         // +inf at the root
+    std::vector<double> bnd;   // lb_k, ub_k per integer variable (+-inf: no bound)
+};
+
+struct OpenKey {
+    double bound;
+    int64_t id;
+    bool operator<(const OpenKey &o) const
+    {
+        if (bound != o.bound) return bound > o.bound; // best (largest) bound first
+        return id < o.id;
+    }
+};
+
+struct StructInfo {
+    int gpu_id = -1; // -1: solved through dzg_model_solve
+    int64_t m = 0;
+};
+
+// Node model: md with the integer variables' bounds replaced.
+struct NodeModel {
+    std::vector<int32_t> has_lb, has_ub;
+    std::vector<double> lb, ub;
+    dzg_model md;
+    NodeModel(const dzg_model *base, const std::vector<int> &ints, const std::vector<double> &bnd)
+        : has_lb(base->has_lb, base->has_lb + base->nvars), has_ub(base->has_ub, base->has_ub + base->nvars),
+          lb(base->lb, base->lb + base->nvars), ub(base->ub, base->ub + base->nvars)
+    {
+        for (size_t k = 0; k < ints.size(); ++k) {
+            const int u = ints[k];
+            const double l = bnd[2 * k], h = bnd[2 * k + 1];
+            has_lb[(size_t)u] = std::isinf(l) ? 0 : 1;
+            lb[(size_t)u] = std::isinf(l) ? 0.0 : l;
+            has_ub[(size_t)u] = std::isinf(h) ? 0 : 1;
+            ub[(size_t)u] = std::isinf(h) ? 0.0 : h;
+        }
+        md = *base;
+        if (base->nvars > 0) {
+            md.has_lb = has_lb.data();
+            md.has_ub = has_ub.data();
+            md.lb = lb.data();
+            md.ub = ub.data();
+        }
+    }
+};
+
+bool bad_tol(double t) { return !(t >= 0.0); } // NaN or negative
+
+} // namespace
+
+extern "C" void dzg_mip_opts_default(dzg_mip_opts *mo)
+{
+    if (!mo) return;
+    std::memset(mo, 0, sizeof(*mo));
+    mo->int_tol = 1e-6;
+    mo->abs_gap = 1e-9;
+    mo->rel_gap = 0.0;
+}
+
+extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
+                             const dzg_mip_opts *mip_opts, dzg_mip_result *res)
+{
+    // ---- argument checks, before any device work
+    if (!model || !res) return dzg_set_error(DZG_E_ARG, "mip: model or res is NULL");
+    if (model->nvars > 0 && !is_integer) return dzg_set_error(DZG_E_ARG, "mip: is_integer is NULL");
+    if (!valid(model)) return dzg_set_error(DZG_E_ARG, "mip: the model is malformed");
+    if (model->nvars >= (1ll << 31)) return dzg_set_error(DZG_E_ARG, "mip: too many variables");
+    dzg_opts o;
+    if (opts) o = *opts; else dzg_opts_default(&o);
+    if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_AUTO)
+        return dzg_set_error(DZG_E_ARG, "mip: FAST numerics is not supported for node LPs");
+    dzg_mip_opts mo;
+    if (mip_opts) mo = *mip_opts; else dzg_mip_opts_default(&mo);
+    if (mo.node_limit < 0) return dzg_set_error(DZG_E_ARG, "mip: node_limit < 0");
+    if (mo.nodes_per_round < 0) return dzg_set_error(DZG_E_ARG, "mip: nodes_per_round < 0");
+    if (mo.pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "mip: pivots_per_launch < 0");
+    if (bad_tol(mo.int_tol) || bad_tol(mo.abs_gap) || bad_tol(mo.rel_gap))
+        return dzg_set_error(DZG_E_ARG, "mip: int_tol, abs_gap and rel_gap must be >= 0 (not NaN)");
+    if (res->log_cap < 0 || (res->log_cap > 0 && !res->log))
+        return dzg_set_error(DZG_E_ARG, "mip: log_cap > 0 needs a log buffer");
+
+    const int64_t node_limit = mo.node_limit > 0 ? mo.node_limit : 100000;
+    const int npr = mo.nodes_per_round > 0 ? mo.nodes_per_round : 1024;
+    const int ppl = (int)(mo.pivots_per_launch > 0 ? std::min<int64_t>(mo.pivots_per_launch, 1 << 30) : 16);
+    const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
+    const double eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
+    const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
+    const int nvars = (int)model->nvars;
+
+    std::vector<int> ints;
+    for (int u = 0; u < nvars; ++u) {
+        if (!is_integer[u]) continue;
+        if ((model->has_lb[u] && !std::isfinite(model->lb[u])) || (model->has_ub[u] && !std::isfinite(model->ub[u])))
+            return dzg_set_error(DZG_E_ARG, "mip: integer variable " + std::to_string(u) +
+                                                " has a flagged bound that is not finite");
+        ints.push_back(u);
+    }
+    const int nint = (int)ints.size();
+
+    res->status = DZG_INFEASIBLE;
+    res->has_incumbent = 0;
+    res->objective = 0.0;
+    res->best_bound = -__builtin_inf();
+    res->nodes_solved = res->nodes_batched = res->nodes_sequential = res->nodes_fast = 0;
+    res->nodes_pruned = res->nodes_dropped = res->rounds = res->lp_iterations = 0;
+    res->incumbent_node = res->failed_node = -1;
+    res->log_count = 0;
+
+    MipGpu *gpu = nullptr;
+    struct Guard {
+        MipGpu **g;
+        ~Guard() { mip_gpu_destroy(*g); }
+    } guard{&gpu};
+    {
+        const int rc = mip_gpu_create(&gpu, o.device, nvars, ints);
+        if (rc < 0) return rc;
+    }
+
+    std::map<std::vector<char>, StructInfo> structs; // mask (has_lb, has_ub per integer) -> structure
+    auto structure_of = [&](const std::vector<double> &bnd, const dzg_model *node_md) -> StructInfo {
+        std::vector<char> mask((size_t)2 * nint);
+        for (size_t j = 0; j < mask.size(); ++j) mask[j] = std::isinf(bnd[j]) ? 0 : 1;
+        auto it = structs.find(mask);
+        if (it != structs.end()) return it->second;
+        Built b;
+        build(node_md, b, true);
+        StructInfo info;
+        info.m = b.m;
+        const bool strict = o.numerics == DZG_NUMERICS_STRICT ||
+                            (o.numerics == DZG_NUMERICS_AUTO && b.m <= strict_rows);
+        if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS) {
+            std::vector<int> k_of((size_t)(nvars ? nvars : 1), -1);
+            for (int k = 0; k < nint; ++k) k_of[(size_t)ints[(size_t)k]] = k;
+            MipStructure s;
+            s.m = (int)b.m;
+            s.n = (int)b.n;
+            s.ns = (int)b.ns;
+            s.constant = b.constant;
+            s.a = b.a;
+            s.b0 = b.x;
+            s.c = b.c;
+            s.z0 = b.z;
+            s.var_col.assign(b.var_col.begin(), b.var_col.end());
+            s.basis0.assign(b.basis.begin(), b.basis.end());
+            s.nonbasis0.assign(b.nonbasis.begin(), b.nonbasis.end());
+            s.pos_var.assign(b.pos_var.begin(), b.pos_var.end());
+            s.neg_var.assign(b.neg_var.begin(), b.neg_var.end());
+            s.row_int.assign((size_t)b.m, -1);
+            for (int64_t r = 0; r < b.m; ++r) {
+                const int64_t tag = b.row_tag[(size_t)r];
+                if (tag < 0) continue;
+                const int k = k_of[(size_t)(tag / 2)];
+                if (k < 0) continue;                       // a continuous variable's bound row
+                s.row_int[(size_t)r] = (tag & 1) ? 2 * k : 2 * k + 1; // lb row -> lb_k, ub row -> ub_k
+            }
+            info.gpu_id = mip_gpu_add_structure(gpu, std::move(s));
+        }
+        structs.emplace(mask, info);
+        return info;
+    };
+
+    // ---- the root
+    std::vector<Node> nodes;
+    {
+        Node root;
+        root.id = 0;
+        root.parent = -1;
+        root.branch_var = -1;
+        root.direction = 0;
+        root.bound = 0.0;
+        root.parent_obj = __builtin_inf();
+        root.bnd.resize((size_t)2 * nint);
+        for (int k = 0; k < nint; ++k) {
+            const int u = ints[(size_t)k];
+            root.bnd[(size_t)2 * k] = model->has_lb[u] ? model->lb[u] : -__builtin_inf();
+            root.bnd[(size_t)2 * k + 1] = model->has_ub[u] ? model->ub[u] : __builtin_inf();
+        }
+        nodes.push_back(std::move(root));
+    }
+    std::set<OpenKey> open;
+    open.insert({__builtin_inf(), 0});
+
+    bool has_inc = false;
+    double inc = 0.0;
+    std::vector<double> inc_values((size_t)(nvars ? nvars : 1), 0.0);
+    auto tol = [&]() { return std::max(mo.abs_gap, mo.rel_gap * std::fabs(inc)); };
+    int final_status = -1;
+
+    std::vector<int64_t> round;
+    std::vector<int> sid;
+    std::vector<double> bnd;
+    std::vector<MipNodeRecord> rec;
+    std::vector<double> vals;
+    while (!open.empty()) {
+        // ---- select
+        round.clear();
+        while (!open.empty() && (int)round.size() < npr) {
+            const OpenKey key = *open.begin();
+            if (has_inc && key.bound <= inc + tol()) {
+                open.erase(open.begin());
+                res->nodes_pruned++;
+                continue;
+            }
+            if (res->nodes_solved + (int64_t)round.size() >= node_limit) break;
+            open.erase(open.begin());
+            round.push_back(key.id);
+        }
+        if (round.empty()) {
+            if (!open.empty()) final_status = DZG_NODE_LIMIT;
+            break;
+        }
+        std::sort(round.begin(), round.end());
+        res->rounds++;
+        const int cnt = (int)round.size();
+        rec.assign((size_t)cnt, MipNodeRecord{});
+        vals.assign((size_t)cnt * (size_t)nvars + 1, 0.0);
+        // ---- GPU nodes in one call, the others through dzg_model_solve
+        std::vector<int> gpu_idx;
+        sid.clear();
+        bnd.clear();
+        for (int i = 0; i < cnt; ++i) {
+            const Node &nd = nodes[(size_t)round[(size_t)i]];
+            NodeModel nm(model, ints, nd.bnd);
+            const StructInfo info = structure_of(nd.bnd, &nm.md);
+            if (info.gpu_id >= 0) {
+                gpu_idx.push_back(i);
+                sid.push_back(info.gpu_id);
+                bnd.insert(bnd.end(), nd.bnd.begin(), nd.bnd.end());
+                continue;
+            }
+            dzg_model_result mr;
+            std::memset(&mr, 0, sizeof(mr));
+            mr.values = vals.data() + (size_t)i * nvars;
+            const int rc = dzg_model_solve(&nm.md, &o, &mr);
+            if (rc < 0) return rc;
+            MipNodeRecord &r = rec[(size_t)i];
+            r.status = mr.status;
+            r.iterations = mr.iterations;
+            r.objective = mr.objective;
+            r.branch = -1;
+            r.value = 0.0;
+            r.integral = 0;
+            if (mr.status == DZG_OPTIMAL)
+                mip_branch_choice(mr.values, ints.data(), nint, mo.int_tol, &r.branch, &r.value, &r.integral);
+            res->nodes_sequential++;
+            if (mr.numerics_used == DZG_NUMERICS_FAST) res->nodes_fast++;
+        }
+        if (!gpu_idx.empty()) {
+            const int g = (int)gpu_idx.size();
+            std::vector<MipNodeRecord> grec((size_t)g);
+            std::vector<double> gvals((size_t)g * nvars + 1, 0.0);
+            const int rc = mip_gpu_solve_round(gpu, sid.data(), bnd.data(), g, max_iter, eps, ppl,
+                                               mo.int_tol, grec.data(), gvals.data());
+            if (rc < 0) return rc;
+            for (int j = 0; j < g; ++j) {
+                const int i = gpu_idx[(size_t)j];
+                rec[(size_t)i] = grec[(size_t)j];
+                std::copy(gvals.begin() + (size_t)j * nvars, gvals.begin() + (size_t)(j + 1) * nvars,
+                          vals.begin() + (size_t)i * nvars);
+            }
+            res->nodes_batched += g;
+        }
+        res->nodes_solved += cnt;
+        // ---- process in ascending node id
+        for (int i = 0; i < cnt && final_status < 0; ++i) {
+            const int64_t id = round[(size_t)i];
+            const MipNodeRecord &r = rec[(size_t)i];
+            res->lp_iterations += r.iterations;
+            if (res->log_count < res->log_cap) {
+                const Node &nd = nodes[(size_t)id];
+                dzg_mip_node &e = res->log[res->log_count++];
+                e.id = id;
+                e.parent = nd.parent;
+                e.branch_var = nd.branch_var;
+                e.direction = nd.direction;
+                e.status = r.status;
+                e.bound = nd.bound;
+                e.iterations = r.iterations;
+                e.objective = r.objective;
+            }
+            if (r.status == DZG_INFEASIBLE) {
+                res->nodes_dropped++;
+                continue;
+            }
+            if (r.status != DZG_OPTIMAL) { // the root's UNBOUNDED included: the search stops
+                final_status = r.status;
+                res->failed_node = id;
+                break;
+            }
+            if (has_inc && r.objective <= inc + tol()) {
+                res->nodes_pruned++;
+                continue;
+            }
+            if (r.integral || r.branch < 0) {
+                if (!r.integral) { // no branching candidate (NaN values): nothing to branch on
+                    res->nodes_dropped++;
+                    continue;
+                }
+                has_inc = true;
+                inc = r.objective;
+                res->incumbent_node = id;
+                std::copy(vals.begin() + (size_t)i * nvars, vals.begin() + (size_t)(i + 1) * nvars,
+                          inc_values.begin());
+                continue;
+            }
+            const int k = r.branch;
+            const double fl = std::floor(r.value);
+            for (int dir = -1; dir <= 1; dir += 2) {
+                std::vector<double> cb = nodes[(size_t)id].bnd;
+                double nb;
+                if (dir < 0) {
+                    nb = std::min(cb[(size_t)2 * k + 1], fl);
+                    cb[(size_t)2 * k + 1] = nb;
+                } else {
+                    nb = std::max(cb[(size_t)2 * k], fl + 1.0);
+                    cb[(size_t)2 * k] = nb;
+                }
+                if (cb[(size_t)2 * k] > cb[(size_t)2 * k + 1]) {
+                    res->nodes_dropped++;
+                    continue;
+                }
+                Node child;
+                child.id = (int64_t)nodes.size();
+                child.parent = id;
+                child.branch_var = ints[(size_t)k];
+                child.direction = dir;
+                child.bound = nb;
+                child.parent_obj = r.objective;
+                child.bnd = std::move(cb);
+                open.insert({child.parent_obj, child.id});
+                nodes.push_back(std::move(child));
+            }
+        }
+        if (final_status >= 0) break;
+    }
+    if (final_status < 0) final_status = has_inc ? DZG_OPTIMAL : DZG_INFEASIBLE;
+    res->status = final_status;
+    res->has_incumbent = has_inc ? 1 : 0;
+    if (has_inc) {
+        res->objective = inc;
+        if (res->values && nvars > 0) std::copy(inc_values.begin(), inc_values.begin() + nvars, res->values);
+    }
+    double bb = has_inc ? inc : -__builtin_inf();
+    if (final_status == DZG_NODE_LIMIT)
+        for (const OpenKey &key : open) bb = std::max(bb, key.bound);
+    res->best_bound = bb;
+    return final_status;
+}

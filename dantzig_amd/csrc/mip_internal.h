@@ -1,0 +1,95 @@
+// mip_internal.h -- library-internal seams of the MILP search (not part of the C ABI):
+//   * the standard-form builder of model.cpp (Simplex::new), used by mip.cpp to make a structure;
+//   * the node-LP solver of k_mip.hip, called by mip.cpp once per round.
+#pragma once
+
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "../../include/dantzig_amd.h"
+
+namespace dzg_internal {
+
+struct Built {
+    int64_t m = 0, n = 0, ns = 0;
+    std::vector<double> a; // column-major m x ns, lda = m (dense mode)
+    bool sparse = false;   // large, sparse models: structural block kept CSC, never densified
+    std::vector<int64_t> col_ptr;
+    std::vector<int32_t> row_idx;
+    std::vector<double> val;
+    std::vector<int64_t> var_col, basis, nonbasis, pos_var, neg_var;
+    std::vector<double> c, x, z;
+    double constant = 0.0;
+    // per row: -1 for a user row, 2u for the ub row of user variable u, 2u + 1 for its lb row
+    std::vector<int64_t> row_tag;
+};
+
+bool valid(const dzg_model *md);
+void build(const dzg_model *md, Built &out, bool allow_sparse);
+void solution_values(const dzg_model *md, const Built &b, const int64_t *basis, const double *x,
+                     double *values);
+
+// ---- k_mip.hip
+
+// A structure: the standard form shared by every node whose integer variables have the same set
+// of finite bounds.  Row r's right-hand side is b0[r] when row_int[r] < 0; otherwise it is read
+// from the node's bounds, bnd[row_int[r]] (an ub row, odd code) or -bnd[row_int[r]] (an lb row,
+// even code), with bnd = {lb_0, ub_0, lb_1, ub_1, ...} over the integer variables.
+struct MipStructure {
+    int m = 0, n = 0, ns = 0;
+    double constant = 0.0;
+    std::vector<double> a, b0, c, z0;                  // a: m x ns column-major
+    std::vector<int> var_col, row_int, basis0, nonbasis0;
+    std::vector<int> pos_var, neg_var;                 // nvars each, -1 if unseen
+};
+
+// The kernel's record of one node LP.  branch < 0 when the node is integral (or not OPTIMAL).
+struct MipNodeRecord {
+    int status;
+    int branch;        // index into the integer-variable list, -1: none
+    long long iterations;
+    double objective;  // constant + sum c[basis[p]] x[p], basis-position order
+    double value;      // the branching variable's value
+    int integral;
+    int pad;
+};
+
+struct MipGpu; // device arenas, reused across rounds
+
+int mip_gpu_create(MipGpu **out, int device, int nvars, const std::vector<int> &int_vars);
+void mip_gpu_destroy(MipGpu *g);
+// Registers a structure (uploaded before the next round); returns its id.
+int mip_gpu_add_structure(MipGpu *g, MipStructure &&s);
+// Solves `count` node LPs: node i uses structure sid[i] and bounds bnd[i * 2 * nint ...].
+// rec[i] is filled for every node; values[i * nvars ...] for the integral OPTIMAL ones only.
+int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count, long long max_iter,
+                        double eps, int ppl, double int_tol, MipNodeRecord *rec, double *values);
+
+// The integrality test and the branching rule, shared by the host (sequential route) and the
+// device epilogue so that both take the same decision on the same values.
+#if defined(__HIPCC__)
+__host__ __device__
+#endif
+inline void mip_branch_choice(const double *values, const int *int_vars, int nint, double int_tol,
+                              int *branch, double *value, int *integral)
+{
+    int best = -1;
+    double best_score = -1.0;
+    int all = 1;
+    for (int k = 0; k < nint; ++k) {
+        const double v = values[int_vars[k]];
+        if (!(fabs(v - rint(v)) <= int_tol)) all = 0;
+        const double f = v - floor(v);
+        const double score = fmin(f, 1.0 - f);
+        if (score > best_score) {
+            best_score = score;
+            best = k;
+        }
+    }
+    *integral = all;
+    *branch = all ? -1 : best;
+    *value = all || best < 0 ? 0.0 : values[int_vars[best]];
+}
+
+} // namespace dzg_internal

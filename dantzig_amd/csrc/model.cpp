@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "../../include/dantzig_amd.h"
+#include "mip_internal.h"
 
 namespace {
 
@@ -25,19 +26,12 @@ struct Row {
     std::vector<int64_t> id; // internal ids: 2*ord = x+, 2*ord+1 = x-, slack0 + r = slack
     std::vector<double> coef;
     double b = 0.0;
+    int64_t tag = -1;        // Built::row_tag
 };
 
-struct Built {
-    int64_t m = 0, n = 0, ns = 0;
-    std::vector<double> a; // column-major m x ns, lda = m (dense mode)
-    bool sparse = false;   // large, sparse models: structural block kept CSC, never densified
-    std::vector<int64_t> col_ptr;
-    std::vector<int32_t> row_idx;
-    std::vector<double> val;
-    std::vector<int64_t> var_col, basis, nonbasis, pos_var, neg_var;
-    std::vector<double> c, x, z;
-    double constant = 0.0;
-};
+} // namespace
+
+namespace dzg_internal {
 
 bool valid(const dzg_model *md)
 {
@@ -74,6 +68,7 @@ void build(const dzg_model *md, Built &out, bool allow_sparse)
             r.id = {pos, neg};
             r.coef = {1.0, -1.0};
             r.b = md->ub[u];
+            r.tag = 2 * u;
             bound_rows.push_back(std::move(r));
         }
         if (md->has_lb[u]) { // :145-148
@@ -81,6 +76,7 @@ void build(const dzg_model *md, Built &out, bool allow_sparse)
             r.id = {pos, neg};
             r.coef = {-1.0, 1.0};
             r.b = -md->lb[u];
+            r.tag = 2 * u + 1;
             bound_rows.push_back(std::move(r));
         }
     };
@@ -129,6 +125,8 @@ void build(const dzg_model *md, Built &out, bool allow_sparse)
     out.m = m;
     out.n = n;
     out.ns = ns;
+    out.row_tag.resize((size_t)m);
+    for (int64_t r = 0; r < m; ++r) out.row_tag[(size_t)r] = rows[(size_t)r].tag;
     out.constant = md->obj_const;
     out.c.assign((size_t)n, 0.0);
     for (int64_t t = 0; t < md->obj_nterms; ++t) { // Objective::new, assignment
@@ -222,7 +220,12 @@ void solution_values(const dzg_model *md, const Built &b, const int64_t *basis, 
     }
 }
 
-} // namespace
+} // namespace dzg_internal
+
+using dzg_internal::Built;
+using dzg_internal::build;
+using dzg_internal::solution_values;
+using dzg_internal::valid;
 
 extern "C" int dzg_build_standard_form(const dzg_model *md, dzg_stdform *out)
 {

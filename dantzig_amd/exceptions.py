@@ -17,3 +17,8 @@ class InfeasibleError(SolveError):
 class NearTieWarning(UserWarning):
     """FAST numerics met a pivot choice within rounding of a tie on a model too large for the
     bit-exact re-solve (not in the reference: it has one arithmetic only)."""
+
+
+class MipLimitWarning(UserWarning):
+    """Branch and bound stopped at its node limit: the best integral solution found so far is
+    returned, not a proven optimum (not in the reference: it has no integer variables)."""

@@ -114,11 +114,13 @@ class _Algebra:
 class Variable(_Algebra):
     """A decision variable with optional inclusive bounds (model.py:8-46).
 
-    `lb` and `ub` are both required keywords; None means unbounded on that side."""
+    `lb` and `ub` are both required keywords; None means unbounded on that side.  integer=True (an
+    addition of this package) asks .solve() for an integral value: the model is then solved by
+    branch and bound (rust.solve_mip)."""
 
-    def __init__(self, *, lb, ub, name=None) -> None:
+    def __init__(self, *, lb, ub, integer: bool = False, name=None) -> None:
         self._name = name
-        self._variable = rs.Variable(lb=lb, ub=ub)
+        self._variable = rs.Variable(lb=lb, ub=ub, integer=integer)
 
     @classmethod
     def free(cls, name=None) -> "Variable":
@@ -132,6 +134,14 @@ class Variable(_Algebra):
     def nonpos(cls, name=None) -> "Variable":
         return cls(lb=None, ub=0.0, name=name)
 
+    @classmethod
+    def integer(cls, lb=0.0, ub=None, name=None) -> "Variable":
+        return cls(lb=lb, ub=ub, integer=True, name=name)
+
+    @classmethod
+    def binary(cls, name=None) -> "Variable":
+        return cls(lb=0.0, ub=1.0, integer=True, name=name)
+
     nn = nonneg
     np = nonpos
 
@@ -139,6 +149,7 @@ class Variable(_Algebra):
     id = property(lambda self: self._variable.id)
     lb = property(lambda self: self._variable.lb)
     ub = property(lambda self: self._variable.ub)
+    is_integer = property(lambda self: self._variable.is_integer)
 
     def to_rust_variable(self) -> rs.Variable:
         return self._variable
@@ -150,7 +161,8 @@ class Variable(_Algebra):
         return hash(self.id)
 
     def __repr__(self) -> str:
-        return f"Variable(id={self.id}, lb={self.lb}, ub={self.ub})"
+        extra = ", integer=True" if self.is_integer else ""
+        return f"Variable(id={self.id}, lb={self.lb}, ub={self.ub}{extra})"
 
 
 class LinExpr(_Algebra):

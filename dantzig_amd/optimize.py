@@ -1,7 +1,8 @@
 """Minimize / Maximize / Solution (python-source/dantzig/optimize.py:8-154).
 
 The core always maximises: Minimize negates the objective on the way in and the optimal value
-on the way out (optimize.py:114-117, :21-27)."""
+on the way out (optimize.py:114-117, :21-27).  A model with an integer variable is solved by
+branch and bound (rust.solve_mip); Solution.mip then reports the search in the user's sense."""
 from __future__ import annotations
 
 import abc
@@ -27,6 +28,18 @@ class Solution:
 
     def __getitem__(self, variable: Variable) -> float:
         return self._solution[variable.to_rust_variable()]
+
+    @property
+    def mip(self):
+        """None for an LP.  For a model with integer variables: the search's MipInfo (status,
+        nodes, rounds, lp_iterations, best_bound, gap), best_bound in the user's sense."""
+        info = self._solution.mip
+        if info is None or self._sense == "maximize":
+            return info
+        flipped = rs.MipInfo(**{k: getattr(info, k) for k in rs.MipInfo.__slots__})
+        flipped.best_bound = -info.best_bound
+        flipped.objective = None if info.objective is None else -info.objective
+        return flipped
 
 
 class Optimize(abc.ABC):
@@ -64,7 +77,10 @@ class Optimize(abc.ABC):
 
     def solve(self) -> Solution:
         """Solve on the GPU.  Raises exceptions.UnboundedError / InfeasibleError."""
-        return Solution(solution=rs.solve(*self._rust_problem()), sense=self.sense)
+        objective, constraints = self._rust_problem()
+        if rs._has_integer(objective, constraints):
+            return Solution(solution=rs.solve_mip(objective, constraints), sense=self.sense)
+        return Solution(solution=rs.solve(objective, constraints), sense=self.sense)
 
 
 class Minimize(Optimize):

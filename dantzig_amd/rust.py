@@ -11,6 +11,9 @@ and operator behaviour, backed by the HIP engine through the C ABI
     PyInequality(*, linexpr, b)                                     src/pyobjs.rs:135-152
     PySolution                     .objective_value, [Variable]     src/pyobjs.rs:154-175
     solve(objective, constraints)  -> PySolution                    src/lib.rs:16-27
+
+Additions of this package: Variable(..., integer=True) and solve_mip() (branch and bound,
+dzg_mip_solve), set_options() / set_mip_options() for the engine's knobs, solve_many().
 """
 from __future__ import annotations
 
@@ -22,13 +25,15 @@ import warnings
 import numpy as np
 
 from . import _ffi
-from .exceptions import InfeasibleError, NearTieWarning, UnboundedError
+from .exceptions import InfeasibleError, MipLimitWarning, NearTieWarning, UnboundedError
 
 _counter = itertools.count()          # static COUNTER: AtomicUsize, src/pyobjs.rs:8
 _counter_lock = threading.Lock()
 
 # options applied by solve(); see set_options()
 _options: dict = {}
+# options applied by solve_mip(); see set_mip_options()
+_mip_options: dict = {}
 
 
 def set_options(**opts) -> None:
@@ -37,6 +42,14 @@ def set_options(**opts) -> None:
     _ffi.default_opts(**opts)  # validates names
     _options.clear()
     _options.update(opts)
+
+
+def set_mip_options(**opts) -> None:
+    """Branch-and-bound knobs for subsequent solve_mip() calls (fields of dzg_mip_opts: node_limit,
+    nodes_per_round, pivots_per_launch, int_tol, abs_gap, rel_gap)."""
+    _ffi.default_mip_opts(**opts)  # validates names
+    _mip_options.clear()
+    _mip_options.update(opts)
 
 
 def _opt_float(v, what: str):
@@ -48,20 +61,23 @@ def _opt_float(v, what: str):
 
 
 class Variable:
-    __slots__ = ("_id", "_lb", "_ub")
+    __slots__ = ("_id", "_lb", "_ub", "_integer")
 
-    def __init__(self, *, lb, ub):
+    def __init__(self, *, lb, ub, integer: bool = False):
         self._lb = _opt_float(lb, "lb")
         self._ub = _opt_float(ub, "ub")
+        self._integer = bool(integer)
         with _counter_lock:
             self._id = next(_counter)
 
     id = property(lambda self: self._id)
     lb = property(lambda self: self._lb)
     ub = property(lambda self: self._ub)
+    is_integer = property(lambda self: self._integer)
 
     def __repr__(self) -> str:
-        return f"rust.Variable(id={self._id}, lb={self._lb}, ub={self._ub})"
+        extra = ", integer=True" if self._integer else ""
+        return f"rust.Variable(id={self._id}, lb={self._lb}, ub={self._ub}{extra})"
 
 
 def _check_number(k, what: str) -> float:
@@ -137,16 +153,34 @@ class PyInequality:
         self._b = _check_number(b, "b")
 
 
+class MipInfo:
+    """What the branch and bound of solve_mip() did (core sense: maximised).  `log` is the node
+    log, a list of dzg_mip_node tuples (id, parent, branch_var, direction, bound, status,
+    iterations, objective) when solve_mip(..., node_log=N) asked for one."""
+    __slots__ = ("status", "nodes", "rounds", "lp_iterations", "best_bound", "gap", "objective",
+                 "nodes_batched", "nodes_sequential", "nodes_pruned", "nodes_dropped",
+                 "incumbent_node", "failed_node", "log")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def __repr__(self) -> str:
+        return (f"MipInfo(status={self.status!r}, nodes={self.nodes}, rounds={self.rounds}, "
+                f"lp_iterations={self.lp_iterations}, best_bound={self.best_bound}, gap={self.gap})")
+
+
 class PySolution:
-    __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape")
+    __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape", "mip")
 
     def __init__(self, objective_value: float, values: dict, iterations: int = 0,
-                 numerics: str = "", shape=(0, 0)):
+                 numerics: str = "", shape=(0, 0), mip: "MipInfo | None" = None):
         self._objective_value = objective_value
         self._values = values
         self.iterations = iterations    # extras the reference does not expose
         self.numerics = numerics
         self.shape = shape
+        self.mip = mip                  # None for an LP
 
     objective_value = property(lambda self: self._objective_value)
 
@@ -240,18 +274,100 @@ def solve(objective: PyAffExpr, constraints) -> PySolution:
     return out
 
 
+def _has_integer(objective: PyAffExpr, constraints) -> bool:
+    if any(v.is_integer for v in objective.pylinexpr.vars):
+        return True
+    return any(v.is_integer for ineq in constraints for v in ineq._linexpr.vars)
+
+
+def _mip_call(arrays: dict, is_integer, node_log: int = 0, **mip_opts):
+    """dzg_mip_solve on lowered arrays (is_integer: one flag per variable of the table):
+    (result struct, values, log entries)."""
+    is_int = np.array(list(is_integer) + [0], dtype=np.int32)
+    values = np.zeros(max(arrays["nvars"], 1))
+    res = _ffi.MipResult()
+    res.values = _ffi.ptr(values)
+    log = (_ffi.MipNode * max(int(node_log), 1))()
+    if node_log:
+        res.log = C.cast(log, C.c_void_p)
+        res.log_cap = int(node_log)
+    opts = _ffi.default_opts(**_options)
+    mo = _ffi.default_mip_opts(**{**_mip_options, **mip_opts})
+    md = _c_model(arrays)
+    rc = _ffi.lib().dzg_mip_solve(C.byref(md), _ffi.ptr(is_int), C.byref(opts), C.byref(mo),
+                                  C.byref(res))
+    _ffi.check(rc, "dzg_mip_solve")
+    entries = [(e.id, e.parent, e.branch_var, e.direction, e.bound, e.status, e.iterations,
+                e.objective) for e in log[:res.log_count]]
+    return res, values, entries
+
+
+def _mip_outcome(res, values, order, entries, where: str = "", stacklevel: int = 4):
+    """The PySolution of one dzg_mip_result, or the exception solve_mip() raises for it."""
+    rc = int(res.status)
+    gap = abs(res.best_bound - res.objective) if res.has_incumbent else float("inf")
+    info = MipInfo(status=_ffi.status_str(rc), nodes=int(res.nodes_solved), rounds=int(res.rounds),
+                   lp_iterations=int(res.lp_iterations), best_bound=float(res.best_bound), gap=gap,
+                   objective=float(res.objective) if res.has_incumbent else None,
+                   nodes_batched=int(res.nodes_batched), nodes_sequential=int(res.nodes_sequential),
+                   nodes_pruned=int(res.nodes_pruned), nodes_dropped=int(res.nodes_dropped),
+                   incumbent_node=int(res.incumbent_node), failed_node=int(res.failed_node),
+                   log=entries)
+    if rc == _ffi.INFEASIBLE:
+        return InfeasibleError("The model is infeasible (no integral point)" + where)
+    if rc == _ffi.UNBOUNDED and res.failed_node == 0:
+        return UnboundedError("The objective is unbounded (the root relaxation is unbounded)" + where)
+    if rc == _ffi.NODE_LIMIT:
+        if not res.has_incumbent:
+            return RuntimeError(f"branch and bound hit the node limit after {res.nodes_solved} nodes "
+                                f"without an integral solution{where}")
+        warnings.warn(f"branch and bound hit the node limit after {res.nodes_solved} nodes: the "
+                      f"incumbent is returned, best bound {res.best_bound!r}{where}", MipLimitWarning,
+                      stacklevel=stacklevel)
+    elif rc != _ffi.OPTIMAL:
+        return RuntimeError(f"branch and bound stopped: node {res.failed_node} ended with status "
+                            f"{_ffi.status_str(rc)!r}{where}")
+    # "fast" when at least one node LP was too large for STRICT under AUTO (dzg_model_solve's rule)
+    numerics = "fast" if res.nodes_fast > 0 else "strict"
+    return PySolution(float(res.objective), {v.id: float(values[i]) for i, v in enumerate(order)},
+                      int(res.lp_iterations), numerics, (0, 0), info)
+
+
+def solve_mip(objective: PyAffExpr, constraints, *, node_log: int = 0, **mip_opts) -> PySolution:
+    """Maximise `objective` subject to `constraints` with the variables marked integer=True held
+    integral: branch and bound on the GPU (dzg_mip_solve).  Options: set_mip_options(), overridden
+    per call by keyword.  The returned PySolution carries .mip (a MipInfo); its .numerics is
+    "strict" unless some node LP ran in FAST numerics.  Raises InfeasibleError (no integral
+    point), UnboundedError (the root relaxation is unbounded: such a model may in fact be
+    infeasible), RuntimeError (a node LP failed, or the node limit was hit with no incumbent); at
+    the node limit with an incumbent it warns MipLimitWarning and returns the incumbent."""
+    if not isinstance(objective, PyAffExpr):
+        raise TypeError("objective must be a PyAffExpr")
+    arrays, order = lower(objective, list(constraints))
+    _ffi.require_gpu()
+    res, values, entries = _mip_call(arrays, [v.is_integer for v in order], node_log, **mip_opts)
+    out = _mip_outcome(res, values, order, entries if node_log else None)
+    if isinstance(out, Exception):
+        raise out
+    return out
+
+
 def solve_many(problems, *, return_exceptions: bool = False) -> list:
     """solve() for every (objective, constraints) pair of `problems`, in one dzg_model_solve_batch
     call: the models that solve() would run in STRICT numerics on at most 128 rows share one batch
     on the GPU (one workgroup per model), the others are solved one at a time.  Results keep the
     order of `problems` and equal solve()'s one for one.  A model that ends unbounded or infeasible
     raises solve()'s exception, its index in the message, once the whole batch is done; with
-    return_exceptions=True the exception instance stands in that model's place instead."""
-    lowered = []
-    for i, (objective, constraints) in enumerate(problems):
+    return_exceptions=True the exception instance stands in that model's place instead.  Models with
+    an integer variable are solved one by one through solve_mip(), after the batch."""
+    problems = [(objective, list(constraints)) for objective, constraints in problems]
+    for i, (objective, _) in enumerate(problems):
         if not isinstance(objective, PyAffExpr):
             raise TypeError(f"problems[{i}]: objective must be a PyAffExpr")
-        lowered.append(lower(objective, list(constraints)))
+    mip = [_has_integer(objective, constraints) for objective, constraints in problems]
+    lp_idx = [i for i in range(len(problems)) if not mip[i]]
+    out: list = [None] * len(problems)
+    lowered = [lower(*problems[i]) for i in lp_idx]
     count = len(lowered)
     keep = [(_c_model(arrays), np.zeros(max(len(order), 1))) for arrays, order in lowered]
     models = (_ffi.Model * max(count, 1))(*[md for md, _ in keep])
@@ -261,8 +377,13 @@ def solve_many(problems, *, return_exceptions: bool = False) -> list:
     opts = _ffi.default_opts(**_options)
     rc = _ffi.lib().dzg_model_solve_batch(models, C.c_int64(count), C.byref(opts), results)
     _ffi.check(rc, "dzg_model_solve_batch")
-    out = [_outcome(results[i], keep[i][1], lowered[i][1], f" (model {i})", stacklevel=3)
-           for i in range(count)]
+    for k, i in enumerate(lp_idx):
+        out[i] = _outcome(results[k], keep[k][1], lowered[k][1], f" (model {i})", stacklevel=3)
+    for i in range(len(problems)):
+        if mip[i]:
+            arrays, order = lower(*problems[i])
+            res, values, _ = _mip_call(arrays, [v.is_integer for v in order])
+            out[i] = _mip_outcome(res, values, order, None, f" (model {i})", stacklevel=3)
     if not return_exceptions:
         for o in out:
             if isinstance(o, Exception):

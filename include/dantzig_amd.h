@@ -50,6 +50,8 @@ typedef enum {
                              reference's arithmetic may choose differently.  The state is that
                              of the last executed pivot; dzg_solver_run resumes (that decision is
                              then taken as FAST sees it and counted in near_ties)         */
+    DZG_NODE_LIMIT = 8,   /* dzg_mip_solve: node_limit node LPs solved with the search still open;
+                             the incumbent, if there is one, is returned                  */
     DZG_E_DEVICE = -1,    /* HIP error, or no usable GPU (the product has no CPU path) */
     DZG_E_ARG = -2,       /* malformed input                                           */
     DZG_E_NOMEM = -3
@@ -377,6 +379,62 @@ int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
  * one batch; the others go through dzg_model_solve one at a time. */
 int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
                           dzg_model_result *res);
+
+/* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
+
+/* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
+ * "default" (node_limit 100000, nodes_per_round 1024, pivots_per_launch 16) while the tolerances are
+ * taken as given (0 = exact).  Negative counts or tolerances and NaN tolerances are DZG_E_ARG. */
+typedef struct {
+    int64_t node_limit;        /* node LPs solved at most, then DZG_NODE_LIMIT; 0 = 100000        */
+    int32_t nodes_per_round;   /* open nodes solved together per round; 0 = 1024                  */
+    int32_t reserved0;
+    int64_t pivots_per_launch; /* as in dzg_batch_solve; 0 = 16                                   */
+    double int_tol;            /* v is integral if |v - rint(v)| <= int_tol (default 1e-6)        */
+    double abs_gap;            /* prune when objective <= incumbent + max(abs_gap, rel_gap*|inc|) */
+    double rel_gap;            /*   (defaults 1e-9 and 0)                                         */
+} dzg_mip_opts;
+
+/* One solved node LP.  The root has id 0, parent -1, branch_var -1, direction 0.  A child records
+ * the user variable branched on, direction -1 (down: ub = floor v) or +1 (up: lb = floor v + 1)
+ * and that new bound.  objective (core sense) is meaningful when status is DZG_OPTIMAL. */
+typedef struct {
+    int64_t id, parent, branch_var;
+    int32_t direction, status;
+    double bound;
+    int64_t iterations;
+    double objective;
+} dzg_mip_node;
+
+typedef struct {
+    int32_t status;            /* OPTIMAL, INFEASIBLE, UNBOUNDED (root relaxation), NODE_LIMIT, or
+                                  the status of the node LP that failed (see failed_node)        */
+    int32_t has_incumbent;
+    double objective;          /* the incumbent's, core sense (maximised)                          */
+    double *values;            /* nvars, optional: the incumbent node LP's own values (not rounded) */
+    double best_bound;         /* max of the incumbent and the open nodes' parent bounds           */
+    int64_t nodes_solved, nodes_batched, nodes_sequential;
+    int64_t nodes_fast;        /* sequential node LPs dzg_model_solve ran in FAST numerics (AUTO,
+                                  m > auto_strict_rows): 0 means every node LP is STRICT           */
+    int64_t nodes_pruned;      /* pruned by bound, after solving or when selected                  */
+    int64_t nodes_dropped;     /* infeasible node LPs and children whose bounds cross (never created) */
+    int64_t rounds, lp_iterations;
+    int64_t incumbent_node, failed_node; /* -1 when none */
+    dzg_mip_node *log;         /* optional caller-owned node log, log_cap entries, in solve order  */
+    int64_t log_cap, log_count;
+} dzg_mip_result;
+
+void dzg_mip_opts_default(dzg_mip_opts *mo);
+/* Maximises model's objective with is_integer[u] != 0 marking integer variables.  Every node LP is
+ * the model with the integer variables' bounds replaced by the node's, solved exactly as
+ * dzg_model_solve(node model, opts) solves it: nodes that call would run in STRICT on <= 128 dense
+ * rows go through k_mip.hip in batched rounds, the others through dzg_model_solve one at a time.
+ * The search (best bound first, most fractional branching, incumbent updated between rounds) is
+ * deterministic for a given nodes_per_round.  opts / mip_opts NULL: defaults.  FAST numerics is
+ * DZG_E_ARG, and so is a bound of an integer variable that is flagged (has_lb / has_ub) but not
+ * finite: the search keys nodes on which integer bounds are finite.  Returns res->status (>= 0) or a negative code. */
+int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
+                  const dzg_mip_opts *mip_opts, dzg_mip_result *res);
 
 /* Host-only: the standard-form builder alone (Simplex::new, src/simplex.rs:123-224).
  * Two-call protocol: first call with out->a == NULL fills m, n, n_struct and lda;
