@@ -8,21 +8,26 @@ fp64 LP (generator G1, seed 1003).  One "step" = one executed pivot
 between barriers, continuing the same solve trajectory.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--rows M --cols NS --seed S]
-                  [--price tree|seq|wave] [--no-cpu-baseline] [--no-pmc-traffic] [--no-secondary]
-                  [--no-late] [--late-pivots N] [--warm-k K] [--cpu-size-pivots N]
-                  [--dump-outputs DIR]
+                  [--price tree|seq|wave] [--dump-outputs DIR]
+                  [--full [--no-cpu-baseline] [--no-pmc-traffic] [--no-secondary] [--no-late]
+                          [--late-pivots N] [--cpu-size-pivots N]] [--warm-k K]
 
-`value` is the rate of the K pivots that follow the warm-up (an almost empty basis inverse); the
-"late", "deep" and "end" blocks time K more pivots of the same solve after 20 000, 150 000 and
-400 000 pivots, with the basis inverse grown (config.k_at_* / <block>.k_at_* = its dense columns)
-and a per-kernel-class split; "whole_solve" is the solve to optimality.  The pricing pass is timed
-with HIP events on the solver's stream around every 8th pass (roofline.launches_timed) and its HBM
-traffic counted by rocprofv3 --pmc children (the timed region's pivots; and, warm-started, the deep
-and end blocks' widths).  "cpu_baseline": the CPU oracle on this host -- real pivots of the same LP
-at the same size by its blocked twin on 16 threads, the literal one-core loop beside it.
+`value` is the rate of the K pivots that follow the warm-up (an almost empty basis inverse).  The
+pricing pass is timed with HIP events on the solver's stream around every 8th pass of those pivots
+(roofline.launches_timed).  A plain run measures that and nothing else: it sets up, warms up, times
+the K pivots, writes --dump-outputs if asked, and prints the line.
 
-The default invocation also measures config 5 (32768 x 65536, the LP the multi-GPU target is quoted
-on) and reports it under "secondary"; `value` is always the 8192 x 16384 LP.
+Everything else is measured with --full only, as far as the --no-* options leave it: the "late",
+"deep" and "end" blocks time K more pivots of the same solve after 20 000, 150 000 and 400 000
+pivots, with the basis inverse grown (config.k_at_* / <block>.k_at_* = its dense columns) and a
+per-kernel-class split; "whole_solve" is the solve to optimality; the pricing pass's HBM traffic is
+counted by rocprofv3 --pmc children (the timed region's pivots; and, warm-started, the deep and end
+blocks' widths); "mfma" times refactorisations.  "cpu_baseline": the CPU oracle on this host --
+real pivots of the same LP at the same size by its blocked twin on 16 threads, the literal one-core
+loop beside it.  On the default workload --full also measures config 5 (32768 x 65536, the LP the
+multi-GPU target is quoted on) and reports it under "secondary"; `value` is always the
+8192 x 16384 LP.  With --gpus N, --full adds the replicated and basis-replicated storage forms
+and config 5 (sharded.bench_main).
 
 --dump-outputs DIR (one GPU): right after the timed pivots, what dzg_solver_result hands the caller
 of the timed path is written to DIR/<name>.npy in float64 -- see dump_outputs().  The LP is seeded,
@@ -208,12 +213,12 @@ def pmc_traffic(args, warm_k: int = 0, steps: int | None = None, warmup: int | N
                 # the SAME pivots as the timed region (warm-up included: the counters see every
                 # launch of the child), so that the bytes per pricing pass can stand beside the
                 # algorithmic bytes of the same passes -- both depend on k, which grows with the pivots
+                # (a plain run: the child measures its timed region and nothing else)
                 cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", out, "--",
                        sys.executable, os.path.abspath(__file__), "--steps", str(steps),
                        "--warmup", str(warmup), "--warm-k", str(warm_k),
                        "--rows", str(args.rows), "--cols", str(args.cols), "--seed", str(args.seed),
-                       "--price", args.price, "--no-cpu-baseline", "--no-pmc-traffic",
-                       "--no-secondary", "--no-late"]
+                       "--price", args.price]
                 if args.sparse_per_col > 0:
                     cmd += ["--sparse-per-col", str(args.sparse_per_col)]
                 with open(os.path.join(out, "child.json"), "w") as child_out:
@@ -356,7 +361,7 @@ def under_profiler() -> bool:
 
 
 def secondary_wanted(args) -> bool:
-    """The config-5 measurement rides along with the default invocation only."""
+    """The config-5 measurement rides along with the default workload only (in a --full run: main)."""
     return (not args.no_secondary and not under_profiler() and args.rows == 8192
             and args.cols == 16384 and args.sparse_per_col == 0 and args.numerics == "fast")
 
@@ -686,6 +691,33 @@ def measure(rows, cols, seed, sparse_per_col, price_name, numerics_name, steps, 
     return out
 
 
+def sharded_plain(args, rank: int, world: int, local_rank: int) -> int:
+    """--gpus N without --full: the partitioned run that gives `value` and nothing else, set up and
+    printed as sharded.bench_main does (which adds the replicated and basis-replicated forms, config 5
+    and the CPU baseline)."""
+    import datetime
+
+    import torch
+    import torch.distributed as dist
+
+    from dantzig_amd import _ffi, sharded
+
+    # stdout carries exactly one JSON line (gloo / RCCL banners go to stderr)
+    sys.stdout.flush()
+    json_fd = os.dup(1)
+    os.dup2(2, 1)
+    _ffi.require_gpu()
+    dist.init_process_group("gloo", rank=rank, world_size=world, timeout=datetime.timedelta(seconds=900))
+    out = sharded._measure_sharded(dist, torch, args.rows, args.cols, args.seed, args.price, args.steps,
+                                   args.warmup, rank, world, local_rank, replicate=False)
+    dist.barrier()
+    dist.destroy_process_group()
+    if rank == 0:
+        os.write(json_fd, (json.dumps(out) + "\n").encode())
+    os.close(json_fd)
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -696,6 +728,13 @@ def main() -> int:
     ap.add_argument("--seed", type=int, default=1003)
     ap.add_argument("--price", choices=["auto", "tree", "seq", "wave"], default="auto")
     ap.add_argument("--numerics", choices=["fast", "strict"], default="fast")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline figure: the pricing pass's HBM traffic "
+                         "and the refactorisation's MfmaUtil from rocprofv3 --pmc children, the late / deep / "
+                         "end regimes of the same solve with a per-kernel split, timed refactorisations, the "
+                         "rest of the solve (default workload), config 5 (\"secondary\") and the CPU baseline; "
+                         "with --gpus N the replicated and basis-replicated forms and config 5 with its deep "
+                         "block.  The --no-* options below trim a --full run")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc-traffic", action="store_true")
     ap.add_argument("--no-late", action="store_true",
@@ -715,13 +754,13 @@ def main() -> int:
     ap.add_argument("--whole-solve", action="store_true",
                     help="after the timed regions run the solve to its end and report the stretch and "
                          "the whole solve's average (the benchmark LP: ~515 000 pivots, ~1.5 minutes); "
-                         "on by default for the default workload")
+                         "on with --full for the default workload")
     ap.add_argument("--no-whole-solve", action="store_true")
     ap.add_argument("--seven-launches", action="store_true",
                     help="FAST, dense, one GPU: run an iteration as the seven launches a sharded "
                          "solver uses instead of the three-launch chain (same pivots)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the 32768x65536 measurement that rides along with the default run")
+                    help="skip the 32768x65536 measurement that rides along with a --full run")
     ap.add_argument("--sparse-per-col", type=int, default=0,
                     help="generator G2: this many nonzeros per column, matrix kept CSC on the device")
     ap.add_argument("--force-sharded", action="store_true",
@@ -775,19 +814,21 @@ def main() -> int:
     if world > 1 or args.force_sharded:
         from dantzig_amd import sharded  # column-sharded path, native RCCL loop
 
+        if not args.full:
+            return sharded_plain(args, rank, world, local_rank)
         return sharded.bench_main(args, rank, world, local_rank)
 
     # children first: no GPU state yet (and none at all under a profiler)
-    traffic = None if (args.no_pmc_traffic or under_profiler()) else pmc_traffic(args)
+    traffic = None if (not args.full or args.no_pmc_traffic or under_profiler()) else pmc_traffic(args)
     default_dense = args.rows == 8192 and args.cols == 16384 and args.sparse_per_col == 0 \
         and args.numerics == "fast"
     # the same counters where the pass STREAMS: children warm-started at the compact widths of the
-    # `deep` and `end` blocks (default invocation only)
+    # `deep` and `end` blocks (a --full run of the default workload only)
     regime_traffic = {}
     if traffic is not None and default_dense and not (args.no_late or args.warm_k):
         for name, wk in (("deep", 4050), ("end", 7650)):
             regime_traffic[name] = pmc_traffic(args, warm_k=wk, steps=200, warmup=50)
-    mfma_wanted = default_dense and not (args.no_late or args.no_mfma or under_profiler())
+    mfma_wanted = default_dense and args.full and not (args.no_late or args.no_mfma or under_profiler())
     mfma_pmc = pmc_mfma(args, args.rows) if (mfma_wanted and not args.no_pmc_traffic) else None
 
     from dantzig_amd import _ffi
@@ -795,7 +836,7 @@ def main() -> int:
     # one HIP runtime per process: the library's.  dzg_solver_run returns after synchronising
     # its stream, which brackets the timed region the way torch.cuda.synchronize() would.
     _ffi.require_gpu()
-    late_pivots = 0 if (args.no_late or under_profiler()) else args.late_pivots
+    late_pivots = 0 if (not args.full or args.no_late or under_profiler()) else args.late_pivots
     global SEVEN_LAUNCHES
     SEVEN_LAUNCHES = bool(args.seven_launches)
     global EVENT_STRIDE  # (a short timed region still gets a few timed passes)
@@ -835,7 +876,7 @@ def main() -> int:
                                         "(profiles/r03_bench_before_row_pricing.json)")
     if under_profiler():
         out["config"]["under_profiler"] = True
-    if secondary_wanted(args):
+    if args.full and secondary_wanted(args):
         # the LP the north star's multi-GPU target is quoted on (config 5), on this one GPU too, so
         # that the per-N lines of a scaling run can be compared on it as well as on config 3
         try:
@@ -854,7 +895,7 @@ def main() -> int:
                 "stands beside" % dp["warm_k"])
         except Exception as exc:  # never lose the primary line to the secondary workload
             out.setdefault("secondary", {})["error"] = f"{type(exc).__name__}: {exc}"
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         at_size = (args.cols, args.seed, args.cpu_size_pivots) if args.cpu_size_pivots > 0 and not args.sparse_per_col else None
         out["cpu_baseline"] = cpu_baseline(args.cpu_sample_rows, 2 * args.cpu_sample_rows, 1002,
                                            args.cpu_sample_pivots, args.rows, args.cpu_anchor_rows, at_size)

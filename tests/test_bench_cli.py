@@ -1,6 +1,7 @@
-"""bench.py host logic that needs no GPU: what rides along with which invocation, profiler
-detection, the loud failure when there is no device, and what --dump-outputs writes; one gpu-marked
-test runs --dump-outputs end to end."""
+"""bench.py host logic that needs no GPU: what rides along with which invocation (a plain run times
+its steps and nothing else, --full adds the rest), profiler detection, the loud failure when there is
+no device, and what --dump-outputs writes; gpu-marked tests run a plain line and --dump-outputs end
+to end."""
 import argparse
 import importlib.util
 import os
@@ -47,6 +48,70 @@ def test_profiler_detection_keeps_the_run_to_one_workload(monkeypatch):
     monkeypatch.delenv("ROCP_TOOL_LIBRARIES")
     monkeypatch.setenv("LD_PRELOAD", "/opt/rocm/lib/librocprofiler-sdk.so")
     assert bench.under_profiler()
+
+
+def _main_calls(monkeypatch, capsys, *argv):
+    """bench.main() with every measurement replaced by a recorder: what a run would start, in order,
+    and the line it prints.  No GPU is touched."""
+    import json
+
+    from dantzig_amd import _ffi, sharded
+
+    bench = _bench()
+    monkeypatch.delenv("ROCP_TOOL_LIBRARIES", raising=False)
+    monkeypatch.setenv("LD_PRELOAD", "")
+    for var in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(var, raising=False)
+    calls = []
+
+    def fake_measure(rows, cols, seed, sparse_per_col, price, numerics, steps, warmup,
+                     late_pivots=0, deep_pivots=0, whole_solve=False, mfma_block=False, end_pivots=0,
+                     warm_k=0, dump_dir=None):
+        calls.append(("measure", rows, steps, warmup, late_pivots, deep_pivots, whole_solve, mfma_block,
+                      end_pivots, warm_k))
+        return {"value": 1.0, "unit": "iterations/s", "steps": steps, "warmup": warmup, "ms_per_step": 1.0,
+                "config": {"k_at_start": 0, "k_at_end": 0}, "roofline": {}}
+
+    monkeypatch.setattr(_ffi, "require_gpu", lambda: None)
+    monkeypatch.setattr(bench, "measure", fake_measure)
+    monkeypatch.setattr(bench, "pmc_traffic", lambda *a, **kw: calls.append(("pmc_traffic",)))
+    monkeypatch.setattr(bench, "pmc_mfma", lambda *a, **kw: calls.append(("pmc_mfma",)))
+    monkeypatch.setattr(bench, "refactor_at", lambda *a, **kw: calls.append(("refactor_at",)))
+    monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **kw: calls.append(("cpu_baseline",)) or {})
+    monkeypatch.setattr(bench, "sharded_plain", lambda *a: calls.append(("sharded_plain",)) or 0)
+    monkeypatch.setattr(sharded, "bench_main", lambda *a: calls.append(("sharded.bench_main",)) or 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+    assert bench.main() == 0
+    out = capsys.readouterr().out.strip().splitlines()
+    return calls, (json.loads(out[-1]) if out else None)
+
+
+def test_plain_run_times_its_steps_and_nothing_else(monkeypatch, capsys):
+    calls, line = _main_calls(monkeypatch, capsys, "--gpus", "1", "--steps", "20", "--warmup", "5")
+    assert calls == [("measure", 8192, 20, 5, 0, 0, False, False, 0, 0)]
+    assert set(line) == {"value", "unit", "steps", "warmup", "ms_per_step", "config", "roofline"}
+    assert line["roofline"]["traffic"] is None
+    # (the --no-* options only trim a --full run; on a plain one they change nothing)
+    calls_no, _ = _main_calls(monkeypatch, capsys, "--steps", "20", "--warmup", "5", "--no-late",
+                              "--no-secondary", "--no-cpu-baseline", "--no-pmc-traffic", "--no-mfma")
+    assert calls_no == calls
+    calls, _ = _main_calls(monkeypatch, capsys, "--force-sharded", "--steps", "20", "--warmup", "5")
+    assert calls == [("sharded_plain",)]
+
+
+def test_full_run_measures_everything_the_default_run_used_to(monkeypatch, capsys):
+    calls, line = _main_calls(monkeypatch, capsys, "--full", "--steps", "20", "--warmup", "5")
+    assert calls == [("pmc_traffic",), ("pmc_mfma",),
+                     ("measure", 8192, 20, 5, 20000, 150000, True, True, 400000, 0),
+                     ("measure", 32768, 300, 50, 0, 0, False, False, 0, 0),
+                     ("measure", 32768, 300, 50, 0, 0, False, False, 0, 16384),
+                     ("cpu_baseline",)]
+    assert {"secondary", "cpu_baseline"} <= set(line)
+    calls, _ = _main_calls(monkeypatch, capsys, "--full", "--steps", "20", "--warmup", "5", "--no-late",
+                           "--no-secondary", "--no-cpu-baseline", "--no-pmc-traffic")
+    assert calls == [("measure", 8192, 20, 5, 0, 0, False, False, 0, 0)]
+    calls, _ = _main_calls(monkeypatch, capsys, "--full", "--force-sharded", "--steps", "20", "--warmup", "5")
+    assert calls == [("sharded.bench_main",)]
 
 
 def test_bench_fails_loudly_without_a_gpu():
@@ -217,3 +282,23 @@ def test_bench_dumps_the_timed_paths_outputs_the_same_on_every_run(tmp_path):
         assert np.array_equal(np.load(tmp_path / "a" / f"{name}.npy"), getattr(want, name).astype(np.float64)), name
     assert np.load(tmp_path / "a" / "objective.npy").tolist() == [want.objective]
     assert np.load(tmp_path / "a" / "pivots.npy").tolist() == [list(map(float, p)) for p in want.pivots[warmup:]]
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_timed_steps_alone():
+    """bench.py --steps K --warmup W without --full: the headline line of exactly K timed pivots, its
+    pricing roofline from the same pivots, and none of what --full adds."""
+    import json
+
+    run = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "40",
+                          "--warmup", "10", "--rows", "256", "--cols", "512"],
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stderr[-2000:]
+    lines = run.stdout.strip().splitlines()
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["metric"] == "simplex_iterations_per_sec" and line["unit"] == "iterations/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 40 and line["warmup"] == 10 and line["value"] > 0 and line["ms_per_step"] > 0
+    assert line["roofline"]["launches"] == 40 and line["roofline"]["traffic"] is None
+    assert not {"late", "deep", "end", "mfma", "whole_solve", "secondary", "cpu_baseline"} & set(line)
