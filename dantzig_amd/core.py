@@ -153,7 +153,7 @@ class CoreResult:
     chain_fallbacks: int = 0            # failed device-wide barriers recovered from (k_chain.hip)
     price_pass_used: int = 0            # bit mask: 1 row-wise pricing pass ran, 2 column-wise
     price_rows_copy: int = 0            # 1: the row-major copy of the matrix is resident
-    state_drift: float = 0.0            # carried x_B / z_N vs the fresh inverse at the last refactorisation
+    state_drift: float = 0.0            # carried x, xbar, z, zbar vs the fresh inverse at the last refactorisation
 
 
 def _counters(r) -> dict:

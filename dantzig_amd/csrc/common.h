@@ -84,7 +84,7 @@ struct DzgCtl {
                           // exchange 2: primal step)
     int price_mask;       // pricing passes the executed pivots ran: 1 row-wise, 2 column-wise
     double dxp;
-    double drift_tau;     // 4 x the relative drift of the carried x, xbar, z against the fresh inverse
+    double drift_tau;     // 4 x the relative drift of the carried x, xbar, z, zbar against the fresh inverse
                           // at the last refactorisation (k_drift.hip); part of tau
     unsigned long long bar_gen; // device-wide barriers passed so far (k_chain.hip)
 };
@@ -605,7 +605,7 @@ void dzg_launch_rs_unpack(const DzgDev &d, int slice, const double *recv, hipStr
 
 // k_drift.hip: carried state against the fresh inverse, at a refactorisation
 void dzg_launch_drift(const DzgDev &d, const double *b0, const double *xb0, const double *cdev,
-                      double *agb, double *agx, double *part, double *y, double *dzy, double *out,
+                      const double *cbdev, double *agb, double *agx, double *part, double *y, double *dzy, double *out,
                       int k_bound, hipStream_t st);
 int dzg_drift_blocks(void);
 int dzg_drift_chunks(void);

@@ -118,10 +118,11 @@ struct dzg_solver {
                                  // triggers a refactorisation
     double max_err_life = 0.0; // largest ctl->max_pivot_err ever read (the device value restarts
                                // at every refactorisation)
-    double state_drift = 0.0;  // carried x_B / z_N against the fresh inverse, at the last refactorisation
+    double state_drift = 0.0;  // carried x, xbar, z, zbar against the fresh inverse, at the last refactorisation
     // k_drift.hip: the data the state is recomputed from (solves that start on the slack basis of a
     // dense matrix on one GPU; nullptr otherwise) and scratch
-    double *dr_b0 = nullptr, *dr_xb0 = nullptr, *dr_c = nullptr, *dr_agb = nullptr, *dr_agx = nullptr,
+    double *dr_b0 = nullptr, *dr_xb0 = nullptr, *dr_c = nullptr, *dr_cb = nullptr, *dr_agb = nullptr,
+           *dr_agx = nullptr,
            *dr_part = nullptr, *dr_y = nullptr, *dr_dzy = nullptr, *dr_out = nullptr;
     // FAST, dense, one GPU: the three-launch chain (k_chain.hip)
     unsigned long long *chain_bar = nullptr; // barrier counters (cleared only by chain_recover)
@@ -634,13 +635,18 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
         const bool needs_initial_refactor = !slack_basis && !s->pending_refactor;
         if (slack_basis && d.world == 1 && !d.csc && m > 0 && q > 0) {
             // the state a refactorisation can be checked against (k_drift.hip): b = the starting x,
-            // xbar0 = the starting xbar, c
+            // xbar0 = the starting xbar, c, and cbar: the c whose reduced costs zbar is (-zbar0 on the
+            // starting nonbasics, 0 on the slacks), as c is for z
             TRY(dev_alloc(s, &s->dr_b0, (size_t)m + 2)); TRY(dev_alloc(s, &s->dr_xb0, (size_t)m + 2));
-            TRY(dev_alloc(s, &s->dr_c, (size_t)n));
+            TRY(dev_alloc(s, &s->dr_c, (size_t)n)); TRY(dev_alloc(s, &s->dr_cb, (size_t)n));
+            std::vector<double> cbar((size_t)n, 0.0);
+            for (int k = 0; k < q; ++k) cbar[(size_t)nonbasis[k]] = -(lp->zbar ? lp->zbar[k] : 1.0);
             HIP_OK(hipMemcpyAsync(s->dr_b0, lp->x, sizeof(double) * m, hipMemcpyHostToDevice, s->st));
             HIP_OK(hipMemcpyAsync(s->dr_xb0, lp->xbar ? lp->xbar : ones.data(), sizeof(double) * m,
                                   hipMemcpyHostToDevice, s->st));
             HIP_OK(hipMemcpyAsync(s->dr_c, lp->c, sizeof(double) * n, hipMemcpyHostToDevice, s->st));
+            HIP_OK(hipMemcpyAsync(s->dr_cb, cbar.data(), sizeof(double) * n, hipMemcpyHostToDevice, s->st));
+            HIP_OK(hipStreamSynchronize(s->st)); // (cbar is a local)
         }
         // row stride: not a multiple of a large power of two, so that the first k columns of
         // consecutive rows do not all land on the same HBM channels
@@ -1109,7 +1115,7 @@ static int shard_sum(dzg_solver *s, double *buf, size_t count)
     return 0;
 }
 
-// The carried x, xbar, z against their recomputation from the inverse the refactorisation has just
+// The carried x, xbar, z, zbar against their recomputation from the inverse the refactorisation has just
 // built (k_drift.hip); the result widens the near-tie tolerance and is reported as state_drift.
 static int measure_drift(dzg_solver *s)
 {
@@ -1119,21 +1125,23 @@ static int measure_drift(dzg_solver *s)
         TRY(dev_alloc(s, &s->dr_agb, (size_t)d.m + 2)); TRY(dev_alloc(s, &s->dr_agx, (size_t)d.m + 2));
         TRY(dev_alloc(s, &s->dr_part, (size_t)dzg_drift_chunks() * (size_t)d.ldw));
         TRY(dev_alloc(s, &s->dr_y, (size_t)d.m + 2)); TRY(dev_alloc(s, &s->dr_dzy, (size_t)d.q));
-        TRY(dev_alloc(s, &s->dr_out, (size_t)6 * dzg_drift_blocks()));
+        TRY(dev_alloc(s, &s->dr_out, (size_t)8 * dzg_drift_blocks()));
     }
-    dzg_launch_drift(d, s->dr_b0, s->dr_xb0, s->dr_c, s->dr_agb, s->dr_agx, s->dr_part, s->dr_y, s->dr_dzy,
-                     s->dr_out, (int)s->h_ctl->ncompact, s->st);
+    dzg_launch_drift(d, s->dr_b0, s->dr_xb0, s->dr_c, s->dr_cb, s->dr_agb, s->dr_agx, s->dr_part, s->dr_y,
+                     s->dr_dzy, s->dr_out, (int)s->h_ctl->ncompact, s->st);
     const int nb = dzg_drift_blocks();
-    std::vector<double> out((size_t)6 * nb);
+    std::vector<double> out((size_t)8 * nb);
     HIP_OK(hipMemcpyAsync(out.data(), s->dr_out, sizeof(double) * out.size(), hipMemcpyDeviceToHost, s->st));
     HIP_OK(hipStreamSynchronize(s->st));
-    double e[6] = {0, 0, 0, 0, 0, 0};
+    // e = max |x - x^|, max |x^|, the same for xbar, z, zbar
+    double e[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     for (int b = 0; b < nb; ++b) {
         for (int j = 0; j < 4; ++j) e[j] = std::max(e[j], out[(size_t)4 * b + j]);
         for (int j = 0; j < 2; ++j) e[4 + j] = std::max(e[4 + j], out[(size_t)4 * nb + 2 * b + j]);
+        for (int j = 0; j < 2; ++j) e[6 + j] = std::max(e[6 + j], out[(size_t)6 * nb + 2 * b + j]);
     }
     double drift = 0.0;
-    for (int j = 0; j < 6; j += 2) {
+    for (int j = 0; j < 8; j += 2) {
         const double rel = e[j] / std::max(1.0, e[j + 1]);
         if (rel == rel && rel > drift) drift = rel;
     }

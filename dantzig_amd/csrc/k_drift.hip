@@ -11,10 +11,13 @@
 // monitor reads 8e-14).  Right after a refactorisation the eta file is empty and the inverse is as
 // good as it gets, so the state can be recomputed from the data:
 //
-//      x^ = B^-1 b          xbar^ = B^-1 xbar0          z^_N = N^T (B^-T c_B) - c_N
+//      x^ = B^-1 b          xbar^ = B^-1 xbar0
+//      z^_N = N^T (B^-T c_B) - c_N          zbar^_N = N^T (B^-T cbar_B) - cbar_N
 //
-// (b, xbar0: the x and xbar the solve STARTED with, on the slack basis, where x = rhs).  The largest
-// relative difference  |x - x^|_inf / max(1, |x^|_inf)  (likewise xbar, z) is reported as
+// (b, xbar0: the x and xbar the solve STARTED with, on the slack basis, where x = rhs; cbar: -zbar0
+// on the starting nonbasics and 0 on the slacks -- the costs whose reduced costs zbar is, as z = -c
+// at the start).  The ratio test reads zbar as much as z, so it is measured too.  The largest
+// relative difference  |x - x^|_inf / max(1, |x^|_inf)  over x, xbar, z and zbar is reported as
 // dzg_result.state_drift and widens the near-tie tolerance: tau = max(tie_tol, 64 max_pivot_error,
 // 4 state_drift) -- a decision whose margin is inside what the carried state is known to be off by
 // is one the reference may take the other way.  The carried vectors are NOT replaced (the solve
@@ -22,7 +25,9 @@
 // reference's either).
 //
 // One GPU, dense matrix, solves that start from the slack basis.  B^-1 b is FTRAN's row function
-// with b as the column (fast_rows.h), N^T y the column-wise pricing pass with y as v.
+// with b as the column (fast_rows.h), N^T y the column-wise pricing pass with y as v (once with c,
+// once with cbar).  tests/test_gpu_state.py checks the result against the state the basis defines,
+// computed in long double.
 #include "common.h"
 #include "fast_rows.h"
 
@@ -137,15 +142,17 @@ __global__ __launch_bounds__(256) void k_drift_y_slack(const DzgDev d, const dou
     if (bc < 0) y[-1 - bc] = cdev[d.basis[p]];
 }
 
-// out[2 * block + {0,1}] = max |z - z^|, max |z^|  with  z^_k = -dzy_k - c[nonbasis[k]]  (dzy = -N^T y)
+// out[2 * block + {0,1}] = max |z - z^|, max |z^|  with  z^_k = -dzy_k - c[nonbasis[k]]  (dzy = -N^T y);
+// z: the carried d.z, or d.zbar with cbar as c
 __global__ __launch_bounds__(256) void k_drift_z(const DzgDev d, const double *__restrict__ cdev,
-                                                 const double *__restrict__ dzy, double *__restrict__ out)
+                                                 const double *__restrict__ dzy, const double *__restrict__ z,
+                                                 double *__restrict__ out)
 {
     __shared__ double s_m[4][2];
     double e0 = 0.0, e1 = 0.0;
     for (int kpos = blockIdx.x * blockDim.x + threadIdx.x; kpos < d.q; kpos += gridDim.x * blockDim.x) {
         const double zh = -dzy[kpos] - cdev[d.nonbasis[kpos]];
-        const double dd = fabs(d.z[kpos] - zh);
+        const double dd = fabs(z[kpos] - zh);
         e0 = dd > e0 ? dd : e0;
         e1 = fabs(zh) > e1 ? fabs(zh) : e1;
     }
@@ -170,10 +177,11 @@ __global__ __launch_bounds__(256) void k_drift_z(const DzgDev d, const double *_
 #define DR_BLOCKS 256
 
 // Enqueues the whole measurement.  scratch: agb, agx [m + 2 each], part [DR_CHUNKS x ldw], y [m + 2],
-// dzy [q], out [6 * DR_BLOCKS].  The host reads `out` and reduces (dzg_drift_reduce).
+// dzy [q], out [8 * DR_BLOCKS]: x and xbar, then z, then zbar.  The host reads `out` and reduces
+// (engine.hip measure_drift).
 void dzg_launch_drift(const DzgDev &d, const double *b0, const double *xb0, const double *cdev,
-                      double *agb, double *agx, double *part, double *y, double *dzy, double *out,
-                      int k_bound, hipStream_t st)
+                      const double *cbdev, double *agb, double *agx, double *part, double *y, double *dzy,
+                      double *out, int k_bound, hipStream_t st)
 {
     const int kb = k_bound > 0 ? k_bound : 1;
     hipLaunchKernelGGL(k_drift_gather, dim3((kb + 1 + 255) / 256), dim3(256), 0, st, d, b0, xb0, agb, agx);
@@ -181,12 +189,17 @@ void dzg_launch_drift(const DzgDev &d, const double *b0, const double *xb0, cons
         hipLaunchKernelGGL((k_drift_x<64>), dim3(DR_BLOCKS), dim3(256), 0, st, d, b0, xb0, agb, agx, out);
     else
         hipLaunchKernelGGL((k_drift_x<16>), dim3(DR_BLOCKS), dim3(256), 0, st, d, b0, xb0, agb, agx, out);
-    hipLaunchKernelGGL(k_drift_y_part, dim3((kb + 255) / 256, DR_CHUNKS), dim3(256), 0, st, d, cdev, part);
-    hipLaunchKernelGGL(k_drift_y_sum, dim3((d.m + 2 + 255) / 256), dim3(256), 0, st, d, cdev, part, y);
-    hipLaunchKernelGGL(k_drift_y_slack, dim3((d.m + 255) / 256), dim3(256), 0, st, d, cdev, y);
-    // dzy = -N^T y over every nonbasic position, column-wise (the sums' order does not matter here)
-    dzg_launch_price_raw(DZG_PRICE_TREE, d.m, d.lda, d.A, d.nbcode, d.q, y, dzy, st);
-    hipLaunchKernelGGL(k_drift_z, dim3(DR_BLOCKS), dim3(256), 0, st, d, cdev, dzy, out + 4 * DR_BLOCKS);
+    // z from c, then zbar from cbar: the same passes, one after the other on the same scratch
+    for (int pass = 0; pass < 2; ++pass) {
+        const double *cc = pass == 0 ? cdev : cbdev;
+        hipLaunchKernelGGL(k_drift_y_part, dim3((kb + 255) / 256, DR_CHUNKS), dim3(256), 0, st, d, cc, part);
+        hipLaunchKernelGGL(k_drift_y_sum, dim3((d.m + 2 + 255) / 256), dim3(256), 0, st, d, cc, part, y);
+        hipLaunchKernelGGL(k_drift_y_slack, dim3((d.m + 255) / 256), dim3(256), 0, st, d, cc, y);
+        // dzy = -N^T y over every nonbasic position, column-wise (the sums' order does not matter here)
+        dzg_launch_price_raw(DZG_PRICE_TREE, d.m, d.lda, d.A, d.nbcode, d.q, y, dzy, st);
+        hipLaunchKernelGGL(k_drift_z, dim3(DR_BLOCKS), dim3(256), 0, st, d, cc, dzy,
+                           (const double *)(pass == 0 ? d.z : d.zbar), out + (4 + 2 * pass) * DR_BLOCKS);
+    }
 }
 
 int dzg_drift_blocks(void) { return DR_BLOCKS; }

@@ -264,7 +264,7 @@ typedef struct {
                                 DZG_PRICE_ROWS=0, or hipMalloc could not hold a second copy of the
                                 matrix (the solve then prices column-wise throughout: same pivots,
                                 more bytes early in the solve)                                     */
-    double state_drift;      /* FAST: largest relative difference between the carried x_B / z_N and
+    double state_drift;      /* FAST: largest relative difference between the carried x, xbar, z, zbar and
                                 their recomputation from the fresh inverse, measured at the last
                                 refactorisation (0 if none): what the near-tie tolerance is widened
                                 by (tau = max(tie_tol, 64 max_pivot_error, 4 state_drift))         */

@@ -258,14 +258,20 @@ def stdform_from_dense(a: np.ndarray, b: np.ndarray, c: np.ndarray,
 
 
 def simplex_solve(sf: StdForm, max_iter: int = 1_000_000, log_cap: int | None = None,
-                  blocked: bool = False) -> SolveResult:
+                  blocked: bool = False, xbar=None, zbar=None) -> SolveResult:
+    """Simplex::solve from sf's state.  xbar / zbar: the perturbation vectors to start from (None:
+    ones, as Simplex::new sets them); with them and sf's basis, nonbasis, x, z the solve resumes
+    from any state a SolveResult (or tests/state_check.py) holds."""
     m, n = sf.m, sf.n
     q = n - m
     basis, nonbasis = _i64(sf.basis).copy(), _i64(sf.nonbasis).copy()
     x, z = _f64(sf.x).copy(), _f64(sf.z).copy()
     if len(x) == 0:
         x = np.zeros(0)
-    xbar, zbar = np.ones(max(m, 1))[:m].copy(), np.ones(max(q, 1))[:q].copy()
+    xbar = np.ones(max(m, 1))[:m].copy() if xbar is None else _f64(xbar).copy()
+    zbar = np.ones(max(q, 1))[:q].copy() if zbar is None else _f64(zbar).copy()
+    if len(xbar) != m or len(zbar) != q:
+        raise ValueError("simplex_solve: xbar needs m entries and zbar n - m")
     col_ptr, row_idx, val, c = _i64(sf.col_ptr), _i64(sf.row_idx), _f64(sf.val), _f64(sf.c)
     # keep 1-element backing stores alive for empty vectors
     keep = [np.zeros(1), np.zeros(1, dtype=np.int64)]

@@ -916,7 +916,7 @@ def test_near_tie_stop_is_resumable(core):
 
 def test_state_drift_is_measured_at_a_refactorisation(core):
     """the near-tie tolerance followed the INVERSE's consistency only (64 x
-    max_pivot_error, which a fresh inverse resets), while the carried x, xbar, z keep the rounding of
+    max_pivot_error, which a fresh inverse resets), while the carried x, xbar, z, zbar keep the rounding of
     every pivot so far.  At a refactorisation they are now recomputed from the fresh inverse
     (csrc/k_drift.hip: B^-1 b, B^-1 xbar0, N^T B^-T c_B - c_N), the largest relative difference is
     reported as state_drift and tau = max(tie_tol, 64 max_pivot_error, 4 state_drift).  512 x 1024
@@ -941,6 +941,15 @@ def test_state_drift_is_measured_at_a_refactorisation(core):
     assert mu_gap < 1e-6
     print(f"state_drift {r.state_drift:.3e}, near_ties {r.near_ties}, first {r.first_near_tie}, "
           f"FAST-vs-oracle mu gap {mu_gap:.3e}, min margin {r.min_margin:.3e}")
+    # ... and it is the drift of the carried x, xbar, z, zbar: D in long double from the same state at
+    # the last refactorisation, to within the GPU recomputation's own error (tests/state_check.py)
+    from tests import state_check as sc
+
+    with core.Solver(lp, numerics=core.FAST, poll_interval=50, refactor_interval=2000) as s:
+        assert s.run(6000) == "iter_limit"
+        r6, d6, floor = sc.drift_vs_exact(s, lp, np.asarray(a), int(fx["n_struct"]))
+    assert 0.0 < r6.state_drift < 1e-7 and r6.iterations == 6000
+    print(f"at pivot 6000: state_drift {r6.state_drift:.3e}, D {d6['D']:.3e}, floor {floor:.2e}")
 
 
 def test_row_wise_pricing_alone_follows_the_oracle_log(core, monkeypatch):
