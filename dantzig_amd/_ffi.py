@@ -39,7 +39,7 @@ EXPORTS = [
     "dzg_shard_comm_size", "dzg_solver_upload_columns", "dzg_debug_hold_cus", "dzg_debug_hold_wait",
     "dzg_core_solve_full_csc", "dzg_debug_live_lists", "dzg_debug_rl_listed",
     "dzg_debug_basis_inverse", "dzg_batch_solve", "dzg_model_solve_batch", "dzg_mip_opts_default",
-    "dzg_mip_solve",
+    "dzg_mip_solve", "dzg_mip_last_warm_stats",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -117,9 +117,14 @@ class StdForm(C.Structure):
 
 
 class MipOpts(C.Structure):
-    _fields_ = [("node_limit", C.c_int64), ("nodes_per_round", C.c_int32), ("reserved0", C.c_int32),
+    _fields_ = [("node_limit", C.c_int64), ("nodes_per_round", C.c_int32), ("warm_start", C.c_int32),
                 ("pivots_per_launch", C.c_int64), ("int_tol", C.c_double), ("abs_gap", C.c_double),
                 ("rel_gap", C.c_double)]
+
+
+class MipWarmStats(C.Structure):
+    _fields_ = [("nodes_warm", C.c_int64), ("nodes_restarted", C.c_int64),
+                ("warm_iterations", C.c_int64), ("restart_iterations", C.c_int64)]
 
 
 class MipNode(C.Structure):
@@ -200,6 +205,8 @@ def lib() -> C.CDLL:
         _lib.dzg_mip_opts_default.restype = None
         _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_mip_last_warm_stats.restype = None
+        _lib.dzg_mip_last_warm_stats.argtypes = [C.c_void_p]
         _lib.dzg_solver_upload_columns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                    C.c_int64]
     return _lib
@@ -243,10 +250,17 @@ def default_mip_opts(**kw) -> MipOpts:
     o = MipOpts()
     lib().dzg_mip_opts_default(C.byref(o))
     for k, v in kw.items():
-        if k == "reserved0" or not hasattr(o, k):
+        if not hasattr(o, k):
             raise TypeError(f"unknown MIP option {k!r}")
-        setattr(o, k, v)
+        setattr(o, k, int(v) if k == "warm_start" else v)
     return o
+
+
+def mip_last_warm_stats() -> MipWarmStats:
+    """What warm_start did in this thread's last dzg_mip_solve (zeros after a cold search)."""
+    out = MipWarmStats()
+    lib().dzg_mip_last_warm_stats(C.byref(out))
+    return out
 
 
 def require_gpu() -> None:

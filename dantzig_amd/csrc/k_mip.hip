@@ -17,6 +17,13 @@
 //     basis in LDS; the integrality test and the branching choice are mip_branch_choice
 //     (mip_internal.h), the host's own code.  The node's compact record is written; values stay on
 //     the device unless the node is integral.
+//   * warm starts (dzg_mip_opts.warm_start).  A node with a parent-state slot takes
+//     the parent's final basis, nonbasis and z from the slot pool on its first slice, sets both
+//     perturbation vectors to one and solves B x = b in LDS for its own right-hand side; the loop
+//     then runs from iteration 0 as for any node.  The attempt stands only if it ends OPTIMAL with
+//     every carried x and z >= -DZG_MIP_WARM_TOL; otherwise the workgroup marks the node restarted
+//     and re-queues it, and its next slice initialises it cold.  k_mip_save copies the final state
+//     of the nodes the host branches on from the round arena into their slots.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -49,7 +56,8 @@ struct SDesc {
 // One node of the round: its structure and its state offsets (elements).
 struct NDesc {
     long long m_off, q_off;
-    int sid, pad;
+    int sid;
+    int pslot; // the parent's slot in the state pool, -1: a cold node
 };
 
 struct MArgs {
@@ -69,7 +77,13 @@ struct MArgs {
     long long max_iter;
     double eps, int_tol;
     int ppl, mmax;
+    // the parent-state pool: per slot pool_si ints (basis, then nonbasis) and pool_sz doubles (z)
+    const int *pool_i;
+    const double *pool_z;
+    long long pool_si, pool_sz;
 };
+
+constexpr int kWarmRestarted = 2; // MipNodeRecord::warm
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restrict__ list,
@@ -97,7 +111,39 @@ __global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restri
     S.log_mu = nullptr;
     S.log_cap = 0;
     long long it = g.iter[id];
-    if (it < 0) { // first slice: the node's initial state (model.cpp build(), Simplex::new)
+    // a warm attempt until it is rejected; the rejection is recorded in the node's record
+    const bool warm_try = N.pslot >= 0 && g.rec[id].warm != kWarmRestarted;
+    if (it < 0 && warm_try) { // first slice of a warm node: the parent's final state, x = B^-1 b
+        const double *b0 = g.dpool + D.b0_off, *bnd = g.bnd + (long long)id * 2 * g.nint;
+        const int *ri = g.ipool + D.ri_off;
+        const int *pi = g.pool_i + N.pslot * g.pool_si;
+        const double *pz = g.pool_z + N.pslot * g.pool_sz;
+        for (int r = threadIdx.x; r < m; r += BLOCK) {
+            S.basis[r] = pi[r];
+            S.xbar[r] = 1.0;
+        }
+        for (int k = threadIdx.x; k < q; k += BLOCK) {
+            S.nonbasis[k] = pi[m + k];
+            S.z[k] = pz[k];
+            S.zbar[k] = 1.0;
+        }
+        __syncthreads(); // the gather reads the basis
+        if (m > 0) {
+            double *W = s_mem; // strict_steps' carve-up: W, dx[mmax], v[mmax], one int
+            int *s_flag = (int *)(s_mem + (long long)g.mmax * (g.mmax + 1) + 2 * g.mmax);
+            dzg_bs::gather<BLOCK>(W, m, S.A, S.basis, S.var_col, 0, S.basis[0], -1);
+            // column m: the node's right-hand side in place of an entering column (the same
+            // thread wrote the entry it overwrites)
+            for (int r = threadIdx.x; r < m; r += BLOCK) {
+                const int code = ri[r];
+                W[r * (m + 1) + m] = code < 0 ? b0[r] : ((code & 1) ? bnd[code] : -bnd[code]);
+            }
+            dzg_bs::lu_solve_lds<BLOCK>(W, m, s_flag);
+            for (int r = threadIdx.x; r < m; r += BLOCK) S.x[r] = W[r * (m + 1) + m];
+        }
+        it = 0;
+        __syncthreads();
+    } else if (it < 0) { // first slice: the node's initial state (model.cpp build(), Simplex::new)
         const double *b0 = g.dpool + D.b0_off, *bnd = g.bnd + (long long)id * 2 * g.nint;
         const int *ri = g.ipool + D.ri_off, *bs = g.ipool + D.bs_off, *nb = g.ipool + D.nb_off;
         const double *z0 = g.dpool + D.z0_off;
@@ -123,14 +169,47 @@ __global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restri
         }
         return;
     }
+    long long warm_it = 0;
+    int warm = 0;
+    if (warm_try) {
+        int reject = status != DZG_OPTIMAL;
+        if (!reject) { // the signs of the carried x and z themselves, bars ignored; NaN fails
+            int *s_bad = (int *)s_mem; // W is free after the loop
+            __syncthreads();
+            if (threadIdx.x == 0) *s_bad = 0;
+            __syncthreads();
+            int bad = 0;
+            for (int p = threadIdx.x; p < m; p += BLOCK) bad |= !(S.x[p] >= -DZG_MIP_WARM_TOL);
+            for (int k = threadIdx.x; k < q; k += BLOCK) bad |= !(S.z[k] >= -DZG_MIP_WARM_TOL);
+            if (bad) *s_bad = 1; // every writer stores the same value
+            __syncthreads();
+            reject = *s_bad;
+        }
+        if (reject) { // restart cold inside the round: the next slice sees the mark
+            if (threadIdx.x == 0) {
+                g.rec[id].warm = kWarmRestarted;
+                g.rec[id].warm_iterations = it;
+                g.iter[id] = -1;
+                next_list[atomicAdd(next_count, 1)] = id;
+            }
+            return;
+        }
+        warm = 1;
+        warm_it = it;
+    } else if (N.pslot >= 0) { // the cold run of a restarted node
+        warm = kWarmRestarted;
+        warm_it = g.rec[id].warm_iterations;
+        it += warm_it;
+    }
     MipNodeRecord rec;
     rec.status = status;
     rec.iterations = it;
+    rec.warm = warm;
+    rec.warm_iterations = warm_it;
     rec.branch = -1;
     rec.objective = 0.0;
     rec.value = 0.0;
     rec.integral = 0;
-    rec.pad = 0;
     if (status == DZG_OPTIMAL) {
         const double *c = g.dpool + D.c_off;
         const int *pv = g.ipool + D.pv_off, *nv = pv + g.nvars;
@@ -169,6 +248,24 @@ __global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restri
         g.rec[id] = rec;
         g.status[id] = status;
         g.iter[id] = it;
+    }
+}
+
+// The final basis, nonbasis and z of round node pairs[2 i] into pool slot pairs[2 i + 1].
+__global__ __launch_bounds__(64) void k_mip_save(MArgs g, const int *__restrict__ pairs,
+                                                 int *__restrict__ pool_i,
+                                                 double *__restrict__ pool_z)
+{
+    const int id = pairs[2 * blockIdx.x], slot = pairs[2 * blockIdx.x + 1];
+    const NDesc N = g.nd[id];
+    const SDesc D = g.sd[N.sid];
+    const int m = D.m, q = D.n - D.m;
+    int *pi = pool_i + slot * g.pool_si;
+    double *pz = pool_z + slot * g.pool_sz;
+    for (int r = threadIdx.x; r < m; r += 64) pi[r] = g.basis[N.m_off + r];
+    for (int k = threadIdx.x; k < q; k += 64) {
+        pi[m + k] = g.nonbasis[N.q_off + k];
+        pz[k] = g.z[N.q_off + k];
     }
 }
 
@@ -215,6 +312,18 @@ struct MipGpu {
     unsigned char *rdev = nullptr;
     size_t rcap = 0;
     std::vector<int> int_vars;
+    // warm starts: the parent-state pool.  Slot strides are fixed by the first structure (every
+    // structure of one model has the same q = 2 x its variables; m <= DZG_BATCH_MAX_ROWS).  Slots
+    // are handed out on the host (free list first); the arrays grow when a save needs more.
+    int pool_q = -1;
+    int *pool_i = nullptr;
+    double *pool_z = nullptr;
+    int pool_cap = 0, pool_used = 0;
+    std::vector<int> pool_free;
+    int *pairs_dev = nullptr;
+    int pairs_cap = 0;
+    MArgs last{};      // the last round's arguments: where k_mip_save finds the final states
+    int last_count = 0;
 };
 
 int mip_gpu_create(MipGpu **out, int device, int nvars, const std::vector<int> &int_vars)
@@ -244,12 +353,16 @@ void mip_gpu_destroy(MipGpu *g)
     if (!g) return;
     if (g->sdev) (void)hipFree(g->sdev);
     if (g->rdev) (void)hipFree(g->rdev);
+    if (g->pool_i) (void)hipFree(g->pool_i);
+    if (g->pool_z) (void)hipFree(g->pool_z);
+    if (g->pairs_dev) (void)hipFree(g->pairs_dev);
     if (g->st) (void)hipStreamDestroy(g->st);
     delete g;
 }
 
 int mip_gpu_add_structure(MipGpu *g, MipStructure &&s)
 {
+    if (g->pool_q < 0) g->pool_q = s.n - s.m;
     g->structs.push_back(std::move(s));
     g->dirty = true;
     return (int)g->structs.size() - 1;
@@ -316,8 +429,69 @@ static int upload_structures(MipGpu *g)
     return 0;
 }
 
-int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count, long long max_iter,
-                        double eps, int ppl, double int_tol, MipNodeRecord *rec, double *values)
+int mip_gpu_slot_alloc(MipGpu *g, int sid)
+{
+    const MipStructure &s = g->structs[(size_t)sid];
+    if (s.n - s.m != g->pool_q || s.m > DZG_BATCH_MAX_ROWS) return -1;
+    if (!g->pool_free.empty()) {
+        const int slot = g->pool_free.back();
+        g->pool_free.pop_back();
+        return slot;
+    }
+    return g->pool_used++;
+}
+
+void mip_gpu_slot_free(MipGpu *g, int slot) { g->pool_free.push_back(slot); }
+
+int mip_gpu_save_states(MipGpu *g, const int *pairs, int count)
+{
+    if (count <= 0) return 0;
+    MHIP(hipSetDevice(g->device));
+    const long long si = DZG_BATCH_MAX_ROWS + g->pool_q, sz = g->pool_q > 0 ? g->pool_q : 1;
+    for (int i = 0; i < count; ++i)
+        if (pairs[2 * i] < 0 || pairs[2 * i] >= g->last_count || pairs[2 * i + 1] < 0 ||
+            pairs[2 * i + 1] >= g->pool_used)
+            return dzg_set_error(DZG_E_ARG, "mip: a parent-state slot or round index out of range");
+    if (g->pool_used > g->pool_cap) { // grow: by half again, the live slots copied across
+        const int cap = std::max(64, g->pool_used + g->pool_used / 2);
+        int *ni = nullptr;
+        double *nz = nullptr;
+        MHIP(hipMalloc((void **)&ni, sizeof(int) * si * cap));
+        MHIP(hipMalloc((void **)&nz, sizeof(double) * sz * cap));
+        if (g->pool_cap > 0) {
+            MHIP(hipMemcpyAsync(ni, g->pool_i, sizeof(int) * si * g->pool_cap, hipMemcpyDeviceToDevice, g->st));
+            MHIP(hipMemcpyAsync(nz, g->pool_z, sizeof(double) * sz * g->pool_cap, hipMemcpyDeviceToDevice, g->st));
+            MHIP(hipStreamSynchronize(g->st));
+            MHIP(hipFree(g->pool_i));
+            MHIP(hipFree(g->pool_z));
+        }
+        g->pool_i = ni;
+        g->pool_z = nz;
+        g->pool_cap = cap;
+    }
+    if (count > g->pairs_cap) {
+        if (g->pairs_dev) {
+            MHIP(hipStreamSynchronize(g->st));
+            MHIP(hipFree(g->pairs_dev));
+            g->pairs_dev = nullptr;
+        }
+        const int cap = std::max(256, count + count / 2);
+        MHIP(hipMalloc((void **)&g->pairs_dev, sizeof(int) * 2 * cap));
+        g->pairs_cap = cap;
+    }
+    MHIP(hipMemcpyAsync(g->pairs_dev, pairs, sizeof(int) * 2 * count, hipMemcpyHostToDevice, g->st));
+    MArgs a = g->last;
+    a.pool_si = si;
+    a.pool_sz = sz;
+    hipLaunchKernelGGL(k_mip_save, dim3(count), dim3(64), 0, g->st, a, g->pairs_dev, g->pool_i, g->pool_z);
+    MHIP(hipGetLastError());
+    MHIP(hipStreamSynchronize(g->st)); // `pairs` is the caller's; the next round reads the slots
+    return 0;
+}
+
+int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const double *bnd, int count,
+                        long long max_iter, double eps, int ppl, double int_tol, MipNodeRecord *rec,
+                        double *values)
 {
     if (count <= 0) return 0;
     MHIP(hipSetDevice(g->device));
@@ -333,7 +507,9 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count,
     for (int i = 0; i < count; ++i) {
         const MipStructure &s = g->structs[(size_t)sid[i]];
         nd[(size_t)i].sid = sid[i];
-        nd[(size_t)i].pad = 0;
+        nd[(size_t)i].pslot = pslot ? pslot[i] : -1;
+        if (nd[(size_t)i].pslot >= g->pool_cap || (nd[(size_t)i].pslot >= 0 && s.n - s.m != g->pool_q))
+            return dzg_set_error(DZG_E_ARG, "mip: a node names a parent-state slot that was never saved");
         nd[(size_t)i].m_off = nm;
         nd[(size_t)i].q_off = nq;
         nm += s.m;
@@ -385,6 +561,7 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count,
     hipStream_t st = g->st;
     MHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
     MHIP(hipMemsetAsync(dev + o_iter, 0xff, sizeof(long long) * count, st)); // -1: not initialised
+    MHIP(hipMemsetAsync(dev + o_rec, 0, sizeof(MipNodeRecord) * count, st)); // warm = 0: no restart yet
 
     MArgs a = g->base;
     a.nd = (const NDesc *)(dev + o_nd);
@@ -404,6 +581,12 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count,
     a.eps = eps;
     a.int_tol = int_tol;
     a.ppl = ppl;
+    a.pool_i = g->pool_i;
+    a.pool_z = g->pool_z;
+    a.pool_si = DZG_BATCH_MAX_ROWS + g->pool_q;
+    a.pool_sz = g->pool_q > 0 ? g->pool_q : 1;
+    g->last = a;
+    g->last_count = count;
 
     int *cur = (int *)(dev + o_list), *nxt = (int *)(dev + o_list2);
     int *counts = (int *)(dev + o_counts);

@@ -12,6 +12,13 @@
 // processed in ascending node id: infeasible -> dropped; objective <= incumbent + tol -> pruned;
 // integral -> new incumbent; otherwise branched on the most fractional integer variable (down child
 // first).  A child whose bounds cross is never created.  Node ids follow creation order.
+//
+// Warm starts (opt-in, mip_opts.warm_start): a GPU node that is branched keeps its final basis,
+// nonbasis and z in a slot of a device pool while it has open children of its own structure (the
+// branch tightened a bound that was already finite); such a child names the slot in its round and
+// k_mip.hip starts it from there, restarting it cold if the attempt is not accepted.  A slot is
+// taken back once every child that names it is solved or pruned, so the pool never holds more
+// slots than there are open nodes.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -35,6 +42,7 @@ struct Node {
     double bound;              // the new bound of branch_var
     double parent_obj;         // +inf at the root
     std::vector<double> bnd;   // lb_k, ub_k per integer variable (+-inf: no bound)
+    int pslot = -1;            // warm starts: the parent's slot in the device state pool
 };
 
 struct OpenKey {
@@ -81,6 +89,8 @@ struct NodeModel {
 
 bool bad_tol(double t) { return !(t >= 0.0); } // NaN or negative
 
+thread_local dzg_mip_warm_stats g_warm_stats = {0, 0, 0, 0};
+
 } // namespace
 
 extern "C" void dzg_mip_opts_default(dzg_mip_opts *mo)
@@ -92,9 +102,15 @@ extern "C" void dzg_mip_opts_default(dzg_mip_opts *mo)
     mo->rel_gap = 0.0;
 }
 
+extern "C" void dzg_mip_last_warm_stats(dzg_mip_warm_stats *out)
+{
+    if (out) *out = g_warm_stats;
+}
+
 extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
                              const dzg_mip_opts *mip_opts, dzg_mip_result *res)
 {
+    g_warm_stats = dzg_mip_warm_stats{0, 0, 0, 0};
     // ---- argument checks, before any device work
     if (!model || !res) return dzg_set_error(DZG_E_ARG, "mip: model or res is NULL");
     if (model->nvars > 0 && !is_integer) return dzg_set_error(DZG_E_ARG, "mip: is_integer is NULL");
@@ -109,6 +125,8 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
     if (mo.node_limit < 0) return dzg_set_error(DZG_E_ARG, "mip: node_limit < 0");
     if (mo.nodes_per_round < 0) return dzg_set_error(DZG_E_ARG, "mip: nodes_per_round < 0");
     if (mo.pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "mip: pivots_per_launch < 0");
+    if (mo.warm_start != 0 && mo.warm_start != 1)
+        return dzg_set_error(DZG_E_ARG, "mip: warm_start must be 0 or 1");
     if (bad_tol(mo.int_tol) || bad_tol(mo.abs_gap) || bad_tol(mo.rel_gap))
         return dzg_set_error(DZG_E_ARG, "mip: int_tol, abs_gap and rel_gap must be >= 0 (not NaN)");
     if (res->log_cap < 0 || (res->log_cap > 0 && !res->log))
@@ -222,7 +240,13 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
     int final_status = -1;
 
     std::vector<int64_t> round;
-    std::vector<int> sid;
+    std::vector<int> sid, pslot, slot_refs, round_slot, save_pairs;
+    const bool warm_on = mo.warm_start == 1;
+    auto release = [&](Node &nd) { // one child fewer names its parent's slot
+        if (nd.pslot < 0) return;
+        if (--slot_refs[(size_t)nd.pslot] == 0) mip_gpu_slot_free(gpu, nd.pslot);
+        nd.pslot = -1;
+    };
     std::vector<double> bnd;
     std::vector<MipNodeRecord> rec;
     std::vector<double> vals;
@@ -234,6 +258,7 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
             if (has_inc && key.bound <= inc + tol()) {
                 open.erase(open.begin());
                 res->nodes_pruned++;
+                release(nodes[(size_t)key.id]);
                 continue;
             }
             if (res->nodes_solved + (int64_t)round.size() >= node_limit) break;
@@ -252,14 +277,19 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
         // ---- GPU nodes in one call, the others through dzg_model_solve
         std::vector<int> gpu_idx;
         sid.clear();
+        pslot.clear();
         bnd.clear();
+        round_slot.assign((size_t)cnt, -1); // round index -> index in the GPU call
+        save_pairs.clear();
         for (int i = 0; i < cnt; ++i) {
             const Node &nd = nodes[(size_t)round[(size_t)i]];
             NodeModel nm(model, ints, nd.bnd);
             const StructInfo info = structure_of(nd.bnd, &nm.md);
             if (info.gpu_id >= 0) {
+                round_slot[(size_t)i] = (int)gpu_idx.size();
                 gpu_idx.push_back(i);
                 sid.push_back(info.gpu_id);
+                pslot.push_back(nd.pslot);
                 bnd.insert(bnd.end(), nd.bnd.begin(), nd.bnd.end());
                 continue;
             }
@@ -284,8 +314,9 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
             const int g = (int)gpu_idx.size();
             std::vector<MipNodeRecord> grec((size_t)g);
             std::vector<double> gvals((size_t)g * nvars + 1, 0.0);
-            const int rc = mip_gpu_solve_round(gpu, sid.data(), bnd.data(), g, max_iter, eps, ppl,
-                                               mo.int_tol, grec.data(), gvals.data());
+            const int rc = mip_gpu_solve_round(gpu, sid.data(), warm_on ? pslot.data() : nullptr,
+                                               bnd.data(), g, max_iter, eps, ppl, mo.int_tol,
+                                               grec.data(), gvals.data());
             if (rc < 0) return rc;
             for (int j = 0; j < g; ++j) {
                 const int i = gpu_idx[(size_t)j];
@@ -296,11 +327,20 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
             res->nodes_batched += g;
         }
         res->nodes_solved += cnt;
+        for (int i = 0; i < cnt; ++i) release(nodes[(size_t)round[(size_t)i]]);
         // ---- process in ascending node id
         for (int i = 0; i < cnt && final_status < 0; ++i) {
             const int64_t id = round[(size_t)i];
             const MipNodeRecord &r = rec[(size_t)i];
             res->lp_iterations += r.iterations;
+            if (r.warm) {
+                g_warm_stats.nodes_warm++;
+                g_warm_stats.warm_iterations += r.warm_iterations;
+                if (r.warm == 2) {
+                    g_warm_stats.nodes_restarted++;
+                    g_warm_stats.restart_iterations += r.iterations - r.warm_iterations;
+                }
+            }
             if (res->log_count < res->log_cap) {
                 const Node &nd = nodes[(size_t)id];
                 dzg_mip_node &e = res->log[res->log_count++];
@@ -340,8 +380,11 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
             }
             const int k = r.branch;
             const double fl = std::floor(r.value);
+            int my_slot = -1; // this node's state slot, taken when its first warm child is made
             for (int dir = -1; dir <= 1; dir += 2) {
                 std::vector<double> cb = nodes[(size_t)id].bnd;
+                // the child keeps this node's structure iff the bound it tightens is finite already
+                const bool same_structure = !std::isinf(cb[(size_t)2 * k + (dir < 0 ? 1 : 0)]);
                 double nb;
                 if (dir < 0) {
                     nb = std::min(cb[(size_t)2 * k + 1], fl);
@@ -362,11 +405,30 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
                 child.bound = nb;
                 child.parent_obj = r.objective;
                 child.bnd = std::move(cb);
+                if (warm_on && same_structure && round_slot[(size_t)i] >= 0) {
+                    if (my_slot < 0) {
+                        my_slot = mip_gpu_slot_alloc(gpu, sid[(size_t)round_slot[(size_t)i]]);
+                        if (my_slot >= 0) {
+                            if ((size_t)my_slot >= slot_refs.size()) slot_refs.resize((size_t)my_slot + 1, 0);
+                            slot_refs[(size_t)my_slot] = 0;
+                            save_pairs.push_back(round_slot[(size_t)i]);
+                            save_pairs.push_back(my_slot);
+                        }
+                    }
+                    if (my_slot >= 0) {
+                        child.pslot = my_slot;
+                        slot_refs[(size_t)my_slot]++;
+                    }
+                }
                 open.insert({child.parent_obj, child.id});
                 nodes.push_back(std::move(child));
             }
         }
         if (final_status >= 0) break;
+        if (!save_pairs.empty()) {
+            const int rc = mip_gpu_save_states(gpu, save_pairs.data(), (int)save_pairs.size() / 2);
+            if (rc < 0) return rc;
+        }
     }
     if (final_status < 0) final_status = has_inc ? DZG_OPTIMAL : DZG_INFEASIBLE;
     res->status = final_status;

@@ -52,7 +52,8 @@ struct MipNodeRecord {
     double objective;  // constant + sum c[basis[p]] x[p], basis-position order
     double value;      // the branching variable's value
     int integral;
-    int pad;
+    int warm;                  // 0: cold; 1: warm attempt accepted; 2: rejected and restarted cold
+    long long warm_iterations; // the warm attempt's pivots (iterations holds both runs' sum)
 };
 
 struct MipGpu; // device arenas, reused across rounds
@@ -62,9 +63,19 @@ void mip_gpu_destroy(MipGpu *g);
 // Registers a structure (uploaded before the next round); returns its id.
 int mip_gpu_add_structure(MipGpu *g, MipStructure &&s);
 // Solves `count` node LPs: node i uses structure sid[i] and bounds bnd[i * 2 * nint ...].
+// pslot (NULL: every node cold): node i's parent-state slot, -1 for a cold node; a node with a
+// slot is warm-started from it and restarted cold if the attempt is not accepted.
 // rec[i] is filled for every node; values[i * nvars ...] for the integral OPTIMAL ones only.
-int mip_gpu_solve_round(MipGpu *g, const int *sid, const double *bnd, int count, long long max_iter,
-                        double eps, int ppl, double int_tol, MipNodeRecord *rec, double *values);
+int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const double *bnd, int count,
+                        long long max_iter, double eps, int ppl, double int_tol, MipNodeRecord *rec,
+                        double *values);
+// The parent-state pool (warm starts).  A slot holds the final basis, nonbasis and z of one node of
+// structure sid; alloc returns -1 if that structure cannot use the pool.  Slots are handed out and
+// taken back on the host; save_states copies the final states of nodes of the last round into
+// their slots: pairs = {index in that round, slot} x count.
+int mip_gpu_slot_alloc(MipGpu *g, int sid);
+void mip_gpu_slot_free(MipGpu *g, int slot);
+int mip_gpu_save_states(MipGpu *g, const int *pairs, int count);
 
 // The integrality test and the branching rule, shared by the host (sequential route) and the
 // device epilogue so that both take the same decision on the same values.

@@ -46,7 +46,9 @@ def set_options(**opts) -> None:
 
 def set_mip_options(**opts) -> None:
     """Branch-and-bound knobs for subsequent solve_mip() calls (fields of dzg_mip_opts: node_limit,
-    nodes_per_round, pivots_per_launch, int_tol, abs_gap, rel_gap)."""
+    nodes_per_round, pivots_per_launch, int_tol, abs_gap, rel_gap, and warm_start: True starts a
+    child's node LP from its parent's final basis where the two share a standard form, see
+    dzg_mip_solve)."""
     _ffi.default_mip_opts(**opts)  # validates names
     _mip_options.clear()
     _mip_options.update(opts)
@@ -156,10 +158,12 @@ class PyInequality:
 class MipInfo:
     """What the branch and bound of solve_mip() did (core sense: maximised).  `log` is the node
     log, a list of dzg_mip_node tuples (id, parent, branch_var, direction, bound, status,
-    iterations, objective) when solve_mip(..., node_log=N) asked for one."""
+    iterations, objective) when solve_mip(..., node_log=N) asked for one.  nodes_warm counts the
+    node LPs started from their parent's basis (warm_start=True), nodes_restarted those of them
+    that were discarded and solved again cold."""
     __slots__ = ("status", "nodes", "rounds", "lp_iterations", "best_bound", "gap", "objective",
                  "nodes_batched", "nodes_sequential", "nodes_pruned", "nodes_dropped",
-                 "incumbent_node", "failed_node", "log")
+                 "incumbent_node", "failed_node", "log", "nodes_warm", "nodes_restarted")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -297,6 +301,9 @@ def _mip_call(arrays: dict, is_integer, node_log: int = 0, **mip_opts):
     rc = _ffi.lib().dzg_mip_solve(C.byref(md), _ffi.ptr(is_int), C.byref(opts), C.byref(mo),
                                   C.byref(res))
     _ffi.check(rc, "dzg_mip_solve")
+    stats = _ffi.mip_last_warm_stats()
+    res.warm_stats = (int(stats.nodes_warm), int(stats.nodes_restarted), int(stats.warm_iterations),
+                      int(stats.restart_iterations))
     entries = [(e.id, e.parent, e.branch_var, e.direction, e.bound, e.status, e.iterations,
                 e.objective) for e in log[:res.log_count]]
     return res, values, entries
@@ -312,7 +319,7 @@ def _mip_outcome(res, values, order, entries, where: str = "", stacklevel: int =
                    nodes_batched=int(res.nodes_batched), nodes_sequential=int(res.nodes_sequential),
                    nodes_pruned=int(res.nodes_pruned), nodes_dropped=int(res.nodes_dropped),
                    incumbent_node=int(res.incumbent_node), failed_node=int(res.failed_node),
-                   log=entries)
+                   log=entries, nodes_warm=res.warm_stats[0], nodes_restarted=res.warm_stats[1])
     if rc == _ffi.INFEASIBLE:
         return InfeasibleError("The model is infeasible (no integral point)" + where)
     if rc == _ffi.UNBOUNDED and res.failed_node == 0:

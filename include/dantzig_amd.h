@@ -384,11 +384,12 @@ int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
  * "default" (node_limit 100000, nodes_per_round 1024, pivots_per_launch 16) while the tolerances are
- * taken as given (0 = exact).  Negative counts or tolerances and NaN tolerances are DZG_E_ARG. */
+ * taken as given (0 = exact).  Negative counts or tolerances and NaN tolerances are DZG_E_ARG, and so
+ * is a warm_start other than 0 or 1. */
 typedef struct {
     int64_t node_limit;        /* node LPs solved at most, then DZG_NODE_LIMIT; 0 = 100000        */
     int32_t nodes_per_round;   /* open nodes solved together per round; 0 = 1024                  */
-    int32_t reserved0;
+    int32_t warm_start;        /* 0 = off; 1 = warm-start children from the parent's basis (below) */
     int64_t pivots_per_launch; /* as in dzg_batch_solve; 0 = 16                                   */
     double int_tol;            /* v is integral if |v - rint(v)| <= int_tol (default 1e-6)        */
     double abs_gap;            /* prune when objective <= incumbent + max(abs_gap, rel_gap*|inc|) */
@@ -424,6 +425,18 @@ typedef struct {
     int64_t log_cap, log_count;
 } dzg_mip_result;
 
+/* A warm-started node LP is accepted only if it ends OPTIMAL with every carried x and z at or above
+ * -DZG_MIP_WARM_TOL (the default abs_gap); otherwise the node is solved again from the slack basis. */
+#define DZG_MIP_WARM_TOL 1e-9
+
+/* What warm_start did in the calling thread's last dzg_mip_solve (all zero after a cold search). */
+typedef struct {
+    int64_t nodes_warm;         /* node LPs started from their parent's basis (attempts)          */
+    int64_t nodes_restarted;    /* of those, the attempts discarded and solved again cold          */
+    int64_t warm_iterations;    /* pivots of the warm attempts, kept or discarded                  */
+    int64_t restart_iterations; /* pivots of the cold runs of the restarted nodes                  */
+} dzg_mip_warm_stats;
+
 void dzg_mip_opts_default(dzg_mip_opts *mo);
 /* Maximises model's objective with is_integer[u] != 0 marking integer variables.  Every node LP is
  * the model with the integer variables' bounds replaced by the node's, solved exactly as
@@ -432,9 +445,21 @@ void dzg_mip_opts_default(dzg_mip_opts *mo);
  * The search (best bound first, most fractional branching, incumbent updated between rounds) is
  * deterministic for a given nodes_per_round.  opts / mip_opts NULL: defaults.  FAST numerics is
  * DZG_E_ARG, and so is a bound of an integer variable that is flagged (has_lb / has_ub) but not
- * finite: the search keys nodes on which integer bounds are finite.  Returns res->status (>= 0) or a negative code. */
+ * finite: the search keys nodes on which integer bounds are finite.  Returns res->status (>= 0) or a negative code.
+ *
+ * mip_opts->warm_start = 1 (opt-in; the above holds bit for bit with 0) relaxes "node LP =
+ * dzg_model_solve of the node model" for speed: a child solved by k_mip.hip whose parent was solved
+ * there too, with the same set of finite integer bounds (a branch that adds no bound row), starts
+ * from the parent's final basis, nonbasis and carried z, with x = B^-1 b for its own right-hand side
+ * and both perturbation vectors at one, instead of from the slack basis.  The attempt is kept only
+ * if it ends OPTIMAL and passes the DZG_MIP_WARM_TOL sign check; any other end restarts the node cold
+ * in the same round, and status, objective, values and branching are then the cold run's.  A node's
+ * logged iterations are the pivots of both runs.  The tree may differ from the cold tree (another
+ * optimal vertex, last bits of an objective); the optimum found is the same.  Still independent of
+ * pivots_per_launch and deterministic for a given nodes_per_round. */
 int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
                   const dzg_mip_opts *mip_opts, dzg_mip_result *res);
+void dzg_mip_last_warm_stats(dzg_mip_warm_stats *out);
 
 /* Host-only: the standard-form builder alone (Simplex::new, src/simplex.rs:123-224).
  * Two-call protocol: first call with out->a == NULL fills m, n, n_struct and lda;

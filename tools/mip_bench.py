@@ -15,6 +15,15 @@ speed-up is taken against `oracle16_lp_s`.  `equal` says whether the GPU's statu
 objective and values equal the baseline's bit for bit.
 
     python tools/mip_bench.py [--models 4] [--node-limit 5000] [--out profiles/mip_bench.jsonl]
+
+--warm measures the warm-started search (dzg_mip_opts.warm_start = 1) instead: per model, after a
+warm-up solve of each kind, the cold and the warm GPU search are run alternately `--repeats` times
+(3); the minimum of each is reported with its spread (max - min).  The CPU baseline is the warm
+reference search (tests/mip_warm_reference.py) with its node LPs on 16 oracle threads; `equal`
+says whether the warm GPU search equals it bit for bit (status, nodes, rounds, pivots, objective,
+values, warm counters).  One JSON line per model to profiles/mip_bench_warm.jsonl.
+
+    python tools/mip_bench.py --warm [--models 4] [--node-limit 5000] [--repeats 3]
 """
 from __future__ import annotations
 
@@ -32,6 +41,7 @@ sys.path.insert(0, ROOT)
 
 from dantzig_amd import rust as rs  # noqa: E402
 from tests import mip_reference as mr  # noqa: E402
+from tests import mip_warm_reference as mw  # noqa: E402
 
 
 def knapsack(seed: int):
@@ -66,20 +76,76 @@ def gap(seed: int):
              "constraints": cons}, [1] * nv)
 
 
+def warm_line(family, seed, md, flags, mo, repeats, pool):
+    arrays = mr.c_arrays(md)
+    for w in (0, 1):  # warm-up: device, code objects, allocator
+        rs._mip_call(arrays, flags, 0, warm_start=w, **mo)
+    times = {0: [], 1: []}
+    got = {}
+    for _ in range(repeats):
+        for w in (0, 1):
+            t0 = time.perf_counter()
+            got[w] = rs._mip_call(arrays, flags, 0, warm_start=w, **mo)
+            times[w].append(time.perf_counter() - t0)
+    (cold, _, _), (res, values, _) = got[0], got[1]
+    cold_s, warm_s = min(times[0]), min(times[1])
+    line = dict(family=family, seed=seed, nvars=len(flags), status=int(res.status),
+                objective=res.objective if res.has_incumbent else None,
+                cold_status=int(cold.status), cold_objective=cold.objective if cold.has_incumbent else None,
+                nodes_cold=int(cold.nodes_solved), nodes_warm_search=int(res.nodes_solved),
+                rounds_cold=int(cold.rounds), rounds_warm=int(res.rounds),
+                lp_pivots_cold=int(cold.lp_iterations), lp_pivots_warm=int(res.lp_iterations),
+                warm_attempts=res.warm_stats[0], restarts=res.warm_stats[1],
+                warm_pivots=res.warm_stats[2], restart_pivots=res.warm_stats[3],
+                gpu_cold_s=cold_s, gpu_cold_spread_s=max(times[0]) - cold_s,
+                gpu_warm_s=warm_s, gpu_warm_spread_s=max(times[1]) - warm_s,
+                gpu_warm_over_cold=cold_s / warm_s, repeats=repeats)
+    lp_s = [0.0]
+
+    def timed_map(fn, items):
+        t = time.perf_counter()
+        out = list(pool.map(fn, items))
+        lp_s[0] += time.perf_counter() - t
+        return out
+
+    t0 = time.perf_counter()
+    ref = mw.branch_and_bound_warm(md, flags, map_fn=timed_map, **mo)
+    cpu_s = time.perf_counter() - t0
+    want = {"optimal": 0, "infeasible": 2, "node_limit": 8}.get(ref["status"], ref["status"])
+    same_inc = (ref["objective"] is None and not res.has_incumbent) or (
+        ref["objective"] is not None and bool(res.has_incumbent) and ref["objective"] == res.objective
+        and np.array_equal(ref["values"], values[:len(flags)]))
+    same_counts = (ref["nodes_solved"], ref["rounds"], ref["lp_iterations"]) == (
+        res.nodes_solved, res.rounds, res.lp_iterations) and res.warm_stats == (
+        ref["nodes_warm"], ref["nodes_restarted"], ref["warm_iterations"], ref["restart_iterations"])
+    line.update(oracle16_warm_lp_s=lp_s[0], oracle16_warm_total_s=cpu_s, speedup_warm=lp_s[0] / warm_s,
+                equal=bool(want == res.status and same_counts and same_inc))
+    return line
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", type=int, default=4)
     ap.add_argument("--node-limit", type=int, default=5000)
     ap.add_argument("--nodes-per-round", type=int, default=1024)
     ap.add_argument("--no-oracle", action="store_true")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mip_bench.jsonl"))
+    ap.add_argument("--warm", action="store_true", help="cold vs warm-started GPU search, see above")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "mip_bench_warm.jsonl" if args.warm else "mip_bench.jsonl")
     pool = ThreadPoolExecutor(max_workers=16)
     lines = []
     for family, maker in (("knap", knapsack), ("gap", gap)):
         for k in range(args.models):
             md, flags = maker(1000 + k)
             mo = dict(node_limit=args.node_limit, nodes_per_round=args.nodes_per_round)
+            if args.warm:
+                line = warm_line(family, 1000 + k, md, flags, mo, args.repeats, pool)
+                print(json.dumps(line), flush=True)
+                lines.append(line)
+                continue
             rs._mip_call(mr.c_arrays(md), flags, 0, node_limit=1)  # warm-up: device, code objects
             arrays = mr.c_arrays(md)
             t0 = time.perf_counter()
