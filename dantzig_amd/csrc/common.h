@@ -118,6 +118,34 @@ struct DzgCand2 {
 
 #ifdef __HIPCC__
 
+// Diagnostic (DZG_CHAIN_DEBUG=1): lane 0 of workgroup 0 accumulates the 100 MHz real-time clock
+// between phase boundaries; dbg[16 * kernel_and_kind + stage] += ticks, dbg[.. + 15] += 1.
+// Slots: 0 / 1 k_chain_pre primal / dual, 2 / 3 k_chain_post primal / dual, 4 k_price_rows_small.
+#define DZG_STAMP_SLOTS 5
+struct ChainStamps {
+    unsigned long long *dbg;
+    unsigned long long last;
+    int stage;
+    __device__ __forceinline__ void start(unsigned long long *p)
+    {
+        dbg = (blockIdx.x == 0 && threadIdx.x == 0) ? p : nullptr;
+        stage = 0;
+        if (dbg) last = __builtin_amdgcn_s_memrealtime();
+    }
+    __device__ __forceinline__ void mark(int slot)
+    {
+        if (!dbg) return;
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        dbg[16 * slot + stage] += now - last;
+        last = now;
+        ++stage;
+    }
+    __device__ __forceinline__ void done(int slot)
+    {
+        if (dbg) dbg[16 * slot + 15] += 1;
+    }
+};
+
 __device__ __forceinline__ DzgCand2 dzg_cand2_none()
 {
     DzgCand2 c;
@@ -534,7 +562,7 @@ int dzg_run_second_pivot(int64_t len, double mu, const double *y, const double *
 // k_price.hip
 void dzg_launch_price(const DzgDev &d, int kernel, hipStream_t st);
 void dzg_launch_price_fast(const DzgDev &d, int kernel, hipStream_t st, int need_kind = -1,
-                           int skip_finish = 0, int small = 0);
+                           int skip_finish = 0, int small = 0, unsigned long long *dbg = nullptr);
 int dzg_price_small(const DzgDev &d, int kernel);       // 1: the batch runs the fused small-k row pass
 int dzg_price_small_partials(const DzgDev &d);          // its workgroups (= ratio partials)
 int dzg_price_rows_certain(const DzgDev &d, int kernel); // the host's bounds on k prove the row-wise pass

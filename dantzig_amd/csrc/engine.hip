@@ -260,11 +260,12 @@ static bool partitioned(const dzg_solver *s);
 // DZG_CHAIN_DEBUG=1: where workgroup 0 of the chain kernels spent its time (stderr, at destroy)
 static void chain_debug_report(dzg_solver *s)
 {
-    unsigned long long h[64];
+    unsigned long long h[16 * DZG_STAMP_SLOTS];
     if (hipMemcpy(h, s->chain_dbg, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
-    static const char *names[4] = {"k_chain_pre  primal", "k_chain_pre  dual  ", "k_chain_post primal",
-                                   "k_chain_post dual  "};
-    for (int slot = 0; slot < 4; ++slot) {
+    // (the pricing kernel's stages: control block | row list | rows | finish)
+    static const char *names[DZG_STAMP_SLOTS] = {"k_chain_pre  primal", "k_chain_pre  dual  ", "k_chain_post primal",
+                                                 "k_chain_post dual  ", "k_price_rows_small "};
+    for (int slot = 0; slot < DZG_STAMP_SLOTS; ++slot) {
         const double n = (double)h[16 * slot + 15];
         if (n <= 0) continue;
         std::fprintf(stderr, "[chain] %s x%-8.0f us per stage:", names[slot], n);
@@ -734,8 +735,8 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
                 }
                 if (const char *dbg = std::getenv("DZG_CHAIN_DEBUG")) {
                     if (dbg[0] == '1') {
-                        TRY(dev_alloc(s, &s->chain_dbg, (size_t)64));
-                        HIP_OK(hipMemsetAsync(s->chain_dbg, 0, sizeof(unsigned long long) * 64, s->st));
+                        TRY(dev_alloc(s, &s->chain_dbg, (size_t)16 * DZG_STAMP_SLOTS));
+                        HIP_OK(hipMemsetAsync(s->chain_dbg, 0, sizeof(unsigned long long) * 16 * DZG_STAMP_SLOTS, s->st));
                     }
                 }
                 if (const char *nf = std::getenv("DZG_CHAIN_NO_FOLD")) s->chain_fold = nf[0] != '1';
@@ -911,7 +912,7 @@ static void enqueue_chain_iteration(dzg_solver *s, int slot)
     const int small = dzg_price_small(d, pk);
     const int fold = !small && s->chain_fold && dzg_price_rows_certain(d, pk);
     pf.begin(DZG_K_PRICE);
-    dzg_launch_price_fast(d, pk, st, -1, fold, small);
+    dzg_launch_price_fast(d, pk, st, -1, fold, small, small ? s->chain_dbg : nullptr);
     pf.end(DZG_K_PRICE);
     pf.begin(DZG_K_UPDATE);
     dzg_launch_chain_post(d, s->chain_grid, s->chain_bar, s->chain_dbg, 0,

@@ -153,23 +153,36 @@ __device__ __forceinline__ double fast_gemv_row(int i, int m, int k2, int neta,
     return fast_gemv_row_tail<LPR>(acc, i, m, neta, U, ldu, beta, sub);
 }
 
-// v_r = (row p of Binv)_r = base - sum_t U_t[p] W_t[r]  (BTRAN): the eta file's share, sixteen etas
-// per trip to memory; an eta beyond neta contributes fma(0, 0, acc) = acc exactly.
-__device__ __forceinline__ double fast_btran_eta(int neta, const double *__restrict__ U, long long ldu,
-                                                 const double *__restrict__ W, long long ldw, int p,
-                                                 int r)
+// v_r = (row p of Binv)_r = base - sum_t U_t[p] W_t[r]  (BTRAN): the eta file's share with every
+// load in ONE trip (k_chain_pre; up to four dependent trips when sixteen etas were fetched per turn):
+// (load) all of row r's entries of the pending eta rows leave at once -- W[t][r] does not depend on
+// p -- while one wave fetches the 64 values U[t][p] (zero beyond neta) into LDS, one load per lane;
+// (fma) acc = fma(U[t][p], W[t][r], acc) from acc = 0, t ascending, in blocks of sixteen while the
+// block starts below neta; an eta beyond neta contributes fma(0, 0, acc) = acc exactly.
+__device__ __forceinline__ void fast_btran_eta_load(double (&w)[R_], int neta,
+                                                    const double *__restrict__ W, long long ldw, int r)
+{
+#pragma unroll
+    for (int t0 = 0; t0 < R_; t0 += 16) {
+        if (t0 < neta) { // (block-uniform)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) { // (a slot beyond neta re-reads the last eta's entry: no branch)
+                const int t = t0 + j < neta ? t0 + j : neta - 1;
+                w[t0 + j] = W[(long long)t * ldw + r];
+            }
+        }
+    }
+}
+
+__device__ __forceinline__ double fast_btran_eta_fma(const double (&w)[R_], int neta, const double *s_up)
 {
     double acc = 0.0;
-    for (int t0 = 0; t0 < neta; t0 += 16) {
-        double u[16], w[16];
 #pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const bool ok = t0 + j < neta;
-            u[j] = ok ? U[(long long)(t0 + j) * ldu + p] : 0.0;
-            w[j] = ok ? W[(long long)(t0 + j) * ldw + r] : 0.0;
+    for (int t0 = 0; t0 < R_; t0 += 16) {
+        if (t0 < neta) {
+#pragma unroll
+            for (int j = 0; j < 16; ++j) acc = fma(s_up[t0 + j], t0 + j < neta ? w[t0 + j] : 0.0, acc);
         }
-#pragma unroll
-        for (int j = 0; j < 16; ++j) acc = fma(u[j], w[j], acc);
     }
     return acc;
 }

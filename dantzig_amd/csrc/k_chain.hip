@@ -48,31 +48,7 @@
 
 #include "chain_barrier.h"
 
-// Diagnostic (DZG_CHAIN_DEBUG=1): lane 0 of workgroup 0 accumulates the 100 MHz real-time clock
-// between phase boundaries; dbg[16 * kernel_and_kind + stage] += ticks, dbg[.. + 15] += 1.
-struct ChainStamps {
-    unsigned long long *dbg;
-    unsigned long long last;
-    int stage;
-    __device__ __forceinline__ void start(unsigned long long *p)
-    {
-        dbg = (blockIdx.x == 0 && threadIdx.x == 0) ? p : nullptr;
-        stage = 0;
-        if (dbg) last = __builtin_amdgcn_s_memrealtime();
-    }
-    __device__ __forceinline__ void mark(int slot)
-    {
-        if (!dbg) return;
-        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-        dbg[16 * slot + stage] += now - last;
-        last = now;
-        ++stage;
-    }
-    __device__ __forceinline__ void done(int slot)
-    {
-        if (dbg) dbg[16 * slot + 15] += 1;
-    }
-};
+// (the stage clocks of DZG_CHAIN_DEBUG=1: ChainStamps, common.h)
 
 // ---------------------------------------------------------------------------------
 // Work split.  Workgroup b owns rows [r0, r1) -- thread t the row r0 + t -- in FTRAN, BTRAN and the
@@ -116,6 +92,40 @@ __device__ __forceinline__ void chain_spec_load(ChainSpec &s, const double *__re
         s.k[j] = pk[lane + 64 * j];
         s.h[j] = ph[lane + 64 * j];
     }
+}
+__device__ __forceinline__ DzgCand2 chain_spec_reduce(const ChainSpec &s, int count, int lane);
+// the same for candidates that crossed a barrier of this launch (agent-scope loads): the four
+// slots of a lane leave together -- one trip, where a loop over i = lane, lane + 64, ... waits for
+// each turn's loads before it issues the next
+__device__ __forceinline__ void chain_spec_load_sc1(ChainSpec &s, const double *pr, const int *pk,
+                                                    const double *ph, int lane)
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        s.r[j] = ld_sc1(pr + lane + 64 * j);
+        s.k[j] = ld_sc1(pk + lane + 64 * j);
+        s.h[j] = ld_sc1(ph + lane + 64 * j);
+    }
+}
+// the workgroups' candidates of a barrier-crossing ratio test, reduced by wave 0 (candidates
+// i = lane, lane + 64, ... in ascending order, then the wave: the same order either way)
+__device__ __forceinline__ DzgCand2 chain_reduce_sc1(const double *pr, const int *pk, const double *ph,
+                                                     int n, int lane)
+{
+    if (n <= 256) {
+        ChainSpec sx;
+        chain_spec_load_sc1(sx, pr, pk, ph, lane);
+        return chain_spec_reduce(sx, n, lane);
+    }
+    DzgCand2 w = dzg_cand2_none();
+    for (int i = lane; i < n; i += 64) {
+        DzgCand2 o;
+        o.r = ld_sc1(pr + i);
+        o.k = ld_sc1(pk + i);
+        o.h = ld_sc1(ph + i);
+        w = dzg_better2(w, o);
+    }
+    return dzg_wave_best2(w);
 }
 __device__ __forceinline__ DzgCand2 chain_spec_reduce(const ChainSpec &s, int count, int lane)
 {
@@ -282,7 +292,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
                                                           const double *__restrict__ xrecv)
 {
     __shared__ double s_ag[CH_AGCAP];
-    __shared__ double s_beta[R_], s_dx[CH_THREADS];
+    __shared__ double s_beta[R_], s_dx[CH_THREADS], s_up[R_];
     __shared__ ChainSlots s_c;
     ChainStamps ts;
     ts.start(dbg);
@@ -402,15 +412,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         if (!chain_barrier(ctl, bar, gen)) return;
         ts.mark(slot); // 4: barrier
         if (wave == 0) {
-            DzgCand2 w = dzg_cand2_none();
-            for (int i = lane; i < nwg; i += 64) {
-                DzgCand2 o;
-                o.r = ld_sc1(d.rx_r + i);
-                o.k = ld_sc1(d.rx_k + i);
-                o.h = ld_sc1(d.rx_h + i);
-                w = dzg_better2(w, o);
-            }
-            w = dzg_wave_best2(w);
+            const DzgCand2 w = chain_reduce_sc1(d.rx_r, d.rx_k, d.rx_h, nwg, lane);
             if (lane == 0) chain_put(s_c, 0, w);
         }
         __syncthreads();
@@ -425,17 +427,32 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
     } else {
         p = ci.k;
     }
-    // ---- BTRAN: v = row p of Binv on this thread's row; one trip: nothing below waits for another load
+    // ---- BTRAN: v = row p of Binv on this thread's row; ONE trip: the leaving variable's code and
+    // values, the row of Binv0, U's 64 entries of row p (wave 0, through LDS) and every entry of the
+    // pending eta rows leave together, and nothing below waits for another load
     const int lcode = d.bcode[p];
+    double xp = 0.0, xbp = 0.0;
+    if (lead) { // (into registers first: a store to the control block between them would order the loads)
+        xp = d.x[p];
+        xbp = d.xbar[p];
+    }
+    double up = 0.0, base = 0.0, w[R_];
+    if (tid < R_ && tid < neta) up = d.U[(long long)tid * d.ldw + p];
     if (has_row) {
-        const double base = dslot_i >= 0 ? d.binv[(long long)p * d.ldb + dslot_i] : (lcode == -1 - row ? 1.0 : 0.0);
-        const double vr = base - fast_btran_eta(neta, d.U, d.ldw, d.W, d.ldw, p, row);
+        if (dslot_i >= 0) base = d.binv[(long long)p * d.ldb + dslot_i];
+        fast_btran_eta_load(w, neta, d.W, d.ldw, row);
+    }
+    if (tid < R_) s_up[tid] = up;
+    __syncthreads();
+    if (has_row) {
+        if (dslot_i < 0) base = lcode == -1 - row ? 1.0 : 0.0;
+        const double vr = base - fast_btran_eta_fma(w, neta, s_up);
         d.v[row] = vr;
         if (dslot_i >= 0 && d.vc) d.vc[dslot_i] = vr; // (compact copy: the row-wise pricing pass's coefficients)
     }
     if (lead) {
-        ctl->xp = d.x[p];
-        ctl->xbp = d.xbar[p];
+        ctl->xp = xp;
+        ctl->xbp = xbp;
         ctl->leave_code = lcode;
         if (gen != c.bar_gen) ctl->bar_gen = gen;
     }
@@ -619,15 +636,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
                 }
                 if (!chain_barrier(ctl, bar, gen)) return;
                 if (wave == 0) {
-                    DzgCand2 w = dzg_cand2_none();
-                    for (int i = lane; i < (int)gridDim.x; i += 64) {
-                        DzgCand2 o;
-                        o.r = ld_sc1(d.rz_r + i);
-                        o.k = ld_sc1(d.rz_k + i);
-                        o.h = ld_sc1(d.rz_h + i);
-                        w = dzg_better2(w, o);
-                    }
-                    w = dzg_wave_best2(w);
+                    const DzgCand2 w = chain_reduce_sc1(d.rz_r, d.rz_k, d.rz_h, (int)gridDim.x, lane);
                     if (lane == 0) chain_put(s_c, 0, w);
                 }
                 __syncthreads();

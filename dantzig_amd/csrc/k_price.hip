@@ -173,18 +173,18 @@ int dzg_price_rows_certain(const DzgDev &d, int kernel)
 // need_kind >= 0 (row-sharded ranks, dense, tree / row-wise kernels only): the pass runs only in an
 // iteration of that step kind
 void dzg_launch_price_fast(const DzgDev &d, int kernel, hipStream_t st, int need_kind, int skip_finish,
-                           int small)
+                           int small, unsigned long long *dbg)
 {
     if (small) { // (the caller asked dzg_price_small)
         // (k < 127 for the whole batch: at most eight row groups, one per wave)
         if (d.k_hint < 8 * DZG_PR_BATCH - 1)
             hipLaunchKernelGGL(k_price_rows_small<false>, dim3(dzg_price_small_partials(d)), dim3(512), 0, st,
-                               d.ctl, d.rows_T, d.At, d.ldt, d.col1 - d.col0, d.drow, d.bcode, d.vc, d.cpos, d.q,
-                               d.nbcode, d.v, d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h);
+                               d.ctl, d.rows_T, d.At, d.ldt, d.col1 - d.col0, d.drow, d.vc, d.cpos, d.q,
+                               d.nbcode, d.v, d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h, dbg);
         else
             hipLaunchKernelGGL(k_price_rows_small<true>, dim3(dzg_price_small_partials(d)), dim3(512), 0, st,
-                               d.ctl, d.rows_T, d.At, d.ldt, d.col1 - d.col0, d.drow, d.bcode, d.vc, d.cpos, d.q,
-                               d.nbcode, d.v, d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h);
+                               d.ctl, d.rows_T, d.At, d.ldt, d.col1 - d.col0, d.drow, d.vc, d.cpos, d.q,
+                               d.nbcode, d.v, d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h, dbg);
         return;
     }
     if (d.csc) {

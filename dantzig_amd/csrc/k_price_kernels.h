@@ -978,19 +978,29 @@ __global__ __launch_bounds__(256) void k_price_rows(
 // ---------------------------------------------------------------------------------
 // WIDE: the loads of a wave's four groups leave together (G > 8: k >= 128); otherwise one group
 // per wave and fewer registers (four workgroups per CU instead of two: config 5 has 1 024 tiles).
+// The control block is read as ONE snapshot (scalar loads that all leave before the first is waited
+// for; read field by field behind the early exits they sit on four cache lines and cost a trip
+// each), and the leaving variable's code comes with it (k_chain_pre publishes ctl->leave_code)
+// instead of a dependent load of bcode[leave_pos].
+// dbg != nullptr (DZG_CHAIN_DEBUG=1): the stage clocks of workgroup 0, slot 4 (ChainStamps):
+// control block | row list | rows | finish.
 #define PRS_TILE 64
 #define PRS_ROWS 512
+#define PRS_STAMP_SLOT 4
 template <bool WIDE>
 __global__ __launch_bounds__(512) void k_price_rows_small(
-    const DzgCtl *ctl, int rows_T, const double *__restrict__ At, long long ldt, int ncols,
-    const int *__restrict__ drow, const int *__restrict__ bcode, const double *__restrict__ vc,
+    const DzgCtl *__restrict__ ctl, int rows_T, const double *__restrict__ At, long long ldt, int ncols,
+    const int *__restrict__ drow, const double *__restrict__ vc,
     const int *__restrict__ cpos, int q, const int *__restrict__ nbcode, const double *__restrict__ v,
     double *__restrict__ dz, const double *__restrict__ z, const double *__restrict__ zbar,
-    double *__restrict__ rz_r, int *__restrict__ rz_k, double *__restrict__ rz_h)
+    double *__restrict__ rz_r, int *__restrict__ rz_k, double *__restrict__ rz_h,
+    unsigned long long *dbg)
 {
     __shared__ long long s_off[PRS_ROWS];
     __shared__ double s_coef[PRS_ROWS];
     __shared__ double s_part[PR_GMAX][PRS_TILE];
+    ChainStamps ts;
+    ts.start(dbg);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // first trip, side by side: the control block, this thread's unit-column position, this lane's
     // column and where it sits
@@ -1001,10 +1011,13 @@ __global__ __launch_bounds__(512) void k_price_rows_small(
     int pos = -1;
     if (wave == 0 && j < ncols) pos = cpos[j];
     const int status = ctl->status, k = ctl->ncompact, lp = ctl->leave_pos;
+    const int lcode_c = ctl->leave_code;
     const double mu = ctl->mu, tau = ctl->tau;
+    asm volatile("" ::"s"(status), "s"(k), "s"(lp), "s"(lcode_c), "s"(mu), "s"(tau)); // (one snapshot)
     if (status != DZG_RUNNING || k >= rows_T || k >= PRS_ROWS) return;
+    ts.mark(PRS_STAMP_SLOT); // 0: control block
     // second trip: the row list and its coefficients; z, zbar of this thread's positions
-    const int lcode = lp >= 0 ? bcode[lp] : 0; // < 0: a slack leaves, row -1 - lcode carries v = 1
+    const int lcode = lp >= 0 ? lcode_c : 0; // < 0: a slack leaves, row -1 - lcode carries v = 1
     if (tid < k) {
         s_off[tid] = (long long)drow[tid] * ldt;
         s_coef[tid] = vc[tid];
@@ -1027,6 +1040,7 @@ __global__ __launch_bounds__(512) void k_price_rows_small(
     int G = (k + 1 + PR_BATCH - 1) / PR_BATCH; // (as k_price_rows)
     G = G > PR_GMAX ? PR_GMAX : G;
     __syncthreads();
+    ts.mark(PRS_STAMP_SLOT); // 1: row list
     // third trip: the rows of this tile -- eight rows of each of the wave's (up to four) groups in
     // flight per lane, so that a pass of k + 1 <= 512 rows is two trips whatever G is; a group's
     // rows are still added in ascending order into the group's own accumulator
@@ -1078,6 +1092,7 @@ __global__ __launch_bounds__(512) void k_price_rows_small(
         }
     }
     __syncthreads();
+    ts.mark(PRS_STAMP_SLOT); // 2: rows
     DzgCand2 best = dzg_cand2_none();
     if (pos >= 0) { // (wave 0) the finishing launch's sum: the groups in order
         double sum = 0.0;
@@ -1102,6 +1117,8 @@ __global__ __launch_bounds__(512) void k_price_rows_small(
         }
     }
     price_publish(best, rz_r, rz_k, rz_h);
+    ts.mark(PRS_STAMP_SLOT); // 3: finish
+    ts.done(PRS_STAMP_SLOT);
 }
 
 __global__ __launch_bounds__(256) void k_price_rows_finish(
