@@ -47,7 +47,9 @@ __device__ __forceinline__ int ld_sc1(const int *p)
 // Fast path: unchanged -- one relaxed fetch_add per workgroup, one more by the last arrival of
 // each residue class, polls of one word; the bit is only looked at when the loop ends.
 // INVARIANT (do not break in an edit): everything that crosses a barrier is published by sc1
-// stores of the SAME lane that arrives (thread 0, after s_waitcnt(0)), and read with sc1 loads.
+// stores of the SAME lane that arrives (thread 0, after s_waitcnt(0)) -- or by a lane that waits for
+// its own stores (s_waitcnt(0)) before the workgroup barrier this function begins with, as the waves
+// that publish beta's wave sums do (k_chain.hip, chain_beta_published) -- and read with sc1 loads.
 __device__ __forceinline__ bool chain_barrier(DzgCtl *ctl, unsigned long long *bar,
                                               unsigned long long &gen)
 {

@@ -467,7 +467,10 @@ struct DzgDev {
     long long ldw;
     double *Wc;        // [DZG_RMAX][ldw] W gathered to compact coordinates (flush scratch)
     double *ag;        // [m] entering column gathered to compact coordinates
-    double *beta;      // [DZG_RMAX] W_t . a_j
+    double *beta;      // [DZG_RMAX] W_t . a_j (the seven launches)
+    double *beta_part; // [4 DZG_RMAX] the chain's beta as the four wave sums of fast_beta_dot, slot 4 t + w
+    int beta_split;    // the chain spreads the wave sums of eta t over four workgroups (default), 0: workgroup t
+                       // takes all four (DZG_CHAIN_BETA_SPLIT is the A/B switch)
     int *plist;        // [q] nonbasic positions holding structural variables (first nb_struct)
     int *pslot;        // [q] index into plist or -1
     int *pcode;        // [q] column code of the variable at plist[i] (the pricing waves' column list)

@@ -394,6 +394,8 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
         d.ftran_nt_k = kk > 2e9 ? 2000000000 : (int)kk;
         if (d.ftran_nt_k < 513) d.ftran_nt_k = 513;
     }
+    d.beta_split = 1;
+    if (const char *bs = std::getenv("DZG_CHAIN_BETA_SPLIT")) d.beta_split = bs[0] != '0';
     d.fold_k = 0x7fffffff;
     if (const char *fk = std::getenv("DZG_CHAIN_FOLD_K")) d.fold_k = std::atoi(fk);
     d.world = o.world > 1 ? o.world : 1;
@@ -677,6 +679,7 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
         TRY(dev_alloc(s, &d.W, (size_t)d.ldw * DZG_RMAX));
         TRY(dev_alloc(s, &d.Wc, (size_t)d.ldw * DZG_RMAX));
         TRY(dev_alloc(s, &d.ag, (size_t)m + 2)); TRY(dev_alloc(s, &d.beta, (size_t)DZG_RMAX));
+        TRY(dev_alloc(s, &d.beta_part, (size_t)4 * DZG_RMAX));
         TRY(dev_alloc(s, &d.plist, (size_t)q)); TRY(dev_alloc(s, &d.pslot, (size_t)q));
         TRY(dev_alloc(s, &d.bcode, (size_t)m)); TRY(dev_alloc(s, &d.nbcode, (size_t)q));
         TRY(dev_alloc(s, &d.pcode, (size_t)q));
@@ -1317,7 +1320,7 @@ static int budget_spent(dzg_solver *s, bool *spent)
 
 // A device-wide barrier of the three-launch iteration failed (its workgroups were not all resident:
 // another kernel holds CUs or LDS of this device).  chain_barrier fails CONSISTENTLY -- every
-// workgroup of the launch alike -- and both chain kernels write nothing but scratch (dx, v, beta,
+// workgroup of the launch alike -- and both chain kernels write nothing but scratch (dx, v, beta_part,
 // candidates, the decision fields of the control block) before their last barrier, and every
 // later launch of the batch saw status != RUNNING: the solver state is that of the last completed
 // pivot.  Clear the counters, carry on with the barrier-free seven launches (same arithmetic, same

@@ -70,6 +70,64 @@ __device__ __forceinline__ double fast_beta_dot(const double *__restrict__ wt,
     return block_sum((a0 + a1) + (a2 + a3));
 }
 
+// Wave w (0..3) of fast_beta_dot on its own: ONE wave calls (any wave of any workgroup), no LDS, no
+// workgroup barrier.  Lane l does what thread 64 w + l does above -- the same four strided sums in the
+// same order, the same wave tree -- so the value is bit for bit the s_sum[w] that block_sum adds up;
+// it depends on the elements i = 64 w + l (mod 256) only, a quarter of W_t and of a_j.
+__device__ __forceinline__ double fast_beta_wave(const double *__restrict__ wt,
+                                                 const double *__restrict__ a, int m, int w)
+{
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    int i = 64 * w + (int)(threadIdx.x & 63);
+    // Eight steps of the loop below at a time, their 64 loads issued before the first product: the
+    // scheduling barrier is what keeps them in flight together.  Left to itself the compiler waits
+    // for each step's pair of loads before it issues the next (it does in fast_beta_dot as inlined
+    // in the chain kernels: 32 trips one behind the other at m = 8192, 4 us where one trip is 2).
+    for (; i + 31 * 256 < m; i += 32 * 256) {
+        double wv[32], av[32];
+#pragma unroll
+        for (int j = 0; j < 32; ++j) {
+            wv[j] = wt[i + 256 * j];
+            av[j] = a[i + 256 * j];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int s = 0; s < 8; ++s) {
+            a0 = fma(wv[4 * s], av[4 * s], a0);
+            a1 = fma(wv[4 * s + 1], av[4 * s + 1], a1);
+            a2 = fma(wv[4 * s + 2], av[4 * s + 2], a2);
+            a3 = fma(wv[4 * s + 3], av[4 * s + 3], a3);
+        }
+    }
+    for (; i + 3 * 256 < m; i += 4 * 256) {
+        a0 = fma(wt[i], a[i], a0);
+        a1 = fma(wt[i + 256], a[i + 256], a1);
+        a2 = fma(wt[i + 512], a[i + 512], a2);
+        a3 = fma(wt[i + 768], a[i + 768], a3);
+    }
+    for (; i < m; i += 256) a0 = fma(wt[i], a[i], a0);
+    double x = (a0 + a1) + (a2 + a3);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, DZG_WAVE);
+    return x;
+}
+
+// ... and block_sum's addition of the four wave sums, literally: t = 0.0, t += s_sum[w] for the
+// eight waves of a 512-thread workgroup, the last four of which hold +0.0
+__device__ __forceinline__ double fast_beta_fold(double s0, double s1, double s2, double s3)
+{
+    double t = 0.0;
+    t += s0;
+    t += s1;
+    t += s2;
+    t += s3;
+    t += 0.0;
+    t += 0.0;
+    t += 0.0;
+    t += 0.0;
+    return t;
+}
+
 // One row of dx = Binv a_j by the LPR lanes of a wave that share `i` (lane `sub` of LPR), in two
 // steps so that a kernel may do the first before beta is known: (head) this lane's share of the
 // compact row of Binv0 against the gathered column `ag` (padded with a zero to an even length);

@@ -26,10 +26,10 @@
 //   Barriers per iteration: 2 (primal step: both in k_chain_pre), 1 (dual step: in k_chain_post).
 //
 // The barrier itself is fence-free (profiles/r02_gridsync_vs_kernel_boundary.txt): an agent-scope
-// release would write back the XCD's whole L2.  What crosses a barrier -- 64 doubles of beta, one
-// candidate record per workgroup -- is published with agent-scope (sc1, write-through) stores by
-// lane 0 and read with sc1 loads; everything else a phase reads was written by an earlier launch or
-// by the reading workgroup itself.  Arrivals are counted on eight counters (one per residue of the
+// release would write back the XCD's whole L2.  What crosses a barrier -- beta's 4 x 64 wave sums,
+// one candidate record per workgroup -- is published with agent-scope (sc1, write-through) stores by
+// lane 0 (of the wave that computed it) and read with sc1 loads; everything else a phase reads was
+// written by an earlier launch or by the reading workgroup itself.  Arrivals are counted on eight counters (one per residue of the
 // workgroup index mod 8, so that 256 atomics do not queue on one address), the last arrival of a
 // residue class bumps the top counter everybody polls.  The counters only grow; the number of
 // barriers passed so far lives in the control block (bar_gen).  A poll loop gives up after ~2.4 s (2^24 polls), marks
@@ -195,20 +195,71 @@ __device__ __forceinline__ const double *chain_col(const DzgDev &d, int code,
     return d.A + (long long)(code - d.col0) * d.lda;
 }
 
-// beta_t = W_t . a_j by workgroup t, published for everybody
+// beta_t = W_t . a_j, published for everybody as the FOUR WAVE SUMS fast_beta_dot adds up
+// (fast_rows.h): a wave sum depends on a quarter of W_t and a_j only, so the work items are the pairs
+// (t, w), item = 4 t + w, one wave each -- at the usual grid of one workgroup per CU at most one item
+// per workgroup, 16 + 16 KB of m = 8192 through a CU instead of 64 + 64 KB through the CUs of the
+// first neta workgroups while the others wait for them at the barrier.  The wave that runs an item is
+// one that has no share of the gather (threads < k2) and does not carry row p or the books (the
+// last wave): wave CH_BETA_WAVE, then the waves after it.  Lane 0 publishes the sum in
+// beta_part[item]; chain_beta_fetch adds the four up after the barrier, in block_sum's order.
+// An entering slack (code < 0): beta_t = W_t[row] is one load and takes no part in any sum
+// (0.0 + -0.0 would lose the sign): item (t, 0) publishes it, slot 4 t is taken verbatim.
+// d.beta_split == 0 (DZG_CHAIN_BETA_SPLIT=0, the A/B switch): workgroup t runs the four items of
+// eta t on its first four waves, as fast_beta_dot spreads them; same slots, same bits.
+#define CH_BETA_WAVE 3
+__device__ __forceinline__ void chain_beta_item(const DzgDev &d, int item, int code,
+                                                const double *__restrict__ a)
+{
+    const int t = item >> 2, w = item & 3;
+    const double *wt = d.W + (long long)t * d.ldw;
+    double s;
+    if (code < 0) {
+        if (w != 0) return;
+        s = wt[-1 - code];
+    } else {
+        s = fast_beta_wave(wt, a, d.m, w);
+    }
+    if ((threadIdx.x & 63) == 0) st_sc1(d.beta_part + item, s);
+}
 __device__ __forceinline__ void chain_beta(const DzgDev &d, int neta, int code,
                                            const double *__restrict__ a)
 {
-    // (block-uniform loop: a grid of fewer workgroups than pending etas -- a CU-masked or
-    // partitioned device -- takes several rows per workgroup; same bits, beta_t depends on t only)
-    for (int b = blockIdx.x; b < neta; b += gridDim.x) {
-        const double *wt = d.W + (long long)b * d.ldw;
-        double acc;
-        if (code < 0)
-            acc = wt[-1 - code];
-        else
-            acc = fast_beta_dot(wt, a, d.m);
-        if (threadIdx.x == 0) st_sc1(d.beta + b, acc);
+    const int wave = threadIdx.x >> 6;
+    if (!d.beta_split) {
+        for (int b = blockIdx.x; b < neta; b += gridDim.x)
+            if (wave < 4) chain_beta_item(d, 4 * b + wave, code, a);
+        return;
+    }
+    // (block-uniform loop: a grid of fewer workgroups than items -- a CU-masked or partitioned
+    // device -- takes several per workgroup, on different waves while there are any; an item's bits
+    // depend on the item only)
+    int turn = CH_BETA_WAVE;
+    for (int item = blockIdx.x; item < 4 * neta; item += gridDim.x) {
+        if (wave == turn) chain_beta_item(d, item, code, a);
+        turn = turn + 1 < CH_NW ? turn + 1 : 0;
+    }
+}
+// What crosses a barrier is published by the lane that arrives at it (chain_barrier.h); the lanes
+// that published wave sums are others, so every wave sees its own stores out of the CU before the
+// workgroup barrier that chain_barrier begins with.  (By then the stores are long acknowledged.)
+__device__ __forceinline__ void chain_beta_published()
+{
+    __builtin_amdgcn_s_waitcnt(0);
+}
+// After the barrier: beta into LDS.  Threads < 4 R_ load one slot each -- one trip, as the 64 loads
+// were -- lane 4 j of a wave gathers the four slots of its eta by shuffle and adds them up.  The
+// caller's __syncthreads makes s_beta visible.
+__device__ __forceinline__ void chain_beta_fetch(const DzgDev &d, int neta, int code, double *s_beta)
+{
+    const int tid = threadIdx.x;
+    if (tid < 4 * R_) { // (whole waves: 4 R_ is a multiple of 64)
+        const double s0 = tid < 4 * neta ? ld_sc1(d.beta_part + tid) : 0.0;
+        const double s1 = __shfl_down(s0, 1, DZG_WAVE);
+        const double s2 = __shfl_down(s0, 2, DZG_WAVE);
+        const double s3 = __shfl_down(s0, 3, DZG_WAVE);
+        const int t = tid >> 2;
+        if ((tid & 3) == 0) s_beta[t] = t < neta ? (code < 0 ? s0 : fast_beta_fold(s0, s1, s2, s3)) : 0.0;
     }
 }
 
@@ -364,6 +415,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         if (lead && code < 0) edslot = d.dslot[-1 - code];
         chain_stage_ag(s_ag, k, code, a, d.drow, dr0, dr1);
         chain_beta(d, neta, code, a);
+        ts.mark(slot); // 1: code, column, gather, (this workgroup's wave sum of) beta
         if (lead) {
             ctl->enter_code = code;
             ctl->zr = zr; // (SHARD: z is kept by the column's owner; k_chain_post takes it from
@@ -377,10 +429,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
             chain_dot_head<64>(d, r0, r1, k, s_ag, accs);
         else
             chain_dot_head<16>(d, r0, r1, k, s_ag, accs);
-        ts.mark(slot); // 1: beta, gather, Binv0 rows
+        chain_beta_published();
+        ts.mark(slot); // 2: Binv0 rows
         if (!chain_barrier(ctl, bar, gen)) return;
-        ts.mark(slot); // 2: barrier
-        if (tid < R_) s_beta[tid] = tid < neta ? ld_sc1(d.beta + tid) : 0.0;
+        ts.mark(slot); // 3: barrier
+        chain_beta_fetch(d, neta, code, s_beta);
         __syncthreads();
         if (k > 512)
             chain_dot_tail<64>(d, r0, r1, k, neta, s_ag, s_beta, accs, s_dx);
@@ -408,9 +461,9 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
             st_sc1(d.rx_k + blockIdx.x, best.k);
             st_sc1(d.rx_h + blockIdx.x, best.h);
         }
-        ts.mark(slot); // 3: eta share, candidates
+        ts.mark(slot); // 4: eta share, candidates
         if (!chain_barrier(ctl, bar, gen)) return;
-        ts.mark(slot); // 4: barrier
+        ts.mark(slot); // 5: barrier
         if (wave == 0) {
             const DzgCand2 w = chain_reduce_sc1(d.rx_r, d.rx_k, d.rx_h, nwg, lane);
             if (lane == 0) chain_put(s_c, 0, w);
@@ -423,7 +476,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         }
         p = cw.k;
         if (lead) ctl->leave_pos = p;
-        ts.mark(slot); // 5: ratio test
+        ts.mark(slot); // 6: ratio test
     } else {
         p = ci.k;
     }
@@ -456,7 +509,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         ctl->leave_code = lcode;
         if (gen != c.bar_gen) ctl->bar_gen = gen;
     }
-    ts.mark(slot); // primal 6 / dual 1: BTRAN row
+    ts.mark(slot); // primal 7 / dual 1: BTRAN row
     ts.done(slot);
 }
 
@@ -685,6 +738,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
             if (ci < 0) unit_p = cj >= 0 ? a[-1 - ci] : (cj == ci ? 1.0 : 0.0);
             chain_stage_ag(s_ag, k, cj, a, d.drow, dr0, dr1);
             chain_beta(d, neta, cj, a);
+            ts.mark(slot); // 1: loads, code, column, gather, (this workgroup's wave sum of) beta
             if (lead) {
                 ctl->enter_pos = r;
                 ctl->enter_code = cj;
@@ -705,10 +759,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
                 accp = fast_gemv_row_head<16>(wave == CH_NW - 1 && lane < 16 ? p : m, m, k2, d.binv, d.ldb, s_ag,
                                               lane % 16);
             }
-            ts.mark(slot); // 1: loads, beta, gather, Binv0 rows
+            chain_beta_published();
+            ts.mark(slot); // 2: Binv0 rows
             if (!chain_barrier(ctl, bar, gen)) return;
-            ts.mark(slot); // 2: barrier
-            if (tid < R_) s_beta[tid] = tid < neta ? ld_sc1(d.beta + tid) : 0.0;
+            ts.mark(slot); // 3: barrier
+            chain_beta_fetch(d, neta, cj, s_beta);
             __syncthreads();
             if (k > 512) {
                 chain_dot_tail<64>(d, r0, r1, k, neta, s_ag, s_beta, accs, s_dx);
@@ -731,7 +786,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
                 if (has_unit) dx_i += unit_i;
                 d.dx[row] = dx_i;
             }
-            ts.mark(slot); // 3: eta share
+            ts.mark(slot); // 4: eta share
         } else {
             r = c.enter_pos;
             cj = c.enter_code;
@@ -791,7 +846,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
             if (c.drift_tau > adaptive) adaptive = c.drift_tau;
             tau = adaptive > c.tie_tol ? adaptive : c.tie_tol;
         }
-        ts.mark(slot); // primal 1 / dual 4: step lengths
+        ts.mark(slot); // primal 1 / dual 5: step lengths
     }
     // ---- update of this thread's row and column; candidates on the updated values
     DzgCand2 bx = dzg_cand2_none(), bz = dzg_cand2_none();
@@ -845,7 +900,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
         d.fpz_h[blockIdx.x] = bz.h;
         if (blockIdx.x == 0) ctl->fp_count = (int)gridDim.x;
     }
-    ts.mark(slot); // primal 2 / dual 5: update + candidates
+    ts.mark(slot); // primal 2 / dual 6: update + candidates
     ts.done(slot);
 }
 
