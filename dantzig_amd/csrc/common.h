@@ -121,16 +121,63 @@ struct DzgCand2 {
 // Diagnostic (DZG_CHAIN_DEBUG=1): lane 0 of workgroup 0 accumulates the 100 MHz real-time clock
 // between phase boundaries; dbg[16 * kernel_and_kind + stage] += ticks, dbg[.. + 15] += 1.
 // Slots: 0 / 1 k_chain_pre primal / dual, 2 / 3 k_chain_post primal / dual, 4 k_price_rows_small.
-#define DZG_STAMP_SLOTS 5
+// Sub-stamps of the argmax reduction sites (profiles/cand_reduce.txt): slot 5 holds the ticks of a
+// site, slot 6 how often it ran; sites are numbered DZG_SITE_*.  A site is clocked inside the stage
+// that holds it, so with the diagnostic on every site adds its two clock reads (about 1 us) to that
+// stage.  Without the diagnostic (`on` false, the same for every thread of the launch) a pin, a clock
+// read and a site are each one scalar branch that is never taken.  DZG_SITE_BOOKS / DZG_SITE_POST_END are ticks since the start of a dual k_chain_post: of the
+// lane that keeps the pivot's books (lane 0 of the last wave -- thread 0's clocks never see it) and
+// of thread 0's last stamp.
+#define DZG_STAMP_SLOTS 7
+#define DZG_SITE_SLOT 5
+#define DZG_SITE_PRE_FIRST 0    // k_chain_pre: chain_spec_reduce of fpz on wave 0 (fpx beside it on wave 1)
+#define DZG_SITE_PRE_STATUS 1   // k_chain_pre: fast_status
+#define DZG_SITE_PRE_ROWBEST 2  // k_chain_pre primal: chain_best of the row ratio test
+#define DZG_SITE_PRE_SC1 3      // k_chain_pre primal: chain_reduce_sc1 (loads included) + barrier
+#define DZG_SITE_POST_RATIO 4   // k_chain_post dual: chain_spec_reduce of the ratio test
+#define DZG_SITE_POST_BX 5      // k_chain_post: bx and bz, reduced together (chain_best_pair)
+#define DZG_SITE_POST_BZ 6      // (bz alone, when the two were reduced one behind the other: the "before" build)
+#define DZG_SITE_PUBLISH 7      // k_price_rows_small: the publish step
+#define DZG_SITE_BOOKS 8
+#define DZG_SITE_POST_END 9
+#define DZG_SITE_COUNT 10
 struct ChainStamps {
     unsigned long long *dbg;
-    unsigned long long last;
+    unsigned long long last, t0;
     int stage;
+    bool on; // the diagnostic runs (kernel-uniform)
     __device__ __forceinline__ void start(unsigned long long *p)
     {
+        on = p != nullptr;
         dbg = (blockIdx.x == 0 && threadIdx.x == 0) ? p : nullptr;
         stage = 0;
-        if (dbg) last = __builtin_amdgcn_s_memrealtime();
+        if (dbg) last = t0 = __builtin_amdgcn_s_memrealtime();
+    }
+    // a reduction site: const unsigned long long t = ts.now(); ...; ts.site(DZG_SITE_x, t);
+    __device__ __forceinline__ unsigned long long now() const
+    {
+        return on ? __builtin_amdgcn_s_memrealtime() : 0ull;
+    }
+    __device__ __forceinline__ void site(int which, unsigned long long since)
+    {
+        if (!on || !dbg) return;
+        dbg[16 * DZG_SITE_SLOT + which] += __builtin_amdgcn_s_memrealtime() - since;
+        dbg[16 * (DZG_SITE_SLOT + 1) + which] += 1;
+    }
+    __device__ __forceinline__ void since_start(int which) { site(which, t0); }
+    // the values a site takes or makes are in their registers before the clock is read (pure
+    // arithmetic is otherwise free to move across the read)
+    __device__ __forceinline__ void pin(double &v) const
+    {
+        if (on) asm volatile("" : "+v"(v));
+    }
+    __device__ __forceinline__ void pin(int &v) const
+    {
+        if (on) asm volatile("" : "+v"(v));
+    }
+    __device__ __forceinline__ void pin(DzgCand2 &c) const
+    {
+        if (on) asm volatile("" : "+v"(c.r), "+v"(c.k), "+v"(c.h));
     }
     __device__ __forceinline__ void mark(int slot)
     {
@@ -202,6 +249,162 @@ __device__ __forceinline__ DzgCand2 dzg_block_best2(DzgCand2 c)
         o.h = s2_h[lane];
     }
     return dzg_wave_best2(o);
+}
+
+// ---------------------------------------------------------------------------------
+// The same reduction without the pairwise merge of structs, for the places where ONE wave reduces
+// while its workgroup waits (the three-launch iteration at small k, k_chain.hip and
+// k_price_rows_small).  dzg_wave_best2 costs six rounds of five LDS-crossbar permutes, two waits and
+// two divergent branches each; this form is three scalar reductions and two ballots, straight-line:
+//
+//      R = max r over the valid lanes (k >= 0)             winner: r == R, lowest k among those
+//      K = min k over the lanes with r == R                r: the winner lane's own bits
+//      H = max over every lane's h and over the r of every valid lane that is not the winner
+//
+// Each step of a reduction moves the partner's value with DPP inside a row of 16 lanes (quad_perm
+// xor 1, xor 2, row_half_mirror, row_mirror: after the first two steps a quad is uniform, so the
+// mirrors are xor 4 and xor 8); the four row results are read with v_readlane and combined in
+// scalar registers, so the result is wave-uniform.  EVERY LANE OF THE WAVE MUST BE ACTIVE.
+//
+// Why it equals the fold of dzg_better2 in any grouping, for what the call sites produce:
+//   inputs   a valid lane has k >= 0, the k of valid lanes are pairwise different (positions, rows,
+//            workgroup winners of disjoint shares); a lane without candidate is dzg_cand2_none() but
+//            for its h (r = +0.0, k = -1: dzg_cand2_none and dzg_better2 of two of them make nothing
+//            else); no r of a valid lane and no h is NaN -- dzg_first_pivot_entry admits a ratio only
+//            if r == r, the ratio tests only if r > 0.0, the pseudo-candidates are -inf, and h is
+//            -inf, +inf or some such r.  +-inf are ordinary values here.
+//   winner   dzg_better2 keeps the larger of two valid candidates in the order (r descending, k
+//            ascending) and any valid one against a none.  With different k this order is total, so
+//            every grouping of the fold ends on its one maximum: the lanes with r == R (-0.0 == +0.0,
+//            as in dzg_better2), and of those the lowest k.  r and k are copied, never computed: the
+//            winner's r is the bits of its own lane -- read back from that lane here, since R, a
+//            maximum, may carry the other zero's sign.
+//   no lane  valid: the fold returns a none, r = +0.0, k = -1, and so does this.
+//   h        in the fold every valid lane but the winner loses exactly once, as the winner of its
+//            subtree, and its r joins h there; h is otherwise only ever the larger of two h.  So h is
+//            the maximum of a fixed multiset -- all h, all r of valid non-winners -- taken with
+//            `a > b ? a : b`: with no NaN the VALUE does not depend on the order.  If two or more
+//            lanes hold r == R the losers among them contribute R itself (for R != 0 the same bits
+//            whichever lane), which is how H is formed without knowing K first.
+//   zero h   the one thing that depends on the grouping, in the fold itself: +0.0 against -0.0 in
+//            `a > b ? a : b` keeps b.  No consumer can tell: dzg_margin compares h with +-inf, takes
+//            fabs(h), and where h is a zero and the winner is too it returns 0.0 before the
+//            subtraction (den == 0), while r - (+-0.0) for r != 0 is r either way; ratio_margin only
+//            compares h with -inf before it calls dzg_margin; tie_gate sees the margin alone; and an
+//            h that is folded on (the partial candidates of a workgroup) enters the next fold through
+//            `>` again.
+// ---------------------------------------------------------------------------------
+__device__ __forceinline__ double dzg_readlane_f64(double v, int lane);
+
+#define DZG_DPP_XOR1 0xB1        // quad_perm [1, 0, 3, 2]
+#define DZG_DPP_XOR2 0x4E        // quad_perm [2, 3, 0, 1]
+#define DZG_DPP_HALF_MIRROR 0x141 // lane i <-> 7 - i of its half row
+#define DZG_DPP_MIRROR 0x140      // lane i <-> 15 - i of its row
+
+template <int CTRL>
+__device__ __forceinline__ double dzg_dpp_f64(double v)
+{
+    const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);
+    const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+__device__ __forceinline__ double dzg_max_keep(double a, double b) // one of its operands, bit for bit
+{
+    return a > b ? a : b;
+}
+
+// W = 64: the maximum over the wave.  W = 16 / 8: over lanes 0 .. W-1 (the log2 W steps of one row).
+template <int W>
+__device__ __forceinline__ double dzg_lanes_max_f64(double v)
+{
+    v = dzg_max_keep(v, dzg_dpp_f64<DZG_DPP_XOR1>(v));
+    v = dzg_max_keep(v, dzg_dpp_f64<DZG_DPP_XOR2>(v));
+    v = dzg_max_keep(v, dzg_dpp_f64<DZG_DPP_HALF_MIRROR>(v));
+    if (W > 8) v = dzg_max_keep(v, dzg_dpp_f64<DZG_DPP_MIRROR>(v));
+    const int lo = __double2loint(v), hi = __double2hiint(v);
+    double s = __hiloint2double(__builtin_amdgcn_readlane(hi, 0), __builtin_amdgcn_readlane(lo, 0));
+    if (W > 16) {
+        const double s1 = __hiloint2double(__builtin_amdgcn_readlane(hi, 16), __builtin_amdgcn_readlane(lo, 16));
+        const double s2 = __hiloint2double(__builtin_amdgcn_readlane(hi, 32), __builtin_amdgcn_readlane(lo, 32));
+        const double s3 = __hiloint2double(__builtin_amdgcn_readlane(hi, 48), __builtin_amdgcn_readlane(lo, 48));
+        s = dzg_max_keep(dzg_max_keep(s, s1), dzg_max_keep(s2, s3));
+    }
+    return s;
+}
+
+template <int W>
+__device__ __forceinline__ int dzg_lanes_min_i32(int v)
+{
+    int o = __builtin_amdgcn_update_dpp(0, v, DZG_DPP_XOR1, 0xf, 0xf, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, DZG_DPP_XOR2, 0xf, 0xf, false);
+    v = o < v ? o : v;
+    o = __builtin_amdgcn_update_dpp(0, v, DZG_DPP_HALF_MIRROR, 0xf, 0xf, false);
+    v = o < v ? o : v;
+    if (W > 8) {
+        o = __builtin_amdgcn_update_dpp(0, v, DZG_DPP_MIRROR, 0xf, 0xf, false);
+        v = o < v ? o : v;
+    }
+    int s = __builtin_amdgcn_readlane(v, 0);
+    if (W > 16) {
+        const int s1 = __builtin_amdgcn_readlane(v, 16), s2 = __builtin_amdgcn_readlane(v, 32);
+        const int s3 = __builtin_amdgcn_readlane(v, 48);
+        s = s1 < s ? s1 : s;
+        s = s2 < s ? s2 : s;
+        s = s3 < s ? s3 : s;
+    }
+    return s;
+}
+
+// W = 64: every lane holds a candidate or a none.  W = 16 / 8: lanes 0 .. W-1 do, and ALL OTHER
+// LANES HOLD dzg_cand2_none() (their h = -inf): the reductions then stay inside the first row.
+// The result is wave-uniform.
+template <int W>
+__device__ __forceinline__ DzgCand2 dzg_wave_best2_flat(DzgCand2 c)
+{
+    const double ninf = -__builtin_inf();
+    const bool valid = c.k >= 0;
+    const double R = dzg_lanes_max_f64<W>(valid ? c.r : ninf);
+    const bool top = valid && c.r == R;
+    const int K = dzg_lanes_min_i32<W>(top ? c.k : 0x7fffffff);
+    const double H0 = dzg_lanes_max_f64<W>(dzg_max_keep(c.h, (valid && !top) ? c.r : ninf));
+    const unsigned long long tops = __ballot(top);
+    const unsigned long long wins = __ballot(top && c.k == K);
+    const int wl = wins ? __builtin_ctzll(wins) : 0;
+    DzgCand2 w;
+    w.r = wins ? dzg_readlane_f64(c.r, wl) : 0.0;
+    w.k = wins ? K : -1;
+    w.h = __builtin_popcountll(tops) >= 2 ? dzg_max_keep(H0, R) : H0;
+    return w;
+}
+
+// Block-wide, two stages and ONE workgroup barrier: a wave reduction each, then the NW = blockDim.x / 64
+// wave results inside one row of W >= NW lanes (W = 8: three steps).  Result valid in every thread.
+// The LDS is written once per call: a kernel that calls this twice without a workgroup barrier of its
+// own in between passes guard = true (a barrier first, as dzg_block_best2 has).
+template <int W>
+__device__ __forceinline__ DzgCand2 dzg_block_best2_flat(DzgCand2 c, bool guard)
+{
+    __shared__ double f2_r[16], f2_h[16];
+    __shared__ int f2_k[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int nw = (blockDim.x + 63) >> 6;
+    c = dzg_wave_best2_flat<64>(c);
+    if (guard) __syncthreads();
+    if (lane == 0) {
+        f2_r[wave] = c.r;
+        f2_k[wave] = c.k;
+        f2_h[wave] = c.h;
+    }
+    __syncthreads();
+    DzgCand2 o = dzg_cand2_none();
+    if (lane < nw) {
+        o.r = f2_r[lane];
+        o.k = f2_k[lane];
+        o.h = f2_h[lane];
+    }
+    return dzg_wave_best2_flat<W>(o);
 }
 
 // Relative margin of a decision: (winner - runner-up) / max(|winner|, |runner-up|).

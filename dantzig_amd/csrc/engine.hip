@@ -263,9 +263,9 @@ static void chain_debug_report(dzg_solver *s)
     unsigned long long h[16 * DZG_STAMP_SLOTS];
     if (hipMemcpy(h, s->chain_dbg, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) return;
     // (the pricing kernel's stages: control block | row list | rows | finish)
-    static const char *names[DZG_STAMP_SLOTS] = {"k_chain_pre  primal", "k_chain_pre  dual  ", "k_chain_post primal",
+    static const char *names[DZG_SITE_SLOT] = {"k_chain_pre  primal", "k_chain_pre  dual  ", "k_chain_post primal",
                                                  "k_chain_post dual  ", "k_price_rows_small "};
-    for (int slot = 0; slot < DZG_STAMP_SLOTS; ++slot) {
+    for (int slot = 0; slot < DZG_SITE_SLOT; ++slot) {
         const double n = (double)h[16 * slot + 15];
         if (n <= 0) continue;
         std::fprintf(stderr, "[chain] %s x%-8.0f us per stage:", names[slot], n);
@@ -277,6 +277,17 @@ static void chain_debug_report(dzg_solver *s)
             std::fprintf(stderr, " %d:%.2f", st, us);
         }
         std::fprintf(stderr, "  sum %.2f\n", tot);
+    }
+    // the reduction sites (ChainStamps::site): us per visit; the last two since the kernel's start
+    static const char *sites[DZG_SITE_COUNT] = {"pre first-pivot reduce", "pre fast_status", "pre row chain_best",
+                                                "pre reduce_sc1", "post ratio reduce", "post chain_best bx",
+                                                "post chain_best bz", "price publish", "post dual books end",
+                                                "post dual last stamp"};
+    for (int i = 0; i < DZG_SITE_COUNT; ++i) {
+        const double n = (double)h[16 * (DZG_SITE_SLOT + 1) + i];
+        if (n <= 0) continue;
+        std::fprintf(stderr, "[chain] site %-24s x%-8.0f %.2f us\n", sites[i], n,
+                     (double)h[16 * DZG_SITE_SLOT + i] / n / 100.0);
     }
 }
 

@@ -77,6 +77,19 @@ __device__ __forceinline__ void chain_cols(int q, int &q0, int &q1)
     q1 = q0 + per < q ? q0 + per : q;
 }
 
+// The argmax reductions ONE wave runs while its workgroup waits: the straight-line form of common.h
+// (dzg_wave_best2_flat; bit for bit the fold of dzg_better2, see there; profiles/cand_reduce.txt).
+// All 64 lanes of the calling wave are active at every call below.
+__device__ __forceinline__ DzgCand2 chain_wave_best2(DzgCand2 c)
+{
+    return dzg_wave_best2_flat<64>(c);
+}
+__device__ __forceinline__ DzgCand2 chain_block_best2(DzgCand2 c)
+{
+    static_assert(CH_THREADS == 512, "eight wave results: one half row");
+    return dzg_block_best2_flat<8>(c, true);
+}
+
 // up to 4 x 64 partial candidates in the registers of one wave, loaded before their count is known
 struct ChainSpec {
     double r[4], h[4];
@@ -94,6 +107,13 @@ __device__ __forceinline__ void chain_spec_load(ChainSpec &s, const double *__re
     }
 }
 __device__ __forceinline__ DzgCand2 chain_spec_reduce(const ChainSpec &s, int count, int lane);
+// (DZG_CHAIN_DEBUG=1: a reduction site's clock starts once its operands have arrived)
+__device__ __forceinline__ void chain_spec_pin(const ChainStamps &ts, ChainSpec &s)
+{
+    if (ts.on)
+        asm volatile("" : "+v"(s.r[0]), "+v"(s.r[1]), "+v"(s.r[2]), "+v"(s.r[3]), "+v"(s.k[0]), "+v"(s.k[1]),
+                          "+v"(s.k[2]), "+v"(s.k[3]), "+v"(s.h[0]), "+v"(s.h[1]), "+v"(s.h[2]), "+v"(s.h[3]));
+}
 // the same for candidates that crossed a barrier of this launch (agent-scope loads): the four
 // slots of a lane leave together -- one trip, where a loop over i = lane, lane + 64, ... waits for
 // each turn's loads before it issues the next
@@ -125,7 +145,7 @@ __device__ __forceinline__ DzgCand2 chain_reduce_sc1(const double *pr, const int
         o.h = ld_sc1(ph + i);
         w = dzg_better2(w, o);
     }
-    return dzg_wave_best2(w);
+    return chain_wave_best2(w);
 }
 __device__ __forceinline__ DzgCand2 chain_spec_reduce(const ChainSpec &s, int count, int lane)
 {
@@ -138,7 +158,7 @@ __device__ __forceinline__ DzgCand2 chain_spec_reduce(const ChainSpec &s, int co
         o.h = s.h[j];
         if (lane + 64 * j < count) best = dzg_better2(best, o);
     }
-    return dzg_wave_best2(best);
+    return chain_wave_best2(best);
 }
 
 // two argmax candidates through LDS: written by lane 0 of waves 0 and 1, read by everybody
@@ -164,8 +184,23 @@ __device__ __forceinline__ DzgCand2 chain_get(const ChainSlots &s, int slot)
 // best of the candidates threads 0 .. n-1 hold; valid in wave 0 (n <= 64: no workgroup barrier)
 __device__ __forceinline__ DzgCand2 chain_best(DzgCand2 c, int n)
 {
-    if (n <= 64) return (threadIdx.x < 64) ? dzg_wave_best2(c) : c;
-    return dzg_block_best2(c);
+    if (n <= 64) return (threadIdx.x < 64) ? chain_wave_best2(c) : c;
+    return chain_block_best2(c);
+}
+// two independent ones side by side: in wave 0 the two straight-line reductions are one instruction
+// stream, and each one's waits (DPP, readlane, ballot) are filled with the other's work
+__device__ __forceinline__ void chain_best_pair(DzgCand2 &a, int na, DzgCand2 &b, int nb)
+{
+    if (na <= 64 && nb <= 64) {
+        if (threadIdx.x < 64) {
+            const DzgCand2 wa = chain_wave_best2(a), wb = chain_wave_best2(b);
+            a = wa;
+            b = wb;
+        }
+        return;
+    }
+    a = chain_best(a, na);
+    b = chain_best(b, nb);
 }
 
 // The entering column gathered to compact coordinates, in LDS (zero-padded to an even length).
@@ -379,14 +414,21 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
     const int dr0 = tid < k ? d.drow[tid] : -1;
     const int dr1 = tid + CH_THREADS < k ? d.drow[tid + CH_THREADS] : -1;
     if (wave < 2 && !(SHARD && wave == 0)) {
-        const DzgCand2 w = chain_spec_reduce(sp, c.fp_count, lane);
+        chain_spec_pin(ts, sp);
+        const unsigned long long t_site = ts.now();
+        DzgCand2 w = chain_spec_reduce(sp, c.fp_count, lane);
+        ts.pin(w);
+        ts.site(DZG_SITE_PRE_FIRST, t_site);
         if (lane == 0) chain_put(s_c, wave, w);
     }
     __syncthreads();
     const DzgCand2 cj = SHARD ? cj_rec : chain_get(s_c, 0), ci = chain_get(s_c, 1);
     int kind;
     double mu;
+    const unsigned long long t_status = ts.now();
     if (!fast_status(ctl, c, lead, cj, ci, d.eps, m, SHARD, kind, &mu)) return;
+    ts.pin(mu);
+    ts.site(DZG_SITE_PRE_STATUS, t_status);
     const int slot = kind == DZG_STEP_PRIMAL ? 0 : 1;
     ts.mark(slot); // 0: first touches + status
     if (k > CH_AGCAP || c.fp_count > 256) { // the host runs the seven launches before this can happen
@@ -455,7 +497,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
             if (cnd.r > 0.0) best = dzg_better2(best, cnd);
             if (dzg_noise_zero(den, x_i, scaled, c.tau)) best.h = __builtin_inf();
         }
+        ts.pin(best);
+        const unsigned long long t_rowbest = ts.now();
         best = chain_best(best, r1 - r0);
+        ts.pin(best);
+        ts.site(DZG_SITE_PRE_ROWBEST, t_rowbest);
         if (tid == 0) {
             st_sc1(d.rx_r + blockIdx.x, best.r);
             st_sc1(d.rx_k + blockIdx.x, best.k);
@@ -464,12 +510,15 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         ts.mark(slot); // 4: eta share, candidates
         if (!chain_barrier(ctl, bar, gen)) return;
         ts.mark(slot); // 5: barrier
+        const unsigned long long t_sc1 = ts.now();
         if (wave == 0) {
             const DzgCand2 w = chain_reduce_sc1(d.rx_r, d.rx_k, d.rx_h, nwg, lane);
             if (lane == 0) chain_put(s_c, 0, w);
         }
         __syncthreads();
-        const DzgCand2 cw = chain_get(s_c, 0);
+        DzgCand2 cw = chain_get(s_c, 0);
+        ts.pin(cw);
+        ts.site(DZG_SITE_PRE_SC1, t_sc1);
         if (!fast_ratio_outcome(ctl, c, lead, cw, DZG_UNBOUNDED)) { // :313
             if (lead) ctl->bar_gen = gen;
             return;
@@ -563,6 +612,9 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
     __shared__ ChainSlots s_c;
     ChainStamps ts;
     ts.start(only_partials ? nullptr : dbg);
+    const unsigned long long t_books = (dbg && !only_partials && blockIdx.x == 0 && threadIdx.x == CH_THREADS - 64)
+                                           ? __builtin_amdgcn_s_memrealtime()
+                                           : 0ull;
     int slot = 2;
     DzgCtl *ctl = d.ctl;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -696,7 +748,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
                 cw = chain_get(s_c, 0);
             } else if (one_wave) {
                 if (wave == 0) {
-                    const DzgCand2 w = chain_spec_reduce(sp, nrz, lane);
+                    chain_spec_pin(ts, sp);
+                    const unsigned long long t_site = ts.now();
+                    DzgCand2 w = chain_spec_reduce(sp, nrz, lane);
+                    ts.pin(w);
+                    ts.site(DZG_SITE_POST_RATIO, t_site);
                     if (lane == 0) chain_put(s_c, 0, w);
                 }
                 __syncthreads();
@@ -823,6 +879,11 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
             c.neta = neta;
             c.ncompact = k;
             fast_pivot_books_s(ctl, c, pa, ps, 1);
+            if (t_books && kind == DZG_STEP_DUAL && lane == 0) { // (the books lane's own clock)
+                __builtin_amdgcn_s_waitcnt(0);
+                dbg[16 * DZG_SITE_SLOT + DZG_SITE_BOOKS] += __builtin_amdgcn_s_memrealtime() - t_books;
+                dbg[16 * (DZG_SITE_SLOT + 1) + DZG_SITE_BOOKS] += 1;
+            }
         }
         if (!ps.ok) { // (the books have set DZG_PANIC, src/simplex.rs:466)
             if (lead && gen != c.bar_gen) ctl->bar_gen = gen;
@@ -889,8 +950,13 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
         }
         if (mine) dzg_first_pivot_entry(bz, zk, zb, col, tau);
     }
-    bx = chain_best(bx, r1 - r0);
-    bz = chain_best(bz, q1 - q0);
+    ts.pin(bx);
+    ts.pin(bz);
+    const unsigned long long t_best = ts.now();
+    chain_best_pair(bx, r1 - r0, bz, q1 - q0);
+    ts.pin(bx);
+    ts.pin(bz);
+    ts.site(DZG_SITE_POST_BX, t_best);
     if (tid == 0) {
         d.fpx_r[blockIdx.x] = bx.r;
         d.fpx_k[blockIdx.x] = bx.k;
@@ -901,6 +967,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
         if (blockIdx.x == 0) ctl->fp_count = (int)gridDim.x;
     }
     ts.mark(slot); // primal 2 / dual 6: update + candidates
+    if (slot == 3) ts.since_start(DZG_SITE_POST_END);
     ts.done(slot);
 }
 
@@ -1000,4 +1067,82 @@ extern "C" int dzg_debug_hold_wait(void)
 {
     if (!g_hold_stream) return 0;
     return hipStreamSynchronize(g_hold_stream) == hipSuccess ? 0 : DZG_E_DEVICE;
+}
+
+// ---------------------------------------------------------------------------------
+// Test hook: the straight-line argmax reduction on arrays of cases (include/dantzig_amd.h).
+// One wave (forms 0, 1) or one workgroup of 512 threads (form 2) per case; every lane is active.
+// ---------------------------------------------------------------------------------
+__global__ __launch_bounds__(CH_THREADS) void k_debug_cand_reduce(int form, const double *__restrict__ r,
+                                                                  const int *__restrict__ k,
+                                                                  const double *__restrict__ h,
+                                                                  const int *__restrict__ count,
+                                                                  double *out_r, int *out_k, double *out_h)
+{
+    const long long cs = blockIdx.x;
+    const int tid = threadIdx.x;
+    DzgCand2 w;
+    if (form == 0) {
+        DzgCand2 c;
+        c.r = r[cs * 64 + tid];
+        c.k = k[cs * 64 + tid];
+        c.h = h[cs * 64 + tid];
+        w = dzg_wave_best2_flat<64>(c);
+    } else if (form == 1) {
+        ChainSpec sp;
+        chain_spec_load(sp, r + cs * 256, k + cs * 256, h + cs * 256, tid);
+        w = chain_spec_reduce(sp, count[cs], tid);
+    } else {
+        DzgCand2 c;
+        c.r = r[cs * CH_THREADS + tid];
+        c.k = k[cs * CH_THREADS + tid];
+        c.h = h[cs * CH_THREADS + tid];
+        w = dzg_block_best2_flat<8>(c, false);
+    }
+    if (tid == 0) {
+        out_r[cs] = w.r;
+        out_k[cs] = w.k;
+        out_h[cs] = w.h;
+    }
+}
+
+extern "C" int dzg_debug_cand_reduce(int32_t device, int32_t form, int64_t ncases, const double *r,
+                                     const int32_t *k, const double *h, const int32_t *count, double *out_r,
+                                     int32_t *out_k, double *out_h)
+{
+    if (form < 0 || form > 2 || ncases < 1 || ncases > (1 << 20) || !r || !k || !h || !out_r || !out_k ||
+        !out_h || (form == 1 && !count))
+        return DZG_E_ARG;
+    if (hipSetDevice(device) != hipSuccess) return DZG_E_DEVICE;
+    const size_t width = form == 0 ? 64 : (form == 1 ? 256 : CH_THREADS), n = (size_t)ncases * width;
+    double *d_r = nullptr, *d_h = nullptr, *d_or = nullptr, *d_oh = nullptr;
+    int *d_k = nullptr, *d_cnt = nullptr, *d_ok = nullptr;
+    int rc = DZG_E_NOMEM;
+    if (hipMalloc(&d_r, n * 8) == hipSuccess && hipMalloc(&d_h, n * 8) == hipSuccess &&
+        hipMalloc(&d_k, n * 4) == hipSuccess && hipMalloc(&d_cnt, (size_t)ncases * 4) == hipSuccess &&
+        hipMalloc(&d_or, (size_t)ncases * 8) == hipSuccess && hipMalloc(&d_oh, (size_t)ncases * 8) == hipSuccess &&
+        hipMalloc(&d_ok, (size_t)ncases * 4) == hipSuccess) {
+        rc = DZG_E_DEVICE;
+        bool ok = hipMemcpy(d_r, r, n * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d_h, h, n * 8, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(d_k, k, n * 4, hipMemcpyHostToDevice) == hipSuccess &&
+                  (form != 1 || hipMemcpy(d_cnt, count, (size_t)ncases * 4, hipMemcpyHostToDevice) == hipSuccess);
+        if (ok) {
+            hipLaunchKernelGGL(k_debug_cand_reduce, dim3((unsigned)ncases), dim3(form == 2 ? CH_THREADS : 64), 0,
+                               nullptr, form, d_r, d_k, d_h, d_cnt, d_or, d_ok, d_oh);
+            ok = hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
+                 hipMemcpy(out_r, d_or, (size_t)ncases * 8, hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(out_k, d_ok, (size_t)ncases * 4, hipMemcpyDeviceToHost) == hipSuccess &&
+                 hipMemcpy(out_h, d_oh, (size_t)ncases * 8, hipMemcpyDeviceToHost) == hipSuccess;
+        }
+        if (ok) rc = 0;
+    }
+    hipFree(d_r);
+    hipFree(d_h);
+    hipFree(d_k);
+    hipFree(d_cnt);
+    hipFree(d_or);
+    hipFree(d_oh);
+    hipFree(d_ok);
+    return rc;
 }

@@ -100,6 +100,23 @@ __device__ __forceinline__ void price_publish(DzgCand2 best, double *__restrict_
     }
 }
 
+// k_price_rows_small's publish step (512 threads): the straight-line wave reduction of common.h,
+// then the eight wave results in the three steps of one half row -- one workgroup barrier instead of
+// two, no 64-lane butterfly for eight values.  The same candidate, bit for bit (common.h).
+// Only for a launch of exactly 512 threads, all of which arrive here (k_price_rows_small:
+// __launch_bounds__(512), launched with 512; its early exits are taken by the whole workgroup): the
+// half-row stage holds eight wave results, no more.
+__device__ __forceinline__ void price_publish_small(DzgCand2 best, double *__restrict__ rz_r,
+                                                    int *__restrict__ rz_k, double *__restrict__ rz_h)
+{
+    best = dzg_block_best2_flat<8>(best, false);
+    if (rz_r && threadIdx.x == 0) {
+        rz_r[blockIdx.x] = best.r;
+        rz_k[blockIdx.x] = best.k;
+        rz_h[blockIdx.x] = best.h;
+    }
+}
+
 // ---------------------------------------------------------------------------------
 // k_price_seq2<CW>: 4 waves per workgroup, CW columns per wave and pass, tiles of 128 rows.
 // Engine mode: plist != nullptr, count = ctl->nb_struct.  Raw mode (parity tests):
@@ -1116,7 +1133,10 @@ __global__ __launch_bounds__(512) void k_price_rows_small(
             price_candidate(best, d, ps, mu, tau, z, zbar);
         }
     }
-    price_publish(best, rz_r, rz_k, rz_h);
+    ts.pin(best);
+    const unsigned long long t_publish = ts.now();
+    price_publish_small(best, rz_r, rz_k, rz_h);
+    ts.site(DZG_SITE_PUBLISH, t_publish);
     ts.mark(PRS_STAMP_SLOT); // 3: finish
     ts.done(PRS_STAMP_SLOT);
 }

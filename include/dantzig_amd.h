@@ -614,6 +614,19 @@ int64_t dzg_debug_rl_listed(dzg_solver *s);
  * No solve path calls it. */
 int dzg_debug_basis_inverse(dzg_solver *s, int64_t row0, int64_t row1, double *out, int64_t info[4]);
 
+/* Test hook (tests/test_gpu_cand_reduce.py): runs the straight-line argmax reduction of the small-k
+ * three-launch iteration (csrc/common.h, dzg_wave_best2_flat) on `ncases` independent cases and
+ * returns one (r, k, h) per case.  Case c reads `width` consecutive candidates (r, k, h; k < 0: none)
+ * starting at index c * width of the input arrays:
+ *   form 0, width  64: one wave, candidate i in lane i;
+ *   form 1, width 256: one wave, the four-slot form (k_chain.hip, chain_spec_reduce): candidate i in
+ *                      slot i / 64 of lane i % 64, only the first count[c] of them take part;
+ *   form 2, width 512: a workgroup of eight waves, thread i holds candidate i: the two-stage block form.
+ * count is read for form 1 only.  No solve path calls it. */
+int dzg_debug_cand_reduce(int32_t device, int32_t form, int64_t ncases, const double *r, const int32_t *k,
+                          const double *h, const int32_t *count, double *out_r, int32_t *out_k,
+                          double *out_h);
+
 /* Deterministic max-loc merge: largest ratio wins, lowest global position on ties --
  * the sequential first-wins rule of src/simplex.rs:432-435,456-459.  Returns the index
  * of the winning record, or -1 when every record is empty. */
