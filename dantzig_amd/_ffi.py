@@ -40,9 +40,13 @@ EXPORTS = [
     "dzg_core_solve_full_csc", "dzg_debug_live_lists", "dzg_debug_rl_listed",
     "dzg_debug_basis_inverse", "dzg_batch_solve", "dzg_model_solve_batch", "dzg_mip_opts_default",
     "dzg_mip_solve", "dzg_mip_last_warm_stats", "dzg_debug_cand_reduce",
+    "dzg_solver_duals", "dzg_batch_solve_duals", "dzg_model_solve_duals",
+    "dzg_model_solve_batch_duals", "dzg_model_map_duals",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
+DUALS_FRESH, DUALS_CARRIED = 1, 2
+DUALS_SOURCE_NAMES = {DUALS_FRESH: "fresh", DUALS_CARRIED: "carried"}
 
 
 class Lp(C.Structure):
@@ -105,6 +109,17 @@ class ModelResult(C.Structure):
     _fields_ = [("status", C.c_int32), ("numerics_used", C.c_int32), ("iterations", C.c_int64),
                 ("objective", C.c_double), ("values", C.c_void_p), ("m", C.c_int64),
                 ("n", C.c_int64), ("near_ties", C.c_int64), ("first_near_tie", C.c_int64)]
+
+
+class Duals(C.Structure):
+    _fields_ = [("source", C.c_int32), ("reserved", C.c_int32), ("y", C.c_void_p), ("d", C.c_void_p),
+                ("primal_obj", C.c_double), ("dual_obj", C.c_double), ("primal_infeas", C.c_double),
+                ("dual_infeas", C.c_double), ("z_diff", C.c_double)]
+
+
+class ModelDuals(C.Structure):
+    _fields_ = [("con_dual", C.c_void_p), ("var_rc", C.c_void_p), ("lb_dual", C.c_void_p),
+                ("ub_dual", C.c_void_p), ("core", Duals)]
 
 
 class StdForm(C.Structure):
@@ -205,6 +220,13 @@ def lib() -> C.CDLL:
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_batch_solve.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.dzg_model_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_solver_duals.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_solve_duals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                               C.c_void_p]
+        _lib.dzg_model_solve_duals.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_model_solve_batch_duals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p]
+        _lib.dzg_model_map_duals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.dzg_mip_opts_default.restype = None
         _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

@@ -154,6 +154,30 @@ class CoreResult:
     price_pass_used: int = 0            # bit mask: 1 row-wise pricing pass ran, 2 column-wise
     price_rows_copy: int = 0            # 1: the row-major copy of the matrix is resident
     state_drift: float = 0.0            # carried x, xbar, z, zbar vs the fresh inverse at the last refactorisation
+    duals: "CoreDuals | None" = None    # solve_batch(duals=True): the LP's duals if it ended optimal
+
+
+@dataclass
+class CoreDuals:
+    """Dual values and reduced costs at an optimal basis, core sense (dzg_duals): y per row, d per
+    variable (0.0 for basics), the certificate scalars, and where they come from: "fresh"
+    (recomputed on the device from the final basis) or "carried" (read off the carried z)."""
+    source: str
+    source_code: int
+    y: np.ndarray
+    d: np.ndarray
+    primal_obj: float
+    dual_obj: float
+    primal_infeas: float
+    dual_infeas: float
+    z_diff: float
+
+
+def _core_duals(u, y, d) -> CoreDuals:
+    return CoreDuals(source=_ffi.DUALS_SOURCE_NAMES.get(int(u.source), "none"), source_code=int(u.source),
+                     y=y, d=d, primal_obj=float(u.primal_obj), dual_obj=float(u.dual_obj),
+                     primal_infeas=float(u.primal_infeas), dual_infeas=float(u.dual_infeas),
+                     z_diff=float(u.z_diff))
 
 
 def _counters(r) -> dict:
@@ -259,6 +283,17 @@ class Solver:
         """FAST: rebuild the basis inverse from scratch now (blocked LU + MFMA GEMMs)."""
         _ffi.check(_ffi.lib().dzg_solver_refactor(self._h), "dzg_solver_refactor")
 
+    def duals(self) -> CoreDuals:
+        """dzg_solver_duals: y = B^-T c_B and the reduced costs of the OPTIMAL basis this solver
+        ended on.  A FAST solver refactorises that basis for it (create it with
+        refactor_interval != 0); CSC and sharded solvers return the carried values."""
+        m, n = self._lp.m, self._lp.n
+        y, d = np.zeros(max(m, 1)), np.zeros(max(n, 1))
+        u = _ffi.Duals()
+        u.y, u.d = ptr(y), ptr(d)
+        _ffi.check(_ffi.lib().dzg_solver_duals(self._h, C.byref(u)), "dzg_solver_duals")
+        return _core_duals(u, y[:m].copy(), d[:n].copy())
+
     def debug_inverse(self, row0: int, row1: int) -> tuple[np.ndarray, dict]:
         """Test hook (dzg_debug_basis_inverse): rows [row0, row1) of the basis inverse FAST keeps --
         row i is basis position row0 + i, column r constraint row r -- and
@@ -329,14 +364,15 @@ _PIVOT_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("entering", "<i8
 
 
 def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
-                **opts) -> list:
+                duals: bool = False, **opts) -> list:
     """dzg_batch_solve: every LP of `lps` in STRICT numerics, one workgroup per LP, in one call.
 
     The whole batch is checked on the host first (ValueError: more than 128 rows, CSC input, FAST
     numerics, a column-block LP, vectors that do not match (m, n)); nothing reaches the device
     before that.  Result i is LP i's CoreResult, as `solve(lp, numerics=STRICT)` reports it; its
     solve_ms is the wall time of the whole batch call.  A result resumes through resumed_from, in a
-    batch or in a single Solver."""
+    batch or in a single Solver.  duals=True (dzg_batch_solve_duals): every result gains `.duals`, a
+    CoreDuals for an LP that ended optimal and None otherwise."""
     import time
 
     lps = list(lps)
@@ -373,11 +409,23 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         r.log = logs.ctypes.data + logs.strides[0] * i if cap > 0 else None
         r.log_cap = cap
     o = _ffi.default_opts(**opts)
+    if duals:
+        ns = [lp.n for lp in lps]
+        no = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+        y_all, d_all = np.zeros(mo[-1] + 1), np.zeros(no[-1] + 1)
+        du = (_ffi.Duals * max(count, 1))()
+        for i in range(count):
+            du[i].y = y_all.ctypes.data + 8 * int(mo[i])
+            du[i].d = d_all.ctypes.data + 8 * int(no[i])
     t0 = time.perf_counter()
-    rc = _ffi.lib().dzg_batch_solve(c_lps, C.c_int64(count), C.byref(o),
-                                    C.c_int64(int(pivots_per_launch)), res)
+    if duals:
+        rc = _ffi.lib().dzg_batch_solve_duals(c_lps, C.c_int64(count), C.byref(o),
+                                              C.c_int64(int(pivots_per_launch)), res, du)
+    else:
+        rc = _ffi.lib().dzg_batch_solve(c_lps, C.c_int64(count), C.byref(o),
+                                        C.c_int64(int(pivots_per_launch)), res)
     wall_ms = (time.perf_counter() - t0) * 1e3
-    _ffi.check(rc, "dzg_batch_solve")
+    _ffi.check(rc, "dzg_batch_solve_duals" if duals else "dzg_batch_solve")
     out = []
     for i in range(count):
         r = res[i]
@@ -392,6 +440,9 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
             basis=basis[a0:a1].copy(), nonbasis=nonbasis[b0:b1].copy(), x=x[a0:a1].copy(),
             xbar=xbar[a0:a1].copy(), z=z[b0:b1].copy(), zbar=zbar[b0:b1].copy(), pivots=pivots,
             solve_ms=wall_ms, **_counters(r)))
+        if duals:
+            out[-1].duals = None if du[i].source == 0 else _core_duals(
+                du[i], y_all[a0:a1].copy(), d_all[int(no[i]):int(no[i + 1])].copy())
     return out
 
 

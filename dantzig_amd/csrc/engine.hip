@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "common.h"
+#include "duals.h"
 
 static thread_local std::string g_err;
 
@@ -92,6 +93,8 @@ struct dzg_solver {
     DzgCtl *h_ctl = nullptr; // pinned
     std::vector<void *> allocs;
     std::vector<double> c_host;
+    std::vector<double> x0_host;   // the x the solve started with (rhs0 of the dual objective)
+    std::vector<int> var_col_host; // column code of every variable
     double constant = 0.0;
     double solve_ms = 0.0;
     int since_flush = 0; // iterations enqueued since the eta file was last folded into Binv0
@@ -124,6 +127,11 @@ struct dzg_solver {
     double *dr_b0 = nullptr, *dr_xb0 = nullptr, *dr_c = nullptr, *dr_cb = nullptr, *dr_agb = nullptr,
            *dr_agx = nullptr,
            *dr_part = nullptr, *dr_y = nullptr, *dr_dzy = nullptr, *dr_out = nullptr;
+    // dzg_solver_duals (k_duals.hip): buffers of its own, reserved by the first call
+    double *du_c = nullptr, *du_rhs0 = nullptr, *du_part = nullptr, *du_y = nullptr, *du_dzy = nullptr,
+           *du_d = nullptr, *du_out = nullptr;
+    int *du_codes = nullptr;
+    DzgCtl *du_ctl = nullptr; // STRICT: a control block that reads DZG_RUNNING for the LU kernels
     // FAST, dense, one GPU: the three-launch chain (k_chain.hip)
     unsigned long long *chain_bar = nullptr; // barrier counters (cleared only by chain_recover)
     unsigned long long *chain_dbg = nullptr; // DZG_CHAIN_DEBUG=1: phase clocks of workgroup 0
@@ -253,7 +261,7 @@ const int kNcclSum = 0;
 
 static void shard_comm_destroy(dzg_solver *s);
 static int shard_buffers(dzg_solver *s);
-static int refactor_now(dzg_solver *s);
+static int refactor_now(dzg_solver *s, bool at_end = false);
 static int refactor_workspace(dzg_solver *s);
 static bool partitioned(const dzg_solver *s);
 
@@ -599,6 +607,8 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
     }
     HIP_OK(hipMemsetAsync(d.v, 0, sizeof(double) * ((size_t)m + 2), s->st));
     s->c_host.assign(lp->c, lp->c + n);
+    if (m > 0) s->x0_host.assign(lp->x, lp->x + m);
+    s->var_col_host.assign(var_col.begin(), var_col.begin() + n);
     s->constant = lp->constant;
 
     // --- pivot log
@@ -1076,7 +1086,7 @@ static bool partitioned(const dzg_solver *s) { return s->d.world > 1 && !s->d.re
 
 // Stage A: the basis lists, one host sync to learn k and nl, the rank's share of G = A[R, S].
 // *active = false: the solve has ended, nothing to refactorise (every rank alike).
-static int refactor_stage_a(dzg_solver *s, int counts[2], bool *active)
+static int refactor_stage_a(dzg_solver *s, int counts[2], bool *active, bool at_end = false)
 {
     TRY(refactor_workspace(s));
     const DzgDev &d = s->d;
@@ -1086,6 +1096,8 @@ static int refactor_stage_a(dzg_solver *s, int counts[2], bool *active)
     TRY(read_ctl(s));
     *active = s->h_ctl->status == DZG_RUNNING || s->h_ctl->status == DZG_ITER_LIMIT ||
               s->h_ctl->status == DZG_NEAR_TIE;
+    // (at_end: dzg_solver_duals wants the fresh inverse of the OPTIMAL basis)
+    if (at_end && s->h_ctl->status == DZG_OPTIMAL) *active = true;
     if (!*active) return 0;
     if (counts[0] != s->h_ctl->ncompact)
         return fail(DZG_E_DEVICE, "refactor: structural basics != dense columns");
@@ -1172,13 +1184,13 @@ static int measure_drift(dzg_solver *s)
     return 0;
 }
 
-static int refactor_now(dzg_solver *s)
+static int refactor_now(dzg_solver *s, bool at_end)
 {
     if (partitioned(s) && s->in_lockstep)
         return fail(DZG_E_ARG, "refactor: the lockstep loop refactorises its ranks together");
     int counts[2];
     bool active = false;
-    TRY(refactor_stage_a(s, counts, &active));
+    TRY(refactor_stage_a(s, counts, &active, at_end));
     if (!active) return 0;
     // (every rank of a sharded solve gets here at the same pivot count with the same k and nl: the
     // triggers -- interval, health monitor, a pending warm start -- read replicated state only)
@@ -2176,7 +2188,178 @@ extern "C" int dzg_solver_result(dzg_solver *s, dzg_result *res)
     return 0;
 }
 
-static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res)
+// ---- dual values and reduced costs at the optimum (k_duals.hip) -------------
+static int duals_workspace(dzg_solver *s)
+{
+    if (s->du_out) return 0;
+    const DzgDev &d = s->d;
+    const size_t m = (size_t)d.m, q = (size_t)d.q, n = (size_t)d.n;
+    TRY(dev_alloc(s, &s->du_c, n)); TRY(dev_alloc(s, &s->du_rhs0, m));
+    TRY(dev_alloc(s, &s->du_y, m + 2)); TRY(dev_alloc(s, &s->du_dzy, q));
+    TRY(dev_alloc(s, &s->du_d, n));
+    if (s->numerics == DZG_NUMERICS_FAST) {
+        TRY(dev_alloc(s, &s->du_part, (size_t)dzg_drift_chunks() * (size_t)d.ldw));
+    } else {
+        TRY(dev_alloc(s, &s->du_codes, q));
+        TRY(dev_alloc(s, &s->du_ctl, 1));
+        DzgCtl c0;
+        std::memset(&c0, 0, sizeof(c0));
+        c0.status = DZG_RUNNING; // the LU kernels are no-ops under any other status
+        HIP_OK(hipMemcpyAsync(s->du_ctl, &c0, sizeof(c0), hipMemcpyHostToDevice, s->st));
+        HIP_OK(hipStreamSynchronize(s->st)); // (c0 is a local)
+    }
+    if (n) HIP_OK(hipMemcpyAsync(s->du_c, s->c_host.data(), sizeof(double) * n, hipMemcpyHostToDevice, s->st));
+    if (m) HIP_OK(hipMemcpyAsync(s->du_rhs0, s->x0_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, s->st));
+    HIP_OK(hipMemsetAsync(s->du_y, 0, sizeof(double) * (m + 2), s->st)); // (the two pads stay zero)
+    TRY(dev_alloc(s, &s->du_out, (size_t)DZG_DUALS_BLOCKS * DZG_DUALS_PART)); // set last: "reserved"
+    return 0;
+}
+
+extern "C" int dzg_solver_duals(dzg_solver *s, dzg_duals *out)
+{
+    if (!s || !out) return fail(DZG_E_ARG, "duals: NULL argument");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    if (s->h_ctl->status != DZG_OPTIMAL)
+        return fail(DZG_E_ARG, "duals: the solver's status is not DZG_OPTIMAL");
+    const DzgDev &d = s->d;
+    const int m = d.m, q = d.q, n = d.n;
+    hipStream_t st = s->st;
+    std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1));
+    std::vector<double> x((size_t)(m ? m : 1)), z((size_t)(q ? q : 1));
+    if (m) {
+        HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(x.data(), d.x, sizeof(double) * m, hipMemcpyDeviceToHost));
+    }
+    if (q) {
+        HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(z.data(), d.z, sizeof(double) * q, hipMemcpyDeviceToHost));
+    }
+    double sum = 0.0; // objective_value as dzg_solver_result forms it
+    for (int p = 0; p < m; ++p) {
+        const double prod = s->c_host[(size_t)basis[p]] * x[p];
+        sum = sum + prod;
+    }
+    out->reserved = 0;
+    out->primal_obj = s->constant + sum;
+    std::vector<double> y((size_t)(m ? m : 1), 0.0), dv((size_t)(n ? n : 1), 0.0);
+    double dmin = std::numeric_limits<double>::infinity(), dabs = 0.0, zdiff = 0.0, xmin = dmin, dot = 0.0;
+
+    if (d.csc || d.world > 1) {
+        // carried: the slack entries of z are the dual vector, z the reduced costs
+        for (int k = 0; k < q; ++k) {
+            const int var = nonbasis[k], code = s->var_col_host[(size_t)var];
+            dv[(size_t)var] = z[k];
+            if (code < 0) y[(size_t)(-1 - code)] = z[k];
+            dmin = std::min(dmin, z[k]);
+        }
+        for (int p = 0; p < m; ++p) xmin = std::min(xmin, x[p]);
+        for (int i = 0; i < m; ++i) {
+            const double prod = s->x0_host[(size_t)i] * y[(size_t)i];
+            dot = dot + prod;
+        }
+        out->source = DZG_DUALS_CARRIED;
+        out->dual_obj = s->constant + dot;
+        out->primal_infeas = std::max(0.0, -xmin);
+        out->dual_infeas = std::max(0.0, -dmin);
+        out->z_diff = 0.0;
+        if (out->y && m) std::memcpy(out->y, y.data(), sizeof(double) * m);
+        if (out->d && n) std::memcpy(out->d, dv.data(), sizeof(double) * n);
+        return 0;
+    }
+
+    const bool fast = s->numerics == DZG_NUMERICS_FAST;
+    if (fast && !s->rf_piv)
+        return fail(DZG_E_ARG, "duals: a FAST solver needs its refactorisation workspace: create it "
+                               "with opts.refactor_interval != 0");
+    TRY(duals_workspace(s));
+    if (fast) {
+        // a fresh inverse of the final basis (the eta file emptied), then y by the two-stage scheme of
+        // the drift measurement on buffers of our own, then one column-wise pricing pass with y as v
+        TRY(refactor_now(s, true));
+        TRY(read_ctl(s));
+        if (s->h_ctl->status != DZG_OPTIMAL) { // k_ref_done met a singular block: the solve's outcome stays
+            const int keep = DZG_OPTIMAL;
+            HIP_OK(hipMemcpy(&d.ctl->status, &keep, sizeof(int), hipMemcpyHostToDevice));
+            s->h_ctl->status = keep;
+            return fail(DZG_E_DEVICE, "duals: the optimal basis did not refactorise (singular block)");
+        }
+        dzg_launch_drift_y(d, s->du_c, s->du_part, s->du_y, (int)s->h_ctl->ncompact, st);
+        dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->du_dzy, st);
+    } else {
+        // B^T y = c_B by the LU of every STRICT BTRAN, on a copy of the device view whose control block
+        // reads DZG_RUNNING and whose v is our own buffer; then neg_t_dot in the reference's order
+        std::vector<double> cb((size_t)(m ? m : 1));
+        std::vector<int> codes((size_t)(q ? q : 1));
+        for (int p = 0; p < m; ++p) cb[(size_t)p] = s->c_host[(size_t)basis[p]];
+        for (int k = 0; k < q; ++k) codes[(size_t)k] = s->var_col_host[(size_t)nonbasis[k]];
+        if (m) HIP_OK(hipMemcpyAsync(s->du_y, cb.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+        if (q) HIP_OK(hipMemcpyAsync(s->du_codes, codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st)); // (cb and codes are locals)
+        DzgDev dd = d;
+        dd.ctl = s->du_ctl;
+        dd.v = s->du_y;
+        dzg_launch_strict_solve(dd, 1, st);
+        dzg_launch_price_raw(DZG_PRICE_SEQ, m, d.lda, d.A, s->du_codes, q, s->du_y, s->du_dzy, st);
+    }
+    dzg_launch_duals_finish(m, q, d.basis, d.nonbasis, s->du_c, s->du_dzy, d.z, d.x, s->du_rhs0, s->du_y,
+                            s->du_d, s->du_out, st);
+    std::vector<double> part((size_t)DZG_DUALS_BLOCKS * DZG_DUALS_PART);
+    HIP_OK(hipMemcpyAsync(part.data(), s->du_out, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+    if (m) HIP_OK(hipMemcpyAsync(y.data(), s->du_y, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    if (n) HIP_OK(hipMemcpyAsync(dv.data(), s->du_d, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    for (int b = 0; b < DZG_DUALS_BLOCKS; ++b) { // workgroup order
+        const double *r = &part[(size_t)b * DZG_DUALS_PART];
+        dmin = std::min(dmin, r[0]);
+        dabs = std::max(dabs, r[1]);
+        zdiff = std::max(zdiff, r[2]);
+        xmin = std::min(xmin, r[3]);
+        dot = dot + r[4];
+    }
+    if (!fast) { // the reference's order: rows ascending, one rounded product and sum each
+        dot = 0.0;
+        for (int i = 0; i < m; ++i) {
+            const double prod = s->x0_host[(size_t)i] * y[(size_t)i];
+            dot = dot + prod;
+        }
+    }
+    out->source = DZG_DUALS_FRESH;
+    out->dual_obj = s->constant + dot;
+    out->primal_infeas = std::max(0.0, -xmin);
+    out->dual_infeas = std::max(0.0, -dmin);
+    out->z_diff = zdiff / std::max(1.0, dabs);
+    if (out->y && m) std::memcpy(out->y, y.data(), sizeof(double) * m);
+    if (out->d && n) std::memcpy(out->d, dv.data(), sizeof(double) * n);
+    return 0;
+}
+
+// "no duals": an LP that did not end OPTIMAL, or whose duals could not be computed (k_batch.hip and
+// model.cpp use it too)
+void dzg_duals_none(dzg_duals *du, double objective)
+{
+    du->source = 0;
+    du->reserved = 0;
+    du->primal_obj = objective;
+    du->dual_obj = du->primal_infeas = du->dual_infeas = du->z_diff = 0.0;
+}
+
+// (status, result and, when `du` is given and the LP ended OPTIMAL, the duals of this solver)
+static int finish_solver(dzg_solver *s, int rc, dzg_result *res, dzg_duals *du)
+{
+    const int rc2 = dzg_solver_result(s, res);
+    if (rc2 == 0 && du) {
+        // the solve's outcome is what dzg_core_solve returns, whatever becomes of the duals: a call
+        // that fails (the final basis of a FAST run did not refactorise) leaves source = 0 and its
+        // message in dzg_last_error
+        if (res->status != DZG_OPTIMAL || dzg_solver_duals(s, du) != 0) dzg_duals_none(du, res->objective);
+    }
+    dzg_solver_destroy(s);
+    return rc2 != 0 ? rc2 : rc;
+}
+
+static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res, dzg_duals *du)
 {
     dzg_solver *s = nullptr;
     int rc = dzg_solver_create(lp, o, &s);
@@ -2186,17 +2369,18 @@ static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res)
         dzg_solver_destroy(s);
         return rc;
     }
-    const int rc2 = dzg_solver_result(s, res);
-    dzg_solver_destroy(s);
-    return rc2 != 0 ? rc2 : rc;
+    return finish_solver(s, rc, res, du);
 }
 
-extern "C" int dzg_core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res)
+// dzg_core_solve; with `du` also the duals of whichever solver produced the result (model.cpp)
+int dzg_core_solve_with_duals(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du)
 {
     if (!res) return fail(DZG_E_ARG, "res is NULL");
     if (!lp) return fail(DZG_E_ARG, "lp is NULL");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
+    // (duals of a FAST run: reserve the refactorisation workspace, as a non-slack start does)
+    if (du && o.refactor_interval == 0) o.refactor_interval = -1;
     const bool automatic = o.numerics == DZG_NUMERICS_AUTO;
     const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
     // AUTO above auto_strict_rows = FAST that must prove it followed the reference: up to
@@ -2208,7 +2392,7 @@ extern "C" int dzg_core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result
     const int restart_rows = o.auto_restart_rows != 0 ? o.auto_restart_rows : DZG_AUTO_STRICT_RESTART_ROWS;
     const bool can_restart = automatic && lp->m > strict_rows && lp->m <= restart_rows;
     if (can_restart && o.tie_tol >= 0.0) o.near_tie_action = DZG_NEAR_TIE_STOP;
-    int rc = solve_once(lp, &o, res);
+    int rc = solve_once(lp, &o, res, du);
     if (rc < 0) return rc;
     if (can_restart && res->numerics_used == DZG_NUMERICS_FAST &&
         (rc == DZG_NEAR_TIE || rc == DZG_SINGULAR || rc == DZG_PANIC)) {
@@ -2240,18 +2424,19 @@ extern "C" int dzg_core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result
             dzg_solver_destroy(ss);
             return rc;
         }
-        if (!out_of_time) {
-            const int rc2 = dzg_solver_result(ss, res);
-            dzg_solver_destroy(ss);
-            return rc2 != 0 ? rc2 : rc;
-        }
+        if (!out_of_time) return finish_solver(ss, rc, res, du);
         dzg_solver_destroy(ss);
         dzg_opts fast = o;
         fast.numerics = DZG_NUMERICS_FAST;
         fast.near_tie_action = DZG_NEAR_TIE_COUNT;
-        rc = solve_once(lp, &fast, res);
+        rc = solve_once(lp, &fast, res, du);
     }
     return rc;
+}
+
+extern "C" int dzg_core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res)
+{
+    return dzg_core_solve_with_duals(lp, opts, res, nullptr);
 }
 
 // Level 1 on the fields of the reference's `Simplex` AS THEY ARE (src/simplex.rs:84-112): one

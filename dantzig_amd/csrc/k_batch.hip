@@ -33,6 +33,7 @@
 
 #include "batch_strict.h"
 #include "common.h"
+#include "duals.h"
 
 int dzg_set_error(int code, const std::string &msg); // engine.hip
 int dzg_lp_valid(const dzg_lp *lp, std::string &why);
@@ -140,12 +141,15 @@ struct Section {
 
 #define DZG_BATCH_DEFAULT_PPL 16
 
-extern "C" int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
-                               int64_t pivots_per_launch, dzg_result *res)
+// dzg_batch_solve; with `du` the duals of the LPs that end OPTIMAL follow in the same allocation
+// (k_duals.hip), after the solve and on sections of their own: the solve's layout does not move
+static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots_per_launch,
+                       dzg_result *res, dzg_duals *du, bool want_duals)
 {
     // ---- host checks first: malformed input is DZG_E_ARG on any machine
     if (count < 0) return dzg_set_error(DZG_E_ARG, "batch: count < 0");
     if (count > 0 && (!lps || !res)) return dzg_set_error(DZG_E_ARG, "batch: lps or res is NULL");
+    if (count > 0 && want_duals && !du) return dzg_set_error(DZG_E_ARG, "batch: du is NULL");
     if (count >= (1ll << 31)) return dzg_set_error(DZG_E_ARG, "batch: count out of range");
     if (pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "batch: pivots_per_launch < 0");
     dzg_opts o;
@@ -224,6 +228,18 @@ extern "C" int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts 
     const size_t download_end = top;
     const Section s_dz = section(sizeof(double) * nq), s_list2 = section(sizeof(int) * N),
                   s_count = section(sizeof(int) * kBuckets);
+    // duals: c and the starting x go up, the OPTIMAL LPs' list goes up after the solve, y, d and the
+    // scalars come down
+    Section s_dlp, s_c, s_x0, s_dlist, s_y, s_d, s_scal;
+    if (want_duals) {
+        s_dlp = section(sizeof(DzgDualsLp) * N);
+        s_c = section(sizeof(double) * nvc);
+        s_x0 = section(sizeof(double) * nm);
+        s_dlist = section(sizeof(int) * N);
+        s_y = section(sizeof(double) * nm);
+        s_d = section(sizeof(double) * nvc);
+        s_scal = section(sizeof(double) * DZG_DUALS_SCAL * N);
+    }
 
     std::vector<unsigned char> host(download_end, 0);
     auto hp = [&](const Section &s) { return host.data() + s.off; };
@@ -276,6 +292,28 @@ extern "C" int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts 
     BHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     BHIP(hipMalloc((void **)&dev, top));
     BHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
+    std::vector<unsigned char> dhost; // s_dlp .. s_x0 as uploaded, then s_y .. s_scal as downloaded
+    if (want_duals) {
+        dhost.assign(top - s_dlp.off, 0);
+        DzgDualsLp *dl = (DzgDualsLp *)dhost.data();
+        double *cc = (double *)(dhost.data() + (s_c.off - s_dlp.off));
+        double *x0 = (double *)(dhost.data() + (s_x0.off - s_dlp.off));
+        for (int i = 0; i < N; ++i) {
+            const dzg_lp &lp = lps[i];
+            const BLp &d = desc[(size_t)i];
+            dl[i].a_off = d.a_off;
+            dl[i].vc_off = d.vc_off;
+            dl[i].m_off = d.m_off;
+            dl[i].q_off = d.q_off;
+            dl[i].constant = lp.constant;
+            dl[i].m = d.m;
+            dl[i].n = d.n;
+            for (int64_t v = 0; v < lp.n; ++v) cc[d.vc_off + v] = lp.c[v];
+            for (int64_t k = 0; k < lp.m; ++k) x0[d.m_off + k] = lp.x[k];
+        }
+        BHIP(hipMemcpyAsync(dev + s_dlp.off, dhost.data(), s_dlist.off - s_dlp.off, hipMemcpyHostToDevice,
+                            st));
+    }
 
     BArgs g;
     g.lp = (const BLp *)(dev + s_desc.off);
@@ -326,6 +364,45 @@ extern "C" int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts 
     BHIP(hipMemcpyAsync(host.data() + state0, dev + state0, download_end - state0,
                         hipMemcpyDeviceToHost, st));
     BHIP(hipStreamSynchronize(st));
+
+    // ---- duals of the LPs that ended OPTIMAL: one workgroup each, bucket by bucket
+    if (want_duals) {
+        const int *stat = (const int *)hp(s_status);
+        std::vector<int> dlist;
+        std::vector<int> dseg(kBuckets + 1, 0);
+        for (int b = 0; b < kBuckets; ++b) {
+            for (int i = 0; i < N; ++i)
+                if (stat[i] == DZG_OPTIMAL && bucket_of(lps[i].m) == b) dlist.push_back(i);
+            dseg[(size_t)b + 1] = (int)dlist.size();
+        }
+        if (!dlist.empty()) {
+            BHIP(hipMemcpyAsync(dev + s_dlist.off, dlist.data(), sizeof(int) * dlist.size(),
+                                hipMemcpyHostToDevice, st));
+            DzgDualsArgs a;
+            a.lp = (const DzgDualsLp *)(dev + s_dlp.off);
+            a.A = g.A;
+            a.var_col = g.var_col;
+            a.basis = g.basis;
+            a.nonbasis = g.nonbasis;
+            a.x = g.x;
+            a.z = g.z;
+            a.c = (const double *)(dev + s_c.off);
+            a.rhs0 = (const double *)(dev + s_x0.off);
+            a.y = (double *)(dev + s_y.off);
+            a.d = (double *)(dev + s_d.off);
+            a.scal = (double *)(dev + s_scal.off);
+            for (int b = 0; b < kBuckets; ++b) {
+                const int cnt = dseg[(size_t)b + 1] - dseg[(size_t)b];
+                if (cnt == 0) continue;
+                a.mmax = mmax[b];
+                dzg_launch_duals_small(b, a, (const int *)(dev + s_dlist.off) + dseg[(size_t)b], cnt, st);
+                BHIP(hipGetLastError());
+            }
+            BHIP(hipMemcpyAsync(dhost.data() + (s_y.off - s_dlp.off), dev + s_y.off, top - s_y.off,
+                                hipMemcpyDeviceToHost, st));
+            BHIP(hipStreamSynchronize(st));
+        }
+    }
 
     // ---- results
     const int *bs = (const int *)hp(s_basis), *nb = (const int *)hp(s_nonbasis);
@@ -383,6 +460,38 @@ extern "C" int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts 
         r.price_pass_used = 0;
         r.price_rows_copy = 0;
         r.state_drift = 0.0;
+        if (want_duals) {
+            dzg_duals &u = du[i];
+            if (r.status != DZG_OPTIMAL) {
+                dzg_duals_none(&u, r.objective);
+                continue;
+            }
+            u.reserved = 0;
+            u.primal_obj = r.objective;
+            const double *yv = (const double *)(dhost.data() + (s_y.off - s_dlp.off)) + d.m_off;
+            const double *dv = (const double *)(dhost.data() + (s_d.off - s_dlp.off)) + d.vc_off;
+            const double *sc = (const double *)(dhost.data() + (s_scal.off - s_dlp.off)) +
+                               (size_t)DZG_DUALS_SCAL * i;
+            u.source = DZG_DUALS_FRESH;
+            u.dual_obj = sc[0];
+            u.primal_infeas = sc[1];
+            u.dual_infeas = sc[2];
+            u.z_diff = sc[3] / std::max(1.0, sc[4]);
+            if (u.y && m) std::memcpy(u.y, yv, sizeof(double) * (size_t)m);
+            if (u.d && lp.n) std::memcpy(u.d, dv, sizeof(double) * (size_t)lp.n);
+        }
     }
     return 0;
+}
+
+extern "C" int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                               int64_t pivots_per_launch, dzg_result *res)
+{
+    return batch_solve(lps, count, opts, pivots_per_launch, res, nullptr, false);
+}
+
+extern "C" int dzg_batch_solve_duals(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                                     int64_t pivots_per_launch, dzg_result *res, dzg_duals *du)
+{
+    return batch_solve(lps, count, opts, pivots_per_launch, res, du, true);
 }

@@ -29,6 +29,7 @@
 // once with cbar).  tests/test_gpu_state.py checks the result against the state the basis defines,
 // computed in long double.
 #include "common.h"
+#include "duals.h"
 #include "fast_rows.h"
 
 // gathered copies of b and xbar0 in compact numbering (FTRAN's `ag`), zero-padded to even length
@@ -174,6 +175,17 @@ __global__ __launch_bounds__(256) void k_drift_z(const DzgDev d, const double *_
     }
 }
 
+// y = B^-T c_B with `cdev` as c (the three launches above); also what dzg_solver_duals computes its
+// dual vector with, on buffers of its own (duals.h)
+void dzg_launch_drift_y(const DzgDev &d, const double *cdev, double *part, double *y, int k_bound,
+                        hipStream_t st)
+{
+    const int kb = k_bound > 0 ? k_bound : 1;
+    hipLaunchKernelGGL(k_drift_y_part, dim3((kb + 255) / 256, DR_CHUNKS), dim3(256), 0, st, d, cdev, part);
+    hipLaunchKernelGGL(k_drift_y_sum, dim3((d.m + 2 + 255) / 256), dim3(256), 0, st, d, cdev, part, y);
+    hipLaunchKernelGGL(k_drift_y_slack, dim3((d.m + 255) / 256), dim3(256), 0, st, d, cdev, y);
+}
+
 #define DR_BLOCKS 256
 
 // Enqueues the whole measurement.  scratch: agb, agx [m + 2 each], part [DR_CHUNKS x ldw], y [m + 2],
@@ -192,9 +204,7 @@ void dzg_launch_drift(const DzgDev &d, const double *b0, const double *xb0, cons
     // z from c, then zbar from cbar: the same passes, one after the other on the same scratch
     for (int pass = 0; pass < 2; ++pass) {
         const double *cc = pass == 0 ? cdev : cbdev;
-        hipLaunchKernelGGL(k_drift_y_part, dim3((kb + 255) / 256, DR_CHUNKS), dim3(256), 0, st, d, cc, part);
-        hipLaunchKernelGGL(k_drift_y_sum, dim3((d.m + 2 + 255) / 256), dim3(256), 0, st, d, cc, part, y);
-        hipLaunchKernelGGL(k_drift_y_slack, dim3((d.m + 255) / 256), dim3(256), 0, st, d, cc, y);
+        dzg_launch_drift_y(d, cc, part, y, kb, st);
         // dzy = -N^T y over every nonbasic position, column-wise (the sums' order does not matter here)
         dzg_launch_price_raw(DZG_PRICE_TREE, d.m, d.lda, d.A, d.nbcode, d.q, y, dzy, st);
         hipLaunchKernelGGL(k_drift_z, dim3(DR_BLOCKS), dim3(256), 0, st, d, cc, dzy,

@@ -261,9 +261,81 @@ extern "C" int dzg_build_standard_form(const dzg_model *md, dzg_stdform *out)
     return 0;
 }
 
-extern "C" int dzg_model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res)
+int dzg_set_error(int code, const std::string &msg); // engine.hip
+int dzg_core_solve_with_duals(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du);
+
+// The one place that maps the standard form's dual vector to the user's model: user rows first,
+// then the bound rows by their tag (Built::row_tag).
+static void map_duals(const dzg_model *md, const Built &b, const double *y, dzg_model_duals *out)
+{
+    for (int64_t r = 0; r < md->ncons; ++r) out->con_dual[r] = y[r];
+    for (int64_t u = 0; u < md->nvars; ++u) {
+        if (out->lb_dual) out->lb_dual[u] = 0.0;
+        if (out->ub_dual) out->ub_dual[u] = 0.0;
+    }
+    for (int64_t r = md->ncons; r < b.m; ++r) {
+        const int64_t tag = b.row_tag[(size_t)r];
+        if (tag < 0) continue;
+        double *dst = (tag & 1) ? out->lb_dual : out->ub_dual;
+        if (dst) dst[tag / 2] = y[r];
+    }
+    if (!out->var_rc) return;
+    // var_rc[u] = c_u - sum_r a_{r,u} con_dual[r], rows ascending; a repeated variable keeps its
+    // last coefficient, in the objective and inside a row (assignment semantics of the builder)
+    std::vector<double> acc((size_t)(md->nvars ? md->nvars : 1), 0.0);
+    std::vector<int64_t> last((size_t)(md->nvars ? md->nvars : 1), -1);
+    for (int64_t r = 0; r < md->ncons; ++r) {
+        for (int64_t e = md->con_ptr[r]; e < md->con_ptr[r + 1]; ++e) last[(size_t)md->con_var[e]] = e;
+        for (int64_t e = md->con_ptr[r]; e < md->con_ptr[r + 1]; ++e) {
+            const int64_t u = md->con_var[e];
+            if (last[(size_t)u] != e) continue;
+            const double prod = md->con_coef[e] * y[r];
+            acc[(size_t)u] = acc[(size_t)u] + prod;
+        }
+    }
+    for (int64_t u = 0; u < md->nvars; ++u) {
+        const double cu = b.pos_var[(size_t)u] >= 0 ? b.c[(size_t)b.pos_var[(size_t)u]] : 0.0;
+        out->var_rc[u] = cu - acc[(size_t)u];
+    }
+}
+
+extern "C" int dzg_model_map_duals(const dzg_model *md, const double *y, int64_t m, dzg_model_duals *out)
+{
+    if (!out || !valid(md)) return dzg_set_error(DZG_E_ARG, "map duals: out is NULL or the model is malformed");
+    if (md->ncons > 0 && !out->con_dual) return dzg_set_error(DZG_E_ARG, "map duals: con_dual is NULL");
+    Built b;
+    build(md, b, true);
+    if (m != b.m || (m > 0 && !y))
+        return dzg_set_error(DZG_E_ARG, "map duals: y must hold the " + std::to_string(b.m) +
+                                            " rows of the model's standard form");
+    map_duals(md, b, y, out);
+    return 0;
+}
+
+void dzg_duals_none(dzg_duals *du, double objective); // engine.hip
+
+// What a solve's core duals (scalars, and y in `yv`) become in the caller's dzg_model_duals; the
+// caller's y / d pointers stay the caller's (d was filled in place).
+static void adopt_duals(const dzg_model *md, const Built &b, int status, double objective,
+                        const dzg_duals &core, const double *yv, dzg_model_duals *du)
+{
+    if (status != DZG_OPTIMAL || core.source == 0) {
+        dzg_duals_none(&du->core, objective);
+        return;
+    }
+    double *uy = du->core.y, *ud = du->core.d;
+    du->core = core;
+    du->core.y = uy;
+    du->core.d = ud;
+    if (uy && b.m) std::memcpy(uy, yv, sizeof(double) * (size_t)b.m);
+    map_duals(md, b, yv, du);
+}
+
+static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res,
+                       dzg_model_duals *du, bool want_duals)
 {
     if (!res || !valid(md)) return DZG_E_ARG;
+    if (want_duals && (!du || (md->ncons > 0 && !du->con_dual))) return DZG_E_ARG;
     Built b;
     build(md, b, true);
     res->m = b.m;
@@ -293,7 +365,15 @@ extern "C" int dzg_model_solve(const dzg_model *md, const dzg_opts *opts, dzg_mo
     std::memset(&r, 0, sizeof(r));
     r.basis = basis.data();
     r.x = x.data();
-    const int rc = dzg_core_solve(&lp, opts, &r); // AUTO: falls back to STRICT if FAST gives up
+    // AUTO: falls back to STRICT if FAST gives up; the duals are those of the solver whose result this is
+    std::vector<double> yv((size_t)(b.m ? b.m : 1), 0.0);
+    dzg_duals core;
+    std::memset(&core, 0, sizeof(core));
+    if (want_duals) {
+        core.y = yv.data();
+        core.d = du->core.d;
+    }
+    const int rc = dzg_core_solve_with_duals(&lp, opts, &r, want_duals ? &core : nullptr);
     res->status = rc < 0 ? rc : r.status;
     res->numerics_used = r.numerics_used;
     res->iterations = r.iterations;
@@ -302,21 +382,38 @@ extern "C" int dzg_model_solve(const dzg_model *md, const dzg_opts *opts, dzg_mo
     res->first_near_tie = r.first_near_tie;
     if (rc < 0) return rc;
     if (res->values) solution_values(md, b, basis.data(), x.data(), res->values);
+    if (want_duals) adopt_duals(md, b, r.status, r.objective, core, yv.data(), du);
     return r.status;
 }
 
-int dzg_set_error(int code, const std::string &msg); // engine.hip
+extern "C" int dzg_model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res)
+{
+    return model_solve(md, opts, res, nullptr, false);
+}
+
+extern "C" int dzg_model_solve_duals(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res,
+                                     dzg_model_duals *du)
+{
+    if (!du) return dzg_set_error(DZG_E_ARG, "model duals: du is NULL");
+    if (!res || !valid(md)) return dzg_set_error(DZG_E_ARG, "model duals: res is NULL or the model is malformed");
+    if (md->ncons > 0 && !du->con_dual) return dzg_set_error(DZG_E_ARG, "model duals: con_dual is NULL");
+    return model_solve(md, opts, res, du, true);
+}
 
 // The batch form of dzg_model_solve.  The routing rule lives here and only here: a model that
 // dzg_model_solve would solve in STRICT numerics (STRICT asked for, or AUTO at m <= auto_strict_rows)
 // on a dense block of at most DZG_BATCH_MAX_ROWS rows goes into one dzg_batch_solve call; every
 // other model goes through dzg_model_solve by itself.  The standard form and the values are
 // extracted exactly as dzg_model_solve extracts them.
-extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
-                                     dzg_model_result *res)
+static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                             dzg_model_result *res, dzg_model_duals *du, bool want_duals)
 {
     if (count < 0) return dzg_set_error(DZG_E_ARG, "model batch: count < 0");
     if (count > 0 && (!models || !res)) return dzg_set_error(DZG_E_ARG, "model batch: models or res is NULL");
+    if (count > 0 && want_duals && !du) return dzg_set_error(DZG_E_ARG, "model batch: du is NULL");
+    for (int64_t i = 0; want_duals && i < count; ++i)
+        if (models[i].ncons > 0 && !du[i].con_dual)
+            return dzg_set_error(DZG_E_ARG, "model batch: du[" + std::to_string(i) + "].con_dual is NULL");
     for (int64_t i = 0; i < count; ++i)
         if (!valid(&models[i]))
             return dzg_set_error(DZG_E_ARG, "model batch: models[" + std::to_string(i) + "] is malformed");
@@ -337,6 +434,8 @@ extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, con
     std::vector<dzg_result> rs(nb);
     std::vector<std::vector<int64_t>> basis(nb);
     std::vector<std::vector<double>> x(nb);
+    std::vector<std::vector<double>> yv(want_duals ? nb : 0);
+    std::vector<dzg_duals> cores(want_duals ? nb : 0);
     for (size_t k = 0; k < nb; ++k) {
         const Built &b = built[(size_t)batched[k]];
         dzg_lp &lp = lps[k];
@@ -358,9 +457,16 @@ extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, con
         std::memset(&rs[k], 0, sizeof(dzg_result));
         rs[k].basis = basis[k].data();
         rs[k].x = x[k].data();
+        if (want_duals) {
+            yv[k].assign((size_t)(b.m ? b.m : 1), 0.0);
+            std::memset(&cores[k], 0, sizeof(dzg_duals));
+            cores[k].y = yv[k].data();
+            cores[k].d = du[batched[k]].core.d;
+        }
     }
     if (nb > 0) {
-        const int rc = dzg_batch_solve(lps.data(), (int64_t)nb, &o, 0, rs.data());
+        const int rc = want_duals ? dzg_batch_solve_duals(lps.data(), (int64_t)nb, &o, 0, rs.data(), cores.data())
+                                  : dzg_batch_solve(lps.data(), (int64_t)nb, &o, 0, rs.data());
         if (rc < 0) return rc;
     }
     size_t k = 0;
@@ -378,11 +484,25 @@ extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, con
             out.near_ties = r.near_ties;
             out.first_near_tie = r.first_near_tie;
             if (out.values) solution_values(&models[i], b, basis[k].data(), x[k].data(), out.values);
+            if (want_duals)
+                adopt_duals(&models[i], b, r.status, r.objective, cores[k], yv[k].data(), &du[i]);
             ++k;
             continue;
         }
-        const int rc = dzg_model_solve(&models[i], opts, &out);
+        const int rc = model_solve(&models[i], opts, &out, want_duals ? &du[i] : nullptr, want_duals);
         if (rc < 0) return rc;
     }
     return 0;
+}
+
+extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                     dzg_model_result *res)
+{
+    return model_solve_batch(models, count, opts, res, nullptr, false);
+}
+
+extern "C" int dzg_model_solve_batch_duals(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                           dzg_model_result *res, dzg_model_duals *du)
+{
+    return model_solve_batch(models, count, opts, res, du, true);
 }

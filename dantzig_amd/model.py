@@ -218,8 +218,11 @@ class AffExpr(_Algebra):
 class Constraint:
     """One or two rows `linexpr <= b` (model.py:350-378)."""
 
-    def __init__(self, *, inequalities: list) -> None:
+    def __init__(self, *, inequalities: list, signs: "list | None" = None) -> None:
         self._inequalities = inequalities
+        # per row: +1 if it is the constraint's normal form `linexpr <= b` as written, -1 if negated
+        # (what Solution.dual turns the rows' dual values into the constraint's with)
+        self._signs = [1.0] * len(inequalities) if signs is None else signs
 
     @staticmethod
     def _row(linexpr: LinExpr, b: Number, negate: bool) -> rs.PyInequality:
@@ -233,11 +236,12 @@ class Constraint:
 
     @classmethod
     def greater_than_eq(cls, *, linexpr: LinExpr, b: Number) -> "Constraint":
-        return cls(inequalities=[cls._row(linexpr, b, True)])
+        return cls(inequalities=[cls._row(linexpr, b, True)], signs=[-1.0])
 
     @classmethod
     def equality(cls, *, linexpr: LinExpr, b: Number) -> "Constraint":
-        return cls(inequalities=[cls._row(linexpr, b, False), cls._row(linexpr, b, True)])
+        return cls(inequalities=[cls._row(linexpr, b, False), cls._row(linexpr, b, True)],
+                   signs=[1.0, -1.0])
 
     def rust_inequalities(self) -> list:
         return self._inequalities

@@ -2,10 +2,13 @@
 
 The core always maximises: Minimize negates the objective on the way in and the optimal value
 on the way out (optimize.py:114-117, :21-27).  A model with an integer variable is solved by
-branch and bound (rust.solve_mip); Solution.mip then reports the search in the user's sense."""
+branch and bound (rust.solve_mip); Solution.mip then reports the search in the user's sense.
+solve(duals=True) adds dual values, reduced costs and an optimality certificate, in the user's sense
+too: Solution.dual(constraint), Solution.reduced_cost(variable), Solution.certificate."""
 from __future__ import annotations
 
 import abc
+from dataclasses import dataclass
 from typing import Union
 
 from . import rust as rs
@@ -14,12 +17,66 @@ from .model import AffExpr, Constraint, LinExpr, Variable
 _SENSES = ("minimize", "maximize")
 
 
+@dataclass(frozen=True)
+class Certificate:
+    """The optimality certificate of one solve(duals=True), objectives in the user's sense.  source:
+    "fresh" (duals recomputed on the GPU from the final basis) or "carried" (read off the carried
+    reduced costs); gap = primal_objective - dual_objective; z_diff: how far the carried reduced
+    costs are from the recomputed ones, relative."""
+    source: str
+    primal_objective: float
+    dual_objective: float
+    gap: float
+    primal_infeasibility: float
+    dual_infeasibility: float
+    z_diff: float
+
+
 class Solution:
-    def __init__(self, *, solution: rs.PySolution, sense: str) -> None:
+    def __init__(self, *, solution: rs.PySolution, sense: str, constraints=None) -> None:
         if sense not in _SENSES:
             raise ValueError(f"sense is {sense!r}; a Solution is built for {_SENSES[0]!r} or {_SENSES[1]!r}")
         self._solution = solution
         self._sense = sense
+        # duals: the model's constraints (kept alive, found by identity) and the first row of each
+        self._rows: dict = {}
+        row = 0
+        for constraint in constraints or []:
+            self._rows.setdefault(id(constraint), (constraint, row))
+            row += len(constraint.rust_inequalities())
+
+    def _duals(self) -> "rs.PyDuals":
+        duals = getattr(self._solution, "duals", None)
+        if duals is None:
+            raise RuntimeError("this Solution carries no dual values: ask for them with solve(duals=True)")
+        return duals
+
+    def dual(self, constraint: Constraint) -> float:
+        """d objective_value / d b of `constraint` in its normal form linexpr <=, >= or == b."""
+        duals = self._duals()
+        entry = self._rows.get(id(constraint))
+        if entry is None:
+            raise KeyError("the constraint is not part of the solved model")
+        first = entry[1]
+        value = 0.0
+        for k, sign in enumerate(constraint._signs):
+            value += sign * duals.con_dual[first + k]
+        return -value if self._sense == "minimize" else value
+
+    def reduced_cost(self, variable: Variable) -> float:
+        """The objective coefficient of `variable` less its constraints' duals times its coefficients
+        (bound rows left out), in the user's sense."""
+        value = self._duals().var_rc[variable.to_rust_variable().id]
+        return -value if self._sense == "minimize" else value
+
+    @property
+    def certificate(self) -> Certificate:
+        duals = self._duals()
+        flip = -1.0 if self._sense == "minimize" else 1.0
+        primal, dual = flip * duals.primal_objective, flip * duals.dual_objective
+        return Certificate(source=duals.source, primal_objective=primal, dual_objective=dual,
+                           gap=primal - dual, primal_infeasibility=duals.primal_infeasibility,
+                           dual_infeasibility=duals.dual_infeasibility, z_diff=duals.z_diff)
 
     @property
     def objective_value(self) -> float:
@@ -75,11 +132,18 @@ class Optimize(abc.ABC):
     def _rust_problem(self):
         return self._core_objective().to_rust_affexpr(), list(self.yield_rust_inequalities())
 
-    def solve(self) -> Solution:
-        """Solve on the GPU.  Raises exceptions.UnboundedError / InfeasibleError."""
+    def solve(self, *, duals: bool = False) -> Solution:
+        """Solve on the GPU.  Raises exceptions.UnboundedError / InfeasibleError.  duals=True: the
+        Solution also answers dual(), reduced_cost() and certificate (LPs only: ValueError for a
+        model with an integer variable)."""
         objective, constraints = self._rust_problem()
         if rs._has_integer(objective, constraints):
+            if duals:
+                raise ValueError("duals=True: dual values are not defined for a model with integer variables")
             return Solution(solution=rs.solve_mip(objective, constraints), sense=self.sense)
+        if duals:
+            return Solution(solution=rs.solve(objective, constraints, duals=True), sense=self.sense,
+                            constraints=list(self.constraints))
         return Solution(solution=rs.solve(objective, constraints), sense=self.sense)
 
 
@@ -99,16 +163,18 @@ class Maximize(Optimize):
     sense = property(lambda self: "maximize")
 
 
-def solve_many(problems, *, return_exceptions: bool = False) -> list:
+def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False) -> list:
     """[p.solve() for p in problems] in one batched call (rust.solve_many): the small models share
     one launch on the GPU, one workgroup per model, bit for bit what p.solve() returns.  A model
     that is unbounded or infeasible raises the exception p.solve() raises, with the model's index
     in the message, after the whole batch is done; with return_exceptions=True the exception
-    instance stands in that model's place."""
+    instance stands in that model's place.  duals=True: every Solution is p.solve(duals=True)'s."""
     problems = list(problems)
     for i, p in enumerate(problems):
         if not isinstance(p, Optimize):
             raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
-    raw = rs.solve_many([p._rust_problem() for p in problems], return_exceptions=return_exceptions)
-    return [r if isinstance(r, Exception) else Solution(solution=r, sense=p.sense)
+    raw = rs.solve_many([p._rust_problem() for p in problems], duals=duals,
+                        return_exceptions=return_exceptions)
+    return [r if isinstance(r, Exception)
+            else Solution(solution=r, sense=p.sense, constraints=list(p.constraints) if duals else None)
             for p, r in zip(problems, raw)]

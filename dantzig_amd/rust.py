@@ -174,17 +174,32 @@ class MipInfo:
                 f"lp_iterations={self.lp_iterations}, best_bound={self.best_bound}, gap={self.gap})")
 
 
+class PyDuals:
+    """Duals of one solve(..., duals=True), in the core sense (the model is maximised, every row
+    is linexpr <= b): con_dual[r] the dual value of inequality r in the order they were passed,
+    var_rc / lb_dual / ub_dual keyed by Variable.id (dzg_model_map_duals), and the certificate
+    scalars of dzg_duals with their source, "fresh" or "carried"."""
+    __slots__ = ("source", "con_dual", "var_rc", "lb_dual", "ub_dual", "primal_objective",
+                 "dual_objective", "primal_infeasibility", "dual_infeasibility", "z_diff")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
 class PySolution:
-    __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape", "mip")
+    __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape", "mip", "duals")
 
     def __init__(self, objective_value: float, values: dict, iterations: int = 0,
-                 numerics: str = "", shape=(0, 0), mip: "MipInfo | None" = None):
+                 numerics: str = "", shape=(0, 0), mip: "MipInfo | None" = None,
+                 duals: "PyDuals | None" = None):
         self._objective_value = objective_value
         self._values = values
         self.iterations = iterations    # extras the reference does not expose
         self.numerics = numerics
         self.shape = shape
         self.mip = mip                  # None for an LP
+        self.duals = duals              # None unless solve(..., duals=True)
 
     objective_value = property(lambda self: self._objective_value)
 
@@ -236,6 +251,32 @@ def _c_model(a: dict) -> _ffi.Model:
                       a["ncons"], p(a["con_ptr"]), p(a["con_var"]), p(a["con_coef"]), p(a["con_b"]))
 
 
+class _DualBuffers:
+    """The caller-owned arrays of one dzg_model_duals and the struct that points at them."""
+
+    def __init__(self, arrays: dict):
+        nv, nc = arrays["nvars"], arrays["ncons"]
+        self.con_dual, self.var_rc = np.zeros(max(nc, 1)), np.zeros(max(nv, 1))
+        self.lb_dual, self.ub_dual = np.zeros(max(nv, 1)), np.zeros(max(nv, 1))
+        self.ncons = nc
+
+    def fill(self, c: "_ffi.ModelDuals") -> None:
+        c.con_dual, c.var_rc = _ffi.ptr(self.con_dual), _ffi.ptr(self.var_rc)
+        c.lb_dual, c.ub_dual = _ffi.ptr(self.lb_dual), _ffi.ptr(self.ub_dual)
+
+    def pyduals(self, c: "_ffi.ModelDuals", order) -> "PyDuals | None":
+        core = c.core
+        if core.source == 0:
+            return None
+        by_id = lambda a: {v.id: float(a[i]) for i, v in enumerate(order)}  # noqa: E731
+        return PyDuals(source=_ffi.DUALS_SOURCE_NAMES[int(core.source)],
+                       con_dual=[float(v) for v in self.con_dual[:self.ncons]],
+                       var_rc=by_id(self.var_rc), lb_dual=by_id(self.lb_dual), ub_dual=by_id(self.ub_dual),
+                       primal_objective=float(core.primal_obj), dual_objective=float(core.dual_obj),
+                       primal_infeasibility=float(core.primal_infeas),
+                       dual_infeasibility=float(core.dual_infeas), z_diff=float(core.z_diff))
+
+
 def _outcome(res, values, order, where: str = "", stacklevel: int = 4):
     """The PySolution of one dzg_model_result, or the exception the reference raises for it."""
     rc = int(res.status)
@@ -259,22 +300,34 @@ def _outcome(res, values, order, where: str = "", stacklevel: int = 4):
                       (int(res.m), int(res.n)))
 
 
-def solve(objective: PyAffExpr, constraints) -> PySolution:
-    """Maximise `objective` subject to `constraints` on the GPU (src/lib.rs:16-27)."""
+def solve(objective: PyAffExpr, constraints, duals: bool = False) -> PySolution:
+    """Maximise `objective` subject to `constraints` on the GPU (src/lib.rs:16-27).  duals=True
+    (dzg_model_solve_duals): the same solution with .duals, a PyDuals."""
     if not isinstance(objective, PyAffExpr):
         raise TypeError("objective must be a PyAffExpr")
-    arrays, order = lower(objective, list(constraints))
+    constraints = list(constraints)
+    if duals and _has_integer(objective, constraints):
+        raise ValueError("duals=True: dual values are not defined for a model with integer variables")
+    arrays, order = lower(objective, constraints)
     _ffi.require_gpu()
     values = np.zeros(max(len(order), 1))
     res = _ffi.ModelResult()
     res.values = _ffi.ptr(values)
     opts = _ffi.default_opts(**_options)
     md = _c_model(arrays)
-    rc = _ffi.lib().dzg_model_solve(C.byref(md), C.byref(opts), C.byref(res))
-    _ffi.check(rc, "dzg_model_solve")
+    if duals:
+        buf, cdu = _DualBuffers(arrays), _ffi.ModelDuals()
+        buf.fill(cdu)
+        rc = _ffi.lib().dzg_model_solve_duals(C.byref(md), C.byref(opts), C.byref(res), C.byref(cdu))
+        _ffi.check(rc, "dzg_model_solve_duals")
+    else:
+        rc = _ffi.lib().dzg_model_solve(C.byref(md), C.byref(opts), C.byref(res))
+        _ffi.check(rc, "dzg_model_solve")
     out = _outcome(res, values, order)
     if isinstance(out, Exception):
         raise out
+    if duals:
+        out.duals = buf.pyduals(cdu, order)
     return out
 
 
@@ -359,19 +412,24 @@ def solve_mip(objective: PyAffExpr, constraints, *, node_log: int = 0, **mip_opt
     return out
 
 
-def solve_many(problems, *, return_exceptions: bool = False) -> list:
+def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False) -> list:
     """solve() for every (objective, constraints) pair of `problems`, in one dzg_model_solve_batch
     call: the models that solve() would run in STRICT numerics on at most 128 rows share one batch
     on the GPU (one workgroup per model), the others are solved one at a time.  Results keep the
     order of `problems` and equal solve()'s one for one.  A model that ends unbounded or infeasible
     raises solve()'s exception, its index in the message, once the whole batch is done; with
     return_exceptions=True the exception instance stands in that model's place instead.  Models with
-    an integer variable are solved one by one through solve_mip(), after the batch."""
+    an integer variable are solved one by one through solve_mip(), after the batch.  duals=True
+    (dzg_model_solve_batch_duals): every solution carries .duals as solve(..., duals=True) gives
+    it; a model with an integer variable is then a ValueError."""
     problems = [(objective, list(constraints)) for objective, constraints in problems]
     for i, (objective, _) in enumerate(problems):
         if not isinstance(objective, PyAffExpr):
             raise TypeError(f"problems[{i}]: objective must be a PyAffExpr")
     mip = [_has_integer(objective, constraints) for objective, constraints in problems]
+    if duals and any(mip):
+        raise ValueError(f"problems[{mip.index(True)}]: duals=True: dual values are not defined for a "
+                         "model with integer variables")
     lp_idx = [i for i in range(len(problems)) if not mip[i]]
     out: list = [None] * len(problems)
     lowered = [lower(*problems[i]) for i in lp_idx]
@@ -382,10 +440,20 @@ def solve_many(problems, *, return_exceptions: bool = False) -> list:
     for i, (_, values) in enumerate(keep):
         results[i].values = _ffi.ptr(values)
     opts = _ffi.default_opts(**_options)
-    rc = _ffi.lib().dzg_model_solve_batch(models, C.c_int64(count), C.byref(opts), results)
-    _ffi.check(rc, "dzg_model_solve_batch")
+    if duals:
+        bufs = [_DualBuffers(arrays) for arrays, _ in lowered]
+        cdu = (_ffi.ModelDuals * max(count, 1))()
+        for k, buf in enumerate(bufs):
+            buf.fill(cdu[k])
+        rc = _ffi.lib().dzg_model_solve_batch_duals(models, C.c_int64(count), C.byref(opts), results, cdu)
+        _ffi.check(rc, "dzg_model_solve_batch_duals")
+    else:
+        rc = _ffi.lib().dzg_model_solve_batch(models, C.c_int64(count), C.byref(opts), results)
+        _ffi.check(rc, "dzg_model_solve_batch")
     for k, i in enumerate(lp_idx):
         out[i] = _outcome(results[k], keep[k][1], lowered[k][1], f" (model {i})", stacklevel=3)
+        if duals and not isinstance(out[i], Exception):
+            out[i].duals = bufs[k].pyduals(cdu[k], lowered[k][1])
     for i in range(len(problems)):
         if mip[i]:
             arrays, order = lower(*problems[i])

@@ -380,6 +380,66 @@ int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
 int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
                           dzg_model_result *res);
 
+/* ---- Dual values and reduced costs at the optimum (csrc/k_duals.hip) ------------------ */
+
+/* In the core sense (maximise c.x + constant, [A | I] x = rhs, x >= 0), at an OPTIMAL basis B with
+ * nonbasic set N:
+ *   y = B^-T c_B                   the dual value of every row (m entries)
+ *   d[j] = a_j . y - c[j]          the reduced cost of nonbasic variable j (for the slack of row i
+ *                                  that is y[i]); exactly 0.0 for a basic variable (n entries)
+ *   primal_obj                     the solver's objective
+ *   dual_obj = constant + sum_i rhs0[i] * y[i]     (rhs0: the x the solve started with)
+ *   primal_infeas = max(0, -min x) over the carried x,   dual_infeas = max(0, -min_j d[j])
+ *   z_diff = |z_carried - d_N|_inf / max(1, |d_N|_inf)
+ * source DZG_DUALS_FRESH: y and d were recomputed on the device from the final basis -- STRICT: the
+ * reference's LU::solve of B^T y = c_B and its neg_t_dot, bit for bit, dual_obj summed over ascending
+ * rows; FAST: from a fresh refactorisation of the basis, deterministic, dual_obj summed in chunks.
+ * source DZG_DUALS_CARRIED (CSC storage, column- or row-sharded solvers): no device work, y[i] is
+ * the carried z of row i's slack where it is nonbasic and 0 otherwise, d the carried z by
+ * variable, dual_obj follows from that y, z_diff = 0. */
+#define DZG_DUALS_FRESH 1
+#define DZG_DUALS_CARRIED 2
+typedef struct {
+    int32_t source;      /* DZG_DUALS_FRESH / DZG_DUALS_CARRIED; 0: none (the LP did not end OPTIMAL) */
+    int32_t reserved;
+    double *y;           /* m, optional: NULL = not wanted                                      */
+    double *d;           /* n, optional                                                         */
+    double primal_obj, dual_obj, primal_infeas, dual_infeas, z_diff;
+} dzg_duals;
+
+/* The solver's status must be DZG_OPTIMAL, else DZG_E_ARG.  A FAST solver (dense, one GPU)
+ * refactorises its final basis for this, like dzg_solver_refactor (refactors and state_drift move
+ * accordingly), and needs the workspace of opts.refactor_interval != 0, else DZG_E_ARG.  The carried
+ * x, xbar, z, zbar, the basis, the objective and the pivot count are not touched; two calls on the
+ * same state return the same bits. */
+int dzg_solver_duals(dzg_solver *s, dzg_duals *out);
+/* dzg_batch_solve, then k_duals_small over the LPs that ended OPTIMAL, in the same device
+ * allocation; du[i].source = 0 for the others.  res[] is what dzg_batch_solve fills, bit for bit. */
+int dzg_batch_solve_duals(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                          int64_t pivots_per_launch, dzg_result *res, dzg_duals *du);
+
+/* The duals in terms of the user's model (still the core sense: the model is maximised, rows are
+ * coef.x <= b):  con_dual[r] = y[r] of user row r;  ub_dual[u] / lb_dual[u] = y of the bound rows
+ * Simplex::new appends after the user rows (ub before lb per variable, in order of first
+ * appearance), 0 where the bound is absent;  var_rc[u] = c_u - sum_r a_{r,u} con_dual[r] over the
+ * user rows in row order (c_u: the objective's coefficient, the last one if u is repeated). */
+typedef struct {
+    double *con_dual;                    /* ncons                                              */
+    double *var_rc, *lb_dual, *ub_dual;  /* nvars, optional                                    */
+    dzg_duals core;                      /* scalars and source; y / d optional, sized by res->m / res->n */
+} dzg_model_duals;
+/* dzg_model_solve / dzg_model_solve_batch with the duals of whichever solver produced the result
+ * (res and the return value are exactly what those give); core.source = 0 unless the status is
+ * DZG_OPTIMAL, and also when the duals of an OPTIMAL solve could not be computed (the final basis of
+ * a FAST run did not refactorise: dzg_last_error says so) -- the solve's outcome stands. */
+int dzg_model_solve_duals(const dzg_model *model, const dzg_opts *opts, dzg_model_result *res,
+                          dzg_model_duals *du);
+int dzg_model_solve_batch_duals(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                dzg_model_result *res, dzg_model_duals *du);
+/* Host only: fills con_dual and the optional var_rc / lb_dual / ub_dual of `out` from y[0..m), m the
+ * rows of the model's standard form (DZG_E_ARG otherwise). */
+int dzg_model_map_duals(const dzg_model *model, const double *y, int64_t m, dzg_model_duals *out);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
