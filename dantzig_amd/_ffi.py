@@ -42,6 +42,8 @@ EXPORTS = [
     "dzg_mip_solve", "dzg_mip_last_warm_stats", "dzg_debug_cand_reduce",
     "dzg_solver_duals", "dzg_batch_solve_duals", "dzg_model_solve_duals",
     "dzg_model_solve_batch_duals", "dzg_model_map_duals",
+    "dzg_solver_ranging", "dzg_batch_solve_ranging", "dzg_model_solve_ranging",
+    "dzg_model_solve_batch_ranging",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -120,6 +122,23 @@ class Duals(C.Structure):
 class ModelDuals(C.Structure):
     _fields_ = [("con_dual", C.c_void_p), ("var_rc", C.c_void_p), ("lb_dual", C.c_void_p),
                 ("ub_dual", C.c_void_p), ("core", Duals)]
+
+
+class RangingReq(C.Structure):
+    _fields_ = [("ncost", C.c_int64), ("cost_ptr", C.c_void_p), ("cost_idx", C.c_void_p),
+                ("cost_val", C.c_void_p), ("nrhs", C.c_int64), ("rhs_ptr", C.c_void_p),
+                ("rhs_idx", C.c_void_p), ("rhs_val", C.c_void_p), ("pivot_tol", C.c_double)]
+
+
+class Ranging(C.Structure):
+    _fields_ = [("cost_lo", C.c_void_p), ("cost_hi", C.c_void_p), ("cost_lo_var", C.c_void_p),
+                ("cost_hi_var", C.c_void_p), ("rhs_lo", C.c_void_p), ("rhs_hi", C.c_void_p),
+                ("rhs_lo_var", C.c_void_p), ("rhs_hi_var", C.c_void_p)]
+
+
+class ModelRangingReq(C.Structure):
+    _fields_ = [("nvar", C.c_int64), ("var", C.c_void_p), ("nrow", C.c_int64), ("row_ptr", C.c_void_p),
+                ("row_idx", C.c_void_p), ("row_coef", C.c_void_p), ("pivot_tol", C.c_double)]
 
 
 class StdForm(C.Structure):
@@ -227,6 +246,13 @@ def lib() -> C.CDLL:
         _lib.dzg_model_solve_batch_duals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]
         _lib.dzg_model_map_duals.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.dzg_solver_ranging.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_solve_ranging.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_model_solve_ranging.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]
+        _lib.dzg_model_solve_batch_ranging.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_mip_opts_default.restype = None
         _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -259,6 +285,57 @@ def check(rc: int, what: str) -> int:
         msg = lib().dzg_last_error().decode()
         raise DantzigAmdError(f"{what}: {status_str(rc)} ({msg})")
     return rc
+
+
+class RangingBuffers:
+    """One dzg_ranging_req / dzg_ranging pair and the arrays they point at.  cost_dirs / rhs_dirs:
+    lists of {index: coefficient}."""
+
+    def __init__(self, cost_dirs, rhs_dirs, pivot_tol: float = 0.0):
+        def csr(dirs):
+            ptr_, idx, val = [0], [], []
+            for d in dirs:
+                for j, v in d.items():
+                    idx.append(int(j))
+                    val.append(float(v))
+                ptr_.append(len(idx))
+            return i64(ptr_), i64(idx + [0]), f64(val + [0.0])
+
+        self.nc, self.nr = len(cost_dirs), len(rhs_dirs)
+        self.cost = csr(cost_dirs)
+        self.rhs = csr(rhs_dirs)
+        self.pivot_tol = float(pivot_tol)
+        self.lo = [np.zeros(max(self.nc, 1)), np.zeros(max(self.nr, 1))]
+        self.hi = [np.zeros(max(self.nc, 1)), np.zeros(max(self.nr, 1))]
+        self.lo_var = [np.zeros(max(self.nc, 1), dtype=np.int64), np.zeros(max(self.nr, 1), dtype=np.int64)]
+        self.hi_var = [np.zeros(max(self.nc, 1), dtype=np.int64), np.zeros(max(self.nr, 1), dtype=np.int64)]
+
+    def fill(self, req: RangingReq, out: Ranging) -> None:
+        req.ncost, req.nrhs, req.pivot_tol = self.nc, self.nr, self.pivot_tol
+        req.cost_ptr, req.cost_idx, req.cost_val = (ptr(a) for a in self.cost)
+        req.rhs_ptr, req.rhs_idx, req.rhs_val = (ptr(a) for a in self.rhs)
+        self.fill_out(out)
+
+    def fill_out(self, out: Ranging) -> None:
+        out.cost_lo, out.cost_hi = ptr(self.lo[0]), ptr(self.hi[0])
+        out.cost_lo_var, out.cost_hi_var = ptr(self.lo_var[0]), ptr(self.hi_var[0])
+        out.rhs_lo, out.rhs_hi = ptr(self.lo[1]), ptr(self.hi[1])
+        out.rhs_lo_var, out.rhs_hi_var = ptr(self.lo_var[1]), ptr(self.hi_var[1])
+
+    def side(self, which: int):
+        """(lo, hi, lo_var, hi_var) of the cost (0) or right-hand-side (1) directions."""
+        n = self.nc if which == 0 else self.nr
+        return (self.lo[which][:n].copy(), self.hi[which][:n].copy(), self.lo_var[which][:n].copy(),
+                self.hi_var[which][:n].copy())
+
+
+def check_ranging(rc: int, what: str) -> int:
+    """check(), but a route without ranging (the C call says so) is a NotImplementedError."""
+    if rc < 0:
+        msg = lib().dzg_last_error().decode()
+        if "ranging is not supported" in msg:
+            raise NotImplementedError(f"{what}: {msg}")
+    return check(rc, what)
 
 
 def default_opts(**kw) -> Opts:

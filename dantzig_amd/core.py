@@ -155,6 +155,7 @@ class CoreResult:
     price_rows_copy: int = 0            # 1: the row-major copy of the matrix is resident
     state_drift: float = 0.0            # carried x, xbar, z, zbar vs the fresh inverse at the last refactorisation
     duals: "CoreDuals | None" = None    # solve_batch(duals=True): the LP's duals if it ended optimal
+    ranging: "CoreRanging | None" = None  # solve_batch(ranging=...): the LP's ranges if it ended optimal
 
 
 @dataclass
@@ -171,6 +172,36 @@ class CoreDuals:
     primal_infeas: float
     dual_infeas: float
     z_diff: float
+
+
+@dataclass
+class CoreRanging:
+    """Sensitivity ranges at an optimal basis, core sense (dzg_ranging): per requested cost direction
+    and per requested right-hand-side direction the interval [lo, hi] of the step t over which the
+    basis stays optimal (0 is always inside; -inf / +inf where nothing blocks) and the variable that
+    blocks each end (-1: none).  duals: the CoreDuals of the same call."""
+    cost_lo: np.ndarray
+    cost_hi: np.ndarray
+    cost_lo_var: np.ndarray
+    cost_hi_var: np.ndarray
+    rhs_lo: np.ndarray
+    rhs_hi: np.ndarray
+    rhs_lo_var: np.ndarray
+    rhs_hi_var: np.ndarray
+    duals: "CoreDuals | None" = None
+
+
+def _core_ranging(buf: "_ffi.RangingBuffers", duals=None) -> CoreRanging:
+    c, r = buf.side(0), buf.side(1)
+    return CoreRanging(cost_lo=c[0], cost_hi=c[1], cost_lo_var=c[2], cost_hi_var=c[3],
+                       rhs_lo=r[0], rhs_hi=r[1], rhs_lo_var=r[2], rhs_hi_var=r[3], duals=duals)
+
+
+def _ranging_dirs(dirs, count: int) -> list:
+    """None: every index's own unit direction; otherwise a list of {index: coefficient}."""
+    if dirs is None:
+        return [{j: 1.0} for j in range(count)]
+    return [dict(d) for d in dirs]
 
 
 def _core_duals(u, y, d) -> CoreDuals:
@@ -294,6 +325,23 @@ class Solver:
         _ffi.check(_ffi.lib().dzg_solver_duals(self._h, C.byref(u)), "dzg_solver_duals")
         return _core_duals(u, y[:m].copy(), d[:n].copy())
 
+    def ranging(self, cost_dirs=None, rhs_dirs=None, pivot_tol: float = 0.0) -> CoreRanging:
+        """dzg_solver_ranging: how far each cost direction (a {variable: coefficient} dict; None: every
+        variable's own coefficient) and each right-hand-side direction ({row: coefficient}; None:
+        every row's own right-hand side) can be followed before the OPTIMAL basis this solver ended
+        on changes.  Runs duals() first, with its preconditions and side effects; `.duals` of the
+        result is that call's.  CSC and sharded solvers: NotImplementedError."""
+        m, n = self._lp.m, self._lp.n
+        buf = _ffi.RangingBuffers(_ranging_dirs(cost_dirs, n), _ranging_dirs(rhs_dirs, m), pivot_tol)
+        req, out = _ffi.RangingReq(), _ffi.Ranging()
+        buf.fill(req, out)
+        y, d = np.zeros(max(m, 1)), np.zeros(max(n, 1))
+        u = _ffi.Duals()
+        u.y, u.d = ptr(y), ptr(d)
+        _ffi.check_ranging(_ffi.lib().dzg_solver_ranging(self._h, C.byref(req), C.byref(u), C.byref(out)),
+                           "dzg_solver_ranging")
+        return _core_ranging(buf, _core_duals(u, y[:m].copy(), d[:n].copy()))
+
     def debug_inverse(self, row0: int, row1: int) -> tuple[np.ndarray, dict]:
         """Test hook (dzg_debug_basis_inverse): rows [row0, row1) of the basis inverse FAST keeps --
         row i is basis position row0 + i, column r constraint row r -- and
@@ -364,7 +412,7 @@ _PIVOT_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("entering", "<i8
 
 
 def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
-                duals: bool = False, **opts) -> list:
+                duals: bool = False, ranging=False, pivot_tol: float = 0.0, **opts) -> list:
     """dzg_batch_solve: every LP of `lps` in STRICT numerics, one workgroup per LP, in one call.
 
     The whole batch is checked on the host first (ValueError: more than 128 rows, CSC input, FAST
@@ -372,7 +420,10 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
     before that.  Result i is LP i's CoreResult, as `solve(lp, numerics=STRICT)` reports it; its
     solve_ms is the wall time of the whole batch call.  A result resumes through resumed_from, in a
     batch or in a single Solver.  duals=True (dzg_batch_solve_duals): every result gains `.duals`, a
-    CoreDuals for an LP that ended optimal and None otherwise."""
+    CoreDuals for an LP that ended optimal and None otherwise.  ranging=True, or one request per LP
+    as (cost_dirs, rhs_dirs) with the meaning of Solver.ranging (dzg_batch_solve_ranging): every
+    result gains `.ranging`, a CoreRanging, and `.duals` as well; None for an LP that did not end
+    optimal."""
     import time
 
     lps = list(lps)
@@ -409,6 +460,17 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         r.log = logs.ctypes.data + logs.strides[0] * i if cap > 0 else None
         r.log_cap = cap
     o = _ffi.default_opts(**opts)
+    want_ranging = ranging is not False and ranging is not None
+    if want_ranging:
+        duals = True
+        reqs = [(None, None)] * count if ranging is True else list(ranging)
+        if len(reqs) != count:
+            raise ValueError("ranging: one (cost_dirs, rhs_dirs) request per LP")
+        bufs = [_ffi.RangingBuffers(_ranging_dirs(cd, lp.n), _ranging_dirs(rd, lp.m), pivot_tol)
+                for (cd, rd), lp in zip(reqs, lps)]
+        c_req, c_rg = (_ffi.RangingReq * max(count, 1))(), (_ffi.Ranging * max(count, 1))()
+        for i, buf in enumerate(bufs):
+            buf.fill(c_req[i], c_rg[i])
     if duals:
         ns = [lp.n for lp in lps]
         no = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
@@ -418,14 +480,18 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
             du[i].y = y_all.ctypes.data + 8 * int(mo[i])
             du[i].d = d_all.ctypes.data + 8 * int(no[i])
     t0 = time.perf_counter()
-    if duals:
+    if want_ranging:
+        rc = _ffi.lib().dzg_batch_solve_ranging(c_lps, C.c_int64(count), C.byref(o),
+                                                C.c_int64(int(pivots_per_launch)), c_req, res, du, c_rg)
+    elif duals:
         rc = _ffi.lib().dzg_batch_solve_duals(c_lps, C.c_int64(count), C.byref(o),
                                               C.c_int64(int(pivots_per_launch)), res, du)
     else:
         rc = _ffi.lib().dzg_batch_solve(c_lps, C.c_int64(count), C.byref(o),
                                         C.c_int64(int(pivots_per_launch)), res)
     wall_ms = (time.perf_counter() - t0) * 1e3
-    _ffi.check(rc, "dzg_batch_solve_duals" if duals else "dzg_batch_solve")
+    _ffi.check_ranging(rc, "dzg_batch_solve_ranging" if want_ranging else
+                       ("dzg_batch_solve_duals" if duals else "dzg_batch_solve"))
     out = []
     for i in range(count):
         r = res[i]
@@ -443,6 +509,8 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         if duals:
             out[-1].duals = None if du[i].source == 0 else _core_duals(
                 du[i], y_all[a0:a1].copy(), d_all[int(no[i]):int(no[i + 1])].copy())
+        if want_ranging and out[-1].duals is not None:
+            out[-1].ranging = _core_ranging(bufs[i], out[-1].duals)
     return out
 
 

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "duals.h"
+#include "ranging.h"
 
 static thread_local std::string g_err;
 
@@ -2345,21 +2346,281 @@ void dzg_duals_none(dzg_duals *du, double objective)
     du->dual_obj = du->primal_infeas = du->dual_infeas = du->z_diff = 0.0;
 }
 
-// (status, result and, when `du` is given and the LP ended OPTIMAL, the duals of this solver)
-static int finish_solver(dzg_solver *s, int rc, dzg_result *res, dzg_duals *du)
+// ---- sensitivity ranging at the optimum (k_ranging.hip) ----------------------
+static bool ranging_side_valid(const char *name, int64_t count, const int64_t *ptr, const int64_t *idx,
+                               const double *val, int64_t bound, std::vector<int64_t> &mark, std::string &why)
+{
+    const std::string at = std::string("ranging: ") + name;
+    if (count < 0) { why = at + " count < 0"; return false; }
+    if (count == 0) return true;
+    if (count >= (1ll << 31) - 64) { why = at + " count out of range"; return false; }
+    if (!ptr) { why = at + "_ptr is NULL"; return false; }
+    if (ptr[0] != 0) { why = at + "_ptr[0] != 0"; return false; }
+    for (int64_t i = 0; i < count; ++i)
+        if (ptr[i + 1] < ptr[i]) { why = at + "_ptr decreases"; return false; }
+    if (ptr[count] > 0 && (!idx || !val)) { why = at + "_idx or " + name + "_val is NULL"; return false; }
+    mark.assign((size_t)(bound > 0 ? bound : 1), -1);
+    for (int64_t i = 0; i < count; ++i)
+        for (int64_t e = ptr[i]; e < ptr[i + 1]; ++e) {
+            const int64_t j = idx[e];
+            if (j < 0 || j >= bound) {
+                why = at + " direction " + std::to_string(i) + ": index " + std::to_string(j) + " out of range";
+                return false;
+            }
+            if (mark[(size_t)j] == i) {
+                why = at + " direction " + std::to_string(i) + ": index " + std::to_string(j) + " is repeated";
+                return false;
+            }
+            mark[(size_t)j] = i;
+        }
+    return true;
+}
+
+bool dzg_ranging_req_valid(const dzg_ranging_req *req, int64_t m, int64_t n, std::string &why)
+{
+    if (!req) { why = "ranging: req is NULL"; return false; }
+    if (!(req->pivot_tol >= 0.0)) { why = "ranging: pivot_tol is negative or NaN"; return false; }
+    std::vector<int64_t> mark;
+    return ranging_side_valid("cost", req->ncost, req->cost_ptr, req->cost_idx, req->cost_val, n, mark, why) &&
+           ranging_side_valid("rhs", req->nrhs, req->rhs_ptr, req->rhs_idx, req->rhs_val, m, mark, why);
+}
+
+void dzg_ranging_none(const dzg_ranging_req *req, dzg_ranging *rg)
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int64_t i = 0; i < req->ncost; ++i) {
+        if (rg->cost_lo) rg->cost_lo[i] = nan;
+        if (rg->cost_hi) rg->cost_hi[i] = nan;
+        if (rg->cost_lo_var) rg->cost_lo_var[i] = -1;
+        if (rg->cost_hi_var) rg->cost_hi_var[i] = -1;
+    }
+    for (int64_t i = 0; i < req->nrhs; ++i) {
+        if (rg->rhs_lo) rg->rhs_lo[i] = nan;
+        if (rg->rhs_hi) rg->rhs_hi[i] = nan;
+        if (rg->rhs_lo_var) rg->rhs_lo_var[i] = -1;
+        if (rg->rhs_hi_var) rg->rhs_hi_var[i] = -1;
+    }
+}
+
+namespace {
+// device memory of one dzg_solver_ranging call
+struct RangeArena {
+    std::vector<void *> ptrs;
+    ~RangeArena()
+    {
+        for (void *p : ptrs) (void)hipFree(p);
+    }
+    template <typename T> int get(T **p, size_t count)
+    {
+        void *q = nullptr;
+        const size_t bytes = sizeof(T) * (count ? count : 1);
+        if (hipMalloc(&q, bytes) != hipSuccess)
+            return fail(DZG_E_NOMEM, "ranging: hipMalloc of " + std::to_string(bytes) + " bytes failed");
+        ptrs.push_back(q);
+        *p = static_cast<T *>(q);
+        return 0;
+    }
+    template <typename T> int put(T **p, const std::vector<T> &h, hipStream_t st)
+    {
+        TRY(get(p, h.size()));
+        if (!h.empty())
+            HIP_OK(hipMemcpyAsync(*p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice, st));
+        return 0;
+    }
+};
+} // namespace
+
+extern "C" int dzg_solver_ranging(dzg_solver *s, const dzg_ranging_req *req, dzg_duals *duals,
+                                  dzg_ranging *out)
+{
+    if (!s || !req || !out) return fail(DZG_E_ARG, "ranging: NULL argument");
+    HIP_OK(hipSetDevice(s->opts.device));
+    const DzgDev &d = s->d;
+    const int m = d.m, q = d.q, n = d.n;
+    std::string why;
+    if (!dzg_ranging_req_valid(req, m, n, why)) return fail(DZG_E_ARG, why);
+    TRY(read_ctl(s));
+    if (s->h_ctl->status != DZG_OPTIMAL)
+        return fail(DZG_E_ARG, "ranging: the solver's status is not DZG_OPTIMAL");
+    if (d.csc || d.world > 1)
+        return fail(DZG_E_ARG, "ranging is not supported on CSC storage or sharded solvers: a range cannot "
+                               "be read off the carried z");
+    dzg_duals tmp;
+    std::memset(&tmp, 0, sizeof(tmp));
+    TRY(dzg_solver_duals(s, duals ? duals : &tmp)); // leaves the fresh d by variable in s->du_d
+    const double tol = req->pivot_tol == 0.0 ? 1e-9 : req->pivot_tol;
+    const int nc = (int)req->ncost, nr = (int)req->nrhs;
+    hipStream_t st = s->st;
+
+    std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1));
+    if (m) HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
+    if (q) HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
+    std::vector<int> where((size_t)(n ? n : 1), 0); // variable -> basis position p, or -1 - nonbasic position
+    for (int p = 0; p < m; ++p) where[(size_t)basis[p]] = p;
+    for (int k = 0; k < q; ++k) where[(size_t)nonbasis[k]] = -1 - k;
+
+    RangeArena mem;
+    const int nd = nc + nr; // results: cost directions first, then right-hand-side directions
+    double *o_lo = nullptr, *o_hi = nullptr;
+    int *o_lok = nullptr, *o_hik = nullptr;
+    DzgRangePart *part = nullptr;
+    TRY(mem.get(&o_lo, (size_t)nd)); TRY(mem.get(&o_hi, (size_t)nd));
+    TRY(mem.get(&o_lok, (size_t)nd)); TRY(mem.get(&o_hik, (size_t)nd));
+
+    if (s->numerics == DZG_NUMERICS_FAST) {
+        // the eta file is empty after the refactorisation of dzg_solver_duals: Binv = Binv0
+        const int k = (int)s->h_ctl->ncompact;
+        const int rt = dzg_range_row_tiles(m), ct = dzg_range_col_tiles(q), ldy = dzg_range_ldy(m);
+        std::vector<long long> hptr((size_t)nr + 1, 0), bptr((size_t)nc + 1, 0), nptr((size_t)nc + 1, 0);
+        std::vector<int> hidx, bidx, nidx;
+        std::vector<double> hval, bval, nval;
+        for (int i = 0; i < nr; ++i) {
+            for (int64_t e = req->rhs_ptr[i]; e < req->rhs_ptr[i + 1]; ++e) {
+                hidx.push_back((int)req->rhs_idx[e]);
+                hval.push_back(req->rhs_val[e]);
+            }
+            hptr[(size_t)i + 1] = (long long)hidx.size();
+        }
+        for (int i = 0; i < nc; ++i) {
+            for (int64_t e = req->cost_ptr[i]; e < req->cost_ptr[i + 1]; ++e) {
+                const int w = where[(size_t)req->cost_idx[e]];
+                if (w >= 0) {
+                    bidx.push_back(w);
+                    bval.push_back(req->cost_val[e]);
+                } else {
+                    nidx.push_back(-1 - w);
+                    nval.push_back(req->cost_val[e]);
+                }
+            }
+            bptr[(size_t)i + 1] = (long long)bidx.size();
+            nptr[(size_t)i + 1] = (long long)nidx.size();
+        }
+        long long *d_hptr = nullptr, *d_bptr = nullptr, *d_nptr = nullptr;
+        int *d_hidx = nullptr, *d_bidx = nullptr, *d_nidx = nullptr;
+        double *d_hval = nullptr, *d_bval = nullptr, *d_nval = nullptr, *Y = nullptr, *GN = nullptr;
+        TRY(mem.put(&d_hptr, hptr, st)); TRY(mem.put(&d_hidx, hidx, st)); TRY(mem.put(&d_hval, hval, st));
+        TRY(mem.put(&d_bptr, bptr, st)); TRY(mem.put(&d_bidx, bidx, st)); TRY(mem.put(&d_bval, bval, st));
+        TRY(mem.put(&d_nptr, nptr, st)); TRY(mem.put(&d_nidx, nidx, st)); TRY(mem.put(&d_nval, nval, st));
+        const int chunk_c = std::min(nc, DZG_RANGE_CHUNK), chunk_r = std::min(nr, DZG_RANGE_CHUNK);
+        TRY(mem.get(&part, std::max((size_t)chunk_c * (size_t)ct, (size_t)chunk_r * (size_t)rt)));
+        TRY(mem.get(&Y, (size_t)chunk_c * (size_t)ldy));
+        TRY(mem.get(&GN, (size_t)chunk_c * (size_t)q));
+        const DzgRangeDirs H{d_hptr, d_hidx, d_hval}, GB{d_bptr, d_bidx, d_bval}, GNd{d_nptr, d_nidx, d_nval};
+        for (int dir0 = 0; dir0 < nc; dir0 += DZG_RANGE_CHUNK) {
+            const int cnt = std::min(DZG_RANGE_CHUNK, nc - dir0);
+            if (q) HIP_OK(hipMemsetAsync(GN, 0, sizeof(double) * (size_t)cnt * (size_t)q, st));
+            dzg_launch_range_cost_y(d, k, GB, GNd, dir0, cnt, Y, GN, st);
+            dzg_launch_range_cost_mfma(d, s->du_d, Y, GN, cnt, tol, part, st);
+            dzg_launch_range_finish(part, q > 0 ? ct : 0, cnt, o_lo + dir0, o_hi + dir0, o_lok + dir0,
+                                    o_hik + dir0, st);
+        }
+        for (int dir0 = 0; dir0 < nr; dir0 += DZG_RANGE_CHUNK) {
+            const int cnt = std::min(DZG_RANGE_CHUNK, nr - dir0);
+            dzg_launch_range_rhs_fast(d, k, H, dir0, cnt, tol, part, st);
+            dzg_launch_range_finish(part, rt, cnt, o_lo + nc + dir0, o_hi + nc + dir0, o_lok + nc + dir0,
+                                    o_hik + nc + dir0, st);
+        }
+        HIP_OK(hipGetLastError());
+        HIP_OK(hipStreamSynchronize(st)); // (the CSR vectors are locals)
+    } else {
+        // one LU solve of every STRICT FTRAN / BTRAN per direction, on the scratch control block of
+        // dzg_solver_duals; a cost direction also takes the sequential pricing pass
+        double *dxv = nullptr, *gn = nullptr;
+        TRY(mem.get(&dxv, (size_t)m + 2)); TRY(mem.get(&gn, (size_t)q));
+        TRY(mem.get(&part, (size_t)DZG_RANGE_BLOCKS));
+        DzgDev dd = d;
+        dd.ctl = s->du_ctl;
+        dd.v = s->du_y;
+        dd.dx = dxv;
+        std::vector<double> hv((size_t)(m ? m : 1)), gv((size_t)(q ? q : 1));
+        for (int i = 0; i < nc; ++i) {
+            std::fill(hv.begin(), hv.end(), 0.0);
+            std::fill(gv.begin(), gv.end(), 0.0);
+            for (int64_t e = req->cost_ptr[i]; e < req->cost_ptr[i + 1]; ++e) {
+                const int w = where[(size_t)req->cost_idx[e]];
+                if (w >= 0) hv[(size_t)w] = req->cost_val[e]; else gv[(size_t)(-1 - w)] = req->cost_val[e];
+            }
+            if (m) HIP_OK(hipMemcpyAsync(s->du_y, hv.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+            if (q) HIP_OK(hipMemcpyAsync(gn, gv.data(), sizeof(double) * q, hipMemcpyHostToDevice, st));
+            if (m) dzg_launch_strict_solve(dd, 1, st);
+            dzg_launch_price_raw(DZG_PRICE_SEQ, m, d.lda, d.A, s->du_codes, q, s->du_y, s->du_dzy, st);
+            dzg_launch_range_ratio(q, s->du_dzy, gn, s->du_d, d.nonbasis, tol, part, st);
+            dzg_launch_range_finish(part, DZG_RANGE_BLOCKS, 1, o_lo + i, o_hi + i, o_lok + i, o_hik + i, st);
+            HIP_OK(hipStreamSynchronize(st)); // (hv and gv are reused)
+        }
+        for (int i = 0; i < nr; ++i) {
+            std::fill(hv.begin(), hv.end(), 0.0);
+            for (int64_t e = req->rhs_ptr[i]; e < req->rhs_ptr[i + 1]; ++e)
+                hv[(size_t)req->rhs_idx[e]] = req->rhs_val[e];
+            if (m) HIP_OK(hipMemcpyAsync(dxv, hv.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+            if (m) dzg_launch_strict_solve(dd, 0, st);
+            dzg_launch_range_ratio(m, dxv, nullptr, d.x, nullptr, tol, part, st);
+            dzg_launch_range_finish(part, DZG_RANGE_BLOCKS, 1, o_lo + nc + i, o_hi + nc + i, o_lok + nc + i,
+                                    o_hik + nc + i, st);
+            HIP_OK(hipStreamSynchronize(st));
+        }
+        HIP_OK(hipGetLastError());
+    }
+
+    std::vector<double> lo((size_t)(nd ? nd : 1)), hi((size_t)(nd ? nd : 1));
+    std::vector<int> lok((size_t)(nd ? nd : 1)), hik((size_t)(nd ? nd : 1));
+    if (nd) {
+        HIP_OK(hipMemcpyAsync(lo.data(), o_lo, sizeof(double) * nd, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hi.data(), o_hi, sizeof(double) * nd, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(lok.data(), o_lok, sizeof(int) * nd, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipMemcpyAsync(hik.data(), o_hik, sizeof(int) * nd, hipMemcpyDeviceToHost, st));
+        HIP_OK(hipStreamSynchronize(st));
+    }
+    for (int i = 0; i < nc; ++i) {
+        if (out->cost_lo) out->cost_lo[i] = lo[(size_t)i];
+        if (out->cost_hi) out->cost_hi[i] = hi[(size_t)i];
+        if (out->cost_lo_var) out->cost_lo_var[i] = lok[(size_t)i] < 0 ? -1 : nonbasis[(size_t)lok[(size_t)i]];
+        if (out->cost_hi_var) out->cost_hi_var[i] = hik[(size_t)i] < 0 ? -1 : nonbasis[(size_t)hik[(size_t)i]];
+    }
+    for (int i = 0; i < nr; ++i) {
+        const size_t j = (size_t)nc + (size_t)i;
+        if (out->rhs_lo) out->rhs_lo[i] = lo[j];
+        if (out->rhs_hi) out->rhs_hi[i] = hi[j];
+        if (out->rhs_lo_var) out->rhs_lo_var[i] = lok[j] < 0 ? -1 : basis[(size_t)lok[j]];
+        if (out->rhs_hi_var) out->rhs_hi_var[i] = hik[j] < 0 ? -1 : basis[(size_t)hik[j]];
+    }
+    return 0;
+}
+
+// What a one-call solve wants beyond the result: the duals and, with `req`, the ranges of the solver
+// that produced it.  rg_rc: what dzg_solver_ranging returned for an OPTIMAL solve (0 otherwise).
+struct SolveExtras {
+    dzg_duals *du = nullptr;
+    const dzg_ranging_req *req = nullptr;
+    dzg_ranging *rg = nullptr;
+    int rg_rc = 0;
+};
+
+// (status, result and, when asked for and the LP ended OPTIMAL, the duals and ranges of this solver)
+static int finish_solver(dzg_solver *s, int rc, dzg_result *res, SolveExtras &ex)
 {
     const int rc2 = dzg_solver_result(s, res);
-    if (rc2 == 0 && du) {
+    if (rc2 == 0 && ex.rg) {
+        dzg_duals tmp;
+        std::memset(&tmp, 0, sizeof(tmp));
+        dzg_duals *du = ex.du ? ex.du : &tmp;
+        ex.rg_rc = 0;
+        if (res->status == DZG_OPTIMAL) ex.rg_rc = dzg_solver_ranging(s, ex.req, du, ex.rg);
+        if (res->status != DZG_OPTIMAL || ex.rg_rc != 0) {
+            dzg_duals_none(du, res->objective);
+            dzg_ranging_none(ex.req, ex.rg);
+        }
+    } else if (rc2 == 0 && ex.du) {
         // the solve's outcome is what dzg_core_solve returns, whatever becomes of the duals: a call
         // that fails (the final basis of a FAST run did not refactorise) leaves source = 0 and its
         // message in dzg_last_error
-        if (res->status != DZG_OPTIMAL || dzg_solver_duals(s, du) != 0) dzg_duals_none(du, res->objective);
+        if (res->status != DZG_OPTIMAL || dzg_solver_duals(s, ex.du) != 0) dzg_duals_none(ex.du, res->objective);
     }
     dzg_solver_destroy(s);
     return rc2 != 0 ? rc2 : rc;
 }
 
-static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res, dzg_duals *du)
+static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res, SolveExtras &ex)
 {
     dzg_solver *s = nullptr;
     int rc = dzg_solver_create(lp, o, &s);
@@ -2369,18 +2630,19 @@ static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res, dzg_
         dzg_solver_destroy(s);
         return rc;
     }
-    return finish_solver(s, rc, res, du);
+    return finish_solver(s, rc, res, ex);
 }
 
-// dzg_core_solve; with `du` also the duals of whichever solver produced the result (model.cpp)
-int dzg_core_solve_with_duals(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du)
+// dzg_core_solve; with ex.du / ex.rg also the duals / ranges of whichever solver produced the result
+static int core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, SolveExtras &ex)
 {
+    const bool fresh = ex.du || ex.rg; // the final basis will be refactorised
     if (!res) return fail(DZG_E_ARG, "res is NULL");
     if (!lp) return fail(DZG_E_ARG, "lp is NULL");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
     // (duals of a FAST run: reserve the refactorisation workspace, as a non-slack start does)
-    if (du && o.refactor_interval == 0) o.refactor_interval = -1;
+    if (fresh && o.refactor_interval == 0) o.refactor_interval = -1;
     const bool automatic = o.numerics == DZG_NUMERICS_AUTO;
     const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
     // AUTO above auto_strict_rows = FAST that must prove it followed the reference: up to
@@ -2392,7 +2654,7 @@ int dzg_core_solve_with_duals(const dzg_lp *lp, const dzg_opts *opts, dzg_result
     const int restart_rows = o.auto_restart_rows != 0 ? o.auto_restart_rows : DZG_AUTO_STRICT_RESTART_ROWS;
     const bool can_restart = automatic && lp->m > strict_rows && lp->m <= restart_rows;
     if (can_restart && o.tie_tol >= 0.0) o.near_tie_action = DZG_NEAR_TIE_STOP;
-    int rc = solve_once(lp, &o, res, du);
+    int rc = solve_once(lp, &o, res, ex);
     if (rc < 0) return rc;
     if (can_restart && res->numerics_used == DZG_NUMERICS_FAST &&
         (rc == DZG_NEAR_TIE || rc == DZG_SINGULAR || rc == DZG_PANIC)) {
@@ -2424,19 +2686,41 @@ int dzg_core_solve_with_duals(const dzg_lp *lp, const dzg_opts *opts, dzg_result
             dzg_solver_destroy(ss);
             return rc;
         }
-        if (!out_of_time) return finish_solver(ss, rc, res, du);
+        if (!out_of_time) return finish_solver(ss, rc, res, ex);
         dzg_solver_destroy(ss);
         dzg_opts fast = o;
         fast.numerics = DZG_NUMERICS_FAST;
         fast.near_tie_action = DZG_NEAR_TIE_COUNT;
-        rc = solve_once(lp, &fast, res, du);
+        rc = solve_once(lp, &fast, res, ex);
     }
+    return rc;
+}
+
+// (model.cpp)
+int dzg_core_solve_with_duals(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du)
+{
+    SolveExtras ex;
+    ex.du = du;
+    return core_solve(lp, opts, res, ex);
+}
+
+// (model.cpp) the request was validated by the caller; *rg_rc: dzg_solver_ranging's own return value
+int dzg_core_solve_with_ranging(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du,
+                                const dzg_ranging_req *req, dzg_ranging *rg, int *rg_rc)
+{
+    SolveExtras ex;
+    ex.du = du;
+    ex.req = req;
+    ex.rg = rg;
+    const int rc = core_solve(lp, opts, res, ex);
+    if (rg_rc) *rg_rc = ex.rg_rc;
     return rc;
 }
 
 extern "C" int dzg_core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res)
 {
-    return dzg_core_solve_with_duals(lp, opts, res, nullptr);
+    SolveExtras ex;
+    return core_solve(lp, opts, res, ex);
 }
 
 // Level 1 on the fields of the reference's `Simplex` AS THEY ARE (src/simplex.rs:84-112): one

@@ -34,6 +34,7 @@
 #include "batch_strict.h"
 #include "common.h"
 #include "duals.h"
+#include "ranging.h"
 
 int dzg_set_error(int code, const std::string &msg); // engine.hip
 int dzg_lp_valid(const dzg_lp *lp, std::string &why);
@@ -143,15 +144,26 @@ struct Section {
 
 // dzg_batch_solve; with `du` the duals of the LPs that end OPTIMAL follow in the same allocation
 // (k_duals.hip), after the solve and on sections of their own: the solve's layout does not move
+// With `req` / `rg` the ranges of the OPTIMAL LPs follow the duals (k_ranging.hip), in an allocation
+// of their own.
 static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots_per_launch,
-                       dzg_result *res, dzg_duals *du, bool want_duals)
+                       dzg_result *res, dzg_duals *du, bool want_duals, const dzg_ranging_req *req = nullptr,
+                       dzg_ranging *rg = nullptr, bool want_ranging = false)
 {
+    std::vector<dzg_duals> du_own; // ranging needs the fresh d on the device; the caller may not want it
+    if (want_ranging && !du && count > 0 && count < (1ll << 31)) {
+        dzg_duals none;
+        std::memset(&none, 0, sizeof(none));
+        du_own.assign((size_t)count, none);
+        du = du_own.data();
+    }
     // ---- host checks first: malformed input is DZG_E_ARG on any machine
     if (count < 0) return dzg_set_error(DZG_E_ARG, "batch: count < 0");
     if (count > 0 && (!lps || !res)) return dzg_set_error(DZG_E_ARG, "batch: lps or res is NULL");
     if (count > 0 && want_duals && !du) return dzg_set_error(DZG_E_ARG, "batch: du is NULL");
     if (count >= (1ll << 31)) return dzg_set_error(DZG_E_ARG, "batch: count out of range");
     if (pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "batch: pivots_per_launch < 0");
+    if (count > 0 && want_ranging && (!req || !rg)) return dzg_set_error(DZG_E_ARG, "batch: req or rg is NULL");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
     if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_AUTO)
@@ -170,6 +182,8 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
                                                 std::to_string(DZG_BATCH_MAX_ROWS) + ")");
         if (lp->n_struct > 0 && !lp->a) return dzg_set_error(DZG_E_ARG, at + "CSC input is not batched");
         if (lp->n - lp->m > (1ll << 30)) return dzg_set_error(DZG_E_ARG, at + "too many columns");
+        if (want_ranging && !dzg_ranging_req_valid(&req[i], lp->m, lp->n, why))
+            return dzg_set_error(DZG_E_ARG, at + why);
     }
     if (count == 0) return 0;
     int ndev = 0;
@@ -280,15 +294,17 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
 
     unsigned char *dev = nullptr;
     hipStream_t st = nullptr;
+    unsigned char *rdev = nullptr; // the ranging pass's arena
     struct Guard {
-        unsigned char **dev;
+        unsigned char **dev, **rdev;
         hipStream_t *st;
         ~Guard()
         {
             if (*dev) (void)hipFree(*dev);
+            if (*rdev) (void)hipFree(*rdev);
             if (*st) (void)hipStreamDestroy(*st);
         }
-    } guard{&dev, &st};
+    } guard{&dev, &rdev, &st};
     BHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
     BHIP(hipMalloc((void **)&dev, top));
     BHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
@@ -404,6 +420,113 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
         }
     }
 
+    // ---- ranges of the LPs that ended OPTIMAL: one workgroup per (LP, direction), bucket by bucket;
+    // the fresh d of the duals pass is still on the device
+    std::vector<unsigned char> rhost;
+    std::vector<long long> rg_out((size_t)N + 1, 0); // LP i's results: rg_out[i] .. , cost directions first
+    size_t r_lo = 0, r_hi = 0, r_lov = 0, r_hiv = 0;
+    if (want_ranging) {
+        const int *stat = (const int *)hp(s_status);
+        for (int i = 0; i < N; ++i) rg_out[(size_t)i + 1] = rg_out[(size_t)i] + req[i].ncost + req[i].nrhs;
+        const long long nout = rg_out[(size_t)N];
+        std::vector<DzgRangeItem> items;
+        std::vector<int> e_idx;
+        std::vector<double> e_val, tol((size_t)N, 0.0);
+        std::vector<int> iseg(kBuckets + 1, 0);
+        std::vector<long long> e_base((size_t)N + 1, 0); // LP i's entries: cost side, then rhs side
+        for (int i = 0; i < N; ++i) {
+            const dzg_ranging_req &rq = req[i];
+            tol[(size_t)i] = rq.pivot_tol == 0.0 ? 1e-9 : rq.pivot_tol;
+            e_base[(size_t)i] = (long long)e_idx.size();
+            const int64_t ce = rq.ncost ? rq.cost_ptr[rq.ncost] : 0, re = rq.nrhs ? rq.rhs_ptr[rq.nrhs] : 0;
+            for (int64_t e = 0; e < ce; ++e) {
+                e_idx.push_back((int)rq.cost_idx[e]);
+                e_val.push_back(rq.cost_val[e]);
+            }
+            for (int64_t e = 0; e < re; ++e) {
+                e_idx.push_back((int)rq.rhs_idx[e]);
+                e_val.push_back(rq.rhs_val[e]);
+            }
+        }
+        for (int b = 0; b < kBuckets; ++b) {
+            for (int i = 0; i < N; ++i) {
+                if (stat[i] != DZG_OPTIMAL || bucket_of(lps[i].m) != b) continue;
+                const dzg_ranging_req &rq = req[i];
+                const long long cbase = e_base[(size_t)i], rbase = cbase + (rq.ncost ? rq.cost_ptr[rq.ncost] : 0);
+                for (int64_t j = 0; j < rq.ncost; ++j) {
+                    DzgRangeItem it;
+                    it.e0 = cbase + rq.cost_ptr[j];
+                    it.e1 = cbase + rq.cost_ptr[j + 1];
+                    it.out = rg_out[(size_t)i] + j;
+                    it.lp = i;
+                    it.kind = 1;
+                    items.push_back(it);
+                }
+                for (int64_t j = 0; j < rq.nrhs; ++j) {
+                    DzgRangeItem it;
+                    it.e0 = rbase + rq.rhs_ptr[j];
+                    it.e1 = rbase + rq.rhs_ptr[j + 1];
+                    it.out = rg_out[(size_t)i] + rq.ncost + j;
+                    it.lp = i;
+                    it.kind = 0;
+                    items.push_back(it);
+                }
+            }
+            if (items.size() >= ((size_t)1 << 31)) return dzg_set_error(DZG_E_ARG, "batch: too many directions");
+            iseg[(size_t)b + 1] = (int)items.size();
+        }
+        if (!items.empty()) {
+            size_t rtop = 0;
+            auto rsection = [&](size_t bytes) {
+                const size_t off = rtop;
+                rtop += (bytes + 15) / 16 * 16;
+                return off;
+            };
+            const size_t r_items = rsection(sizeof(DzgRangeItem) * items.size()),
+                         r_eidx = rsection(sizeof(int) * e_idx.size()),
+                         r_eval = rsection(sizeof(double) * e_val.size()), r_tol = rsection(sizeof(double) * N);
+            const size_t r_up = rtop;
+            r_lo = rsection(sizeof(double) * (size_t)nout);
+            r_hi = rsection(sizeof(double) * (size_t)nout);
+            r_lov = rsection(sizeof(int) * (size_t)nout);
+            r_hiv = rsection(sizeof(int) * (size_t)nout);
+            rhost.assign(rtop, 0);
+            std::memcpy(rhost.data() + r_items, items.data(), sizeof(DzgRangeItem) * items.size());
+            if (!e_idx.empty()) {
+                std::memcpy(rhost.data() + r_eidx, e_idx.data(), sizeof(int) * e_idx.size());
+                std::memcpy(rhost.data() + r_eval, e_val.data(), sizeof(double) * e_val.size());
+            }
+            std::memcpy(rhost.data() + r_tol, tol.data(), sizeof(double) * N);
+            BHIP(hipMalloc((void **)&rdev, rtop));
+            BHIP(hipMemcpyAsync(rdev, rhost.data(), r_up, hipMemcpyHostToDevice, st));
+            DzgRangingArgs a;
+            a.lp = (const DzgDualsLp *)(dev + s_dlp.off);
+            a.A = g.A;
+            a.var_col = g.var_col;
+            a.basis = g.basis;
+            a.nonbasis = g.nonbasis;
+            a.x = g.x;
+            a.d = (const double *)(dev + s_d.off);
+            a.tol = (const double *)(rdev + r_tol);
+            a.item = (const DzgRangeItem *)(rdev + r_items);
+            a.e_idx = (const int *)(rdev + r_eidx);
+            a.e_val = (const double *)(rdev + r_eval);
+            a.lo = (double *)(rdev + r_lo);
+            a.hi = (double *)(rdev + r_hi);
+            a.lo_var = (int *)(rdev + r_lov);
+            a.hi_var = (int *)(rdev + r_hiv);
+            for (int b = 0; b < kBuckets; ++b) {
+                const int cnt = iseg[(size_t)b + 1] - iseg[(size_t)b];
+                if (cnt == 0) continue;
+                a.mmax = mmax[b];
+                dzg_launch_ranging_small(b, a, a.item + iseg[(size_t)b], cnt, st);
+                BHIP(hipGetLastError());
+            }
+            BHIP(hipMemcpyAsync(rhost.data() + r_lo, rdev + r_lo, rtop - r_lo, hipMemcpyDeviceToHost, st));
+            BHIP(hipStreamSynchronize(st));
+        }
+    }
+
     // ---- results
     const int *bs = (const int *)hp(s_basis), *nb = (const int *)hp(s_nonbasis);
     const double *x = (const double *)hp(s_x), *xb = (const double *)hp(s_xbar),
@@ -460,6 +583,30 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
         r.price_pass_used = 0;
         r.price_rows_copy = 0;
         r.state_drift = 0.0;
+        if (want_ranging) {
+            if (r.status != DZG_OPTIMAL) {
+                dzg_ranging_none(&req[i], &rg[i]);
+            } else {
+                const dzg_ranging_req &rq = req[i];
+                const dzg_ranging &o_ = rg[i];
+                const double *lo = (const double *)(rhost.data() + r_lo) + rg_out[(size_t)i];
+                const double *hi = (const double *)(rhost.data() + r_hi) + rg_out[(size_t)i];
+                const int *lov = (const int *)(rhost.data() + r_lov) + rg_out[(size_t)i];
+                const int *hiv = (const int *)(rhost.data() + r_hiv) + rg_out[(size_t)i];
+                for (int64_t j = 0; j < rq.ncost; ++j) {
+                    if (o_.cost_lo) o_.cost_lo[j] = lo[j];
+                    if (o_.cost_hi) o_.cost_hi[j] = hi[j];
+                    if (o_.cost_lo_var) o_.cost_lo_var[j] = lov[j];
+                    if (o_.cost_hi_var) o_.cost_hi_var[j] = hiv[j];
+                }
+                for (int64_t j = 0; j < rq.nrhs; ++j) {
+                    if (o_.rhs_lo) o_.rhs_lo[j] = lo[rq.ncost + j];
+                    if (o_.rhs_hi) o_.rhs_hi[j] = hi[rq.ncost + j];
+                    if (o_.rhs_lo_var) o_.rhs_lo_var[j] = lov[rq.ncost + j];
+                    if (o_.rhs_hi_var) o_.rhs_hi_var[j] = hiv[rq.ncost + j];
+                }
+            }
+        }
         if (want_duals) {
             dzg_duals &u = du[i];
             if (r.status != DZG_OPTIMAL) {
@@ -494,4 +641,11 @@ extern "C" int dzg_batch_solve_duals(const dzg_lp *lps, int64_t count, const dzg
                                      int64_t pivots_per_launch, dzg_result *res, dzg_duals *du)
 {
     return batch_solve(lps, count, opts, pivots_per_launch, res, du, true);
+}
+
+extern "C" int dzg_batch_solve_ranging(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                                       int64_t pivots_per_launch, const dzg_ranging_req *req, dzg_result *res,
+                                       dzg_duals *du, dzg_ranging *rg)
+{
+    return batch_solve(lps, count, opts, pivots_per_launch, res, du, true, req, rg, true);
 }

@@ -331,13 +331,92 @@ static void adopt_duals(const dzg_model *md, const Built &b, int status, double 
     map_duals(md, b, yv, du);
 }
 
+// engine.hip
+bool dzg_ranging_req_valid(const dzg_ranging_req *req, int64_t m, int64_t n, std::string &why);
+void dzg_ranging_none(const dzg_ranging_req *req, dzg_ranging *rg);
+int dzg_core_solve_with_ranging(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du,
+                                const dzg_ranging_req *req, dzg_ranging *rg, int *rg_rc);
+
+// A model's ranging request as core directions over the standard form `b`.
+struct CoreRanging {
+    std::vector<int64_t> cost_ptr, cost_idx, rhs_ptr, rhs_idx;
+    std::vector<double> cost_val, rhs_val;
+    dzg_ranging_req req;
+};
+
+// The one place that maps a request in the user's terms to core directions (Built's numbering):
+// user variable u -> +1 on x+ and -1 on x-; a group of user rows -> the same rows of the standard
+// form, which lists the user rows first.  false: `why` says what is wrong.
+static bool map_ranging_req(const dzg_model *md, const Built &b, const dzg_model_ranging_req *mr,
+                            CoreRanging &out, std::string &why)
+{
+    if (!mr) { why = "model ranging: req is NULL"; return false; }
+    if (mr->nvar < 0 || mr->nrow < 0) { why = "model ranging: negative count"; return false; }
+    if (mr->nvar > 0 && !mr->var) { why = "model ranging: var is NULL"; return false; }
+    if (mr->nrow > 0 && !mr->row_ptr) { why = "model ranging: row_ptr is NULL"; return false; }
+    out.cost_ptr.assign(1, 0);
+    for (int64_t i = 0; i < mr->nvar; ++i) {
+        const int64_t u = mr->var[i];
+        if (u < 0 || u >= md->nvars) {
+            why = "model ranging: variable " + std::to_string(u) + " out of range";
+            return false;
+        }
+        if (b.pos_var[(size_t)u] < 0) {
+            why = "model ranging: variable " + std::to_string(u) + " appears nowhere in the model";
+            return false;
+        }
+        out.cost_idx.push_back(b.pos_var[(size_t)u]);
+        out.cost_val.push_back(1.0);
+        out.cost_idx.push_back(b.neg_var[(size_t)u]);
+        out.cost_val.push_back(-1.0);
+        out.cost_ptr.push_back((int64_t)out.cost_idx.size());
+    }
+    out.rhs_ptr.assign(1, 0);
+    if (mr->nrow > 0) {
+        if (mr->row_ptr[0] != 0) { why = "model ranging: row_ptr[0] != 0"; return false; }
+        for (int64_t i = 0; i < mr->nrow; ++i)
+            if (mr->row_ptr[i + 1] < mr->row_ptr[i]) { why = "model ranging: row_ptr decreases"; return false; }
+        if (mr->row_ptr[mr->nrow] > 0 && (!mr->row_idx || !mr->row_coef)) {
+            why = "model ranging: row_idx or row_coef is NULL";
+            return false;
+        }
+    }
+    for (int64_t i = 0; i < mr->nrow; ++i) {
+        for (int64_t e = mr->row_ptr[i]; e < mr->row_ptr[i + 1]; ++e) {
+            if (mr->row_idx[e] < 0 || mr->row_idx[e] >= md->ncons) {
+                why = "model ranging: row " + std::to_string(mr->row_idx[e]) + " out of range";
+                return false;
+            }
+            out.rhs_idx.push_back(mr->row_idx[e]); // user rows come first in the standard form
+            out.rhs_val.push_back(mr->row_coef[e]);
+        }
+        out.rhs_ptr.push_back((int64_t)out.rhs_idx.size());
+    }
+    out.req.ncost = mr->nvar;
+    out.req.cost_ptr = out.cost_ptr.data();
+    out.req.cost_idx = out.cost_idx.data();
+    out.req.cost_val = out.cost_val.data();
+    out.req.nrhs = mr->nrow;
+    out.req.rhs_ptr = out.rhs_ptr.data();
+    out.req.rhs_idx = out.rhs_idx.data();
+    out.req.rhs_val = out.rhs_val.data();
+    out.req.pivot_tol = mr->pivot_tol;
+    return dzg_ranging_req_valid(&out.req, b.m, b.n, why); // duplicates inside a group, pivot_tol
+}
+
 static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res,
-                       dzg_model_duals *du, bool want_duals)
+                       dzg_model_duals *du, bool want_duals, const dzg_model_ranging_req *mreq = nullptr,
+                       dzg_ranging *rg = nullptr)
 {
     if (!res || !valid(md)) return DZG_E_ARG;
     if (want_duals && (!du || (md->ncons > 0 && !du->con_dual))) return DZG_E_ARG;
     Built b;
     build(md, b, true);
+    CoreRanging cr;
+    if (rg) {
+        std::string why;
+        if (!map_ranging_req(md, b, mreq, cr, why)) return dzg_set_error(DZG_E_ARG, why);
+    }
     res->m = b.m;
     res->n = b.n;
     dzg_lp lp;
@@ -373,7 +452,9 @@ static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_resu
         core.y = yv.data();
         core.d = du->core.d;
     }
-    const int rc = dzg_core_solve_with_duals(&lp, opts, &r, want_duals ? &core : nullptr);
+    int rg_rc = 0;
+    const int rc = rg ? dzg_core_solve_with_ranging(&lp, opts, &r, &core, &cr.req, rg, &rg_rc)
+                      : dzg_core_solve_with_duals(&lp, opts, &r, want_duals ? &core : nullptr);
     res->status = rc < 0 ? rc : r.status;
     res->numerics_used = r.numerics_used;
     res->iterations = r.iterations;
@@ -383,6 +464,10 @@ static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_resu
     if (rc < 0) return rc;
     if (res->values) solution_values(md, b, basis.data(), x.data(), res->values);
     if (want_duals) adopt_duals(md, b, r.status, r.objective, core, yv.data(), du);
+    // (ranging failed after an OPTIMAL solve -- a route without ranging, no memory, a final basis
+    // that did not refactorise: the call fails with that code, dzg_last_error holds
+    // dzg_solver_ranging's text; res keeps the solve's outcome)
+    if (rg && r.status == DZG_OPTIMAL && rg_rc < 0) return rg_rc;
     return r.status;
 }
 
@@ -406,8 +491,10 @@ extern "C" int dzg_model_solve_duals(const dzg_model *md, const dzg_opts *opts, 
 // other model goes through dzg_model_solve by itself.  The standard form and the values are
 // extracted exactly as dzg_model_solve extracts them.
 static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
-                             dzg_model_result *res, dzg_model_duals *du, bool want_duals)
+                             dzg_model_result *res, dzg_model_duals *du, bool want_duals,
+                             const dzg_model_ranging_req *mreq = nullptr, dzg_ranging *rg = nullptr)
 {
+    if (count > 0 && want_duals && rg && !mreq) return dzg_set_error(DZG_E_ARG, "model batch: req is NULL");
     if (count < 0) return dzg_set_error(DZG_E_ARG, "model batch: count < 0");
     if (count > 0 && (!models || !res)) return dzg_set_error(DZG_E_ARG, "model batch: models or res is NULL");
     if (count > 0 && want_duals && !du) return dzg_set_error(DZG_E_ARG, "model batch: du is NULL");
@@ -429,7 +516,15 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
                             (o.numerics == DZG_NUMERICS_AUTO && b.m <= strict_rows);
         if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS) batched.push_back(i);
     }
+    std::vector<CoreRanging> crs((size_t)(rg ? count : 0));
+    for (int64_t i = 0; rg && i < count; ++i) {
+        std::string why;
+        if (!map_ranging_req(&models[i], built[(size_t)i], &mreq[i], crs[(size_t)i], why))
+            return dzg_set_error(DZG_E_ARG, "model batch: models[" + std::to_string(i) + "]: " + why);
+    }
     const size_t nb = batched.size();
+    std::vector<dzg_ranging_req> breq(rg ? nb : 0);
+    std::vector<dzg_ranging> brg(rg ? nb : 0);
     std::vector<dzg_lp> lps(nb);
     std::vector<dzg_result> rs(nb);
     std::vector<std::vector<int64_t>> basis(nb);
@@ -463,9 +558,15 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
             cores[k].y = yv[k].data();
             cores[k].d = du[batched[k]].core.d;
         }
+        if (rg) {
+            breq[k] = crs[(size_t)batched[k]].req;
+            brg[k] = rg[batched[k]];
+        }
     }
     if (nb > 0) {
-        const int rc = want_duals ? dzg_batch_solve_duals(lps.data(), (int64_t)nb, &o, 0, rs.data(), cores.data())
+        const int rc = rg ? dzg_batch_solve_ranging(lps.data(), (int64_t)nb, &o, 0, breq.data(), rs.data(),
+                                                    cores.data(), brg.data())
+                     : want_duals ? dzg_batch_solve_duals(lps.data(), (int64_t)nb, &o, 0, rs.data(), cores.data())
                                   : dzg_batch_solve(lps.data(), (int64_t)nb, &o, 0, rs.data());
         if (rc < 0) return rc;
     }
@@ -489,7 +590,8 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
             ++k;
             continue;
         }
-        const int rc = model_solve(&models[i], opts, &out, want_duals ? &du[i] : nullptr, want_duals);
+        const int rc = model_solve(&models[i], opts, &out, want_duals ? &du[i] : nullptr, want_duals,
+                                   rg ? &mreq[i] : nullptr, rg ? &rg[i] : nullptr);
         if (rc < 0) return rc;
     }
     return 0;
@@ -505,4 +607,22 @@ extern "C" int dzg_model_solve_batch_duals(const dzg_model *models, int64_t coun
                                            dzg_model_result *res, dzg_model_duals *du)
 {
     return model_solve_batch(models, count, opts, res, du, true);
+}
+
+extern "C" int dzg_model_solve_ranging(const dzg_model *md, const dzg_opts *opts,
+                                       const dzg_model_ranging_req *req, dzg_model_result *res,
+                                       dzg_model_duals *du, dzg_ranging *rg)
+{
+    if (!du || !req || !rg) return dzg_set_error(DZG_E_ARG, "model ranging: req, du or rg is NULL");
+    if (!res || !valid(md)) return dzg_set_error(DZG_E_ARG, "model ranging: res is NULL or the model is malformed");
+    if (md->ncons > 0 && !du->con_dual) return dzg_set_error(DZG_E_ARG, "model ranging: con_dual is NULL");
+    return model_solve(md, opts, res, du, true, req, rg);
+}
+
+extern "C" int dzg_model_solve_batch_ranging(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                             const dzg_model_ranging_req *req, dzg_model_result *res,
+                                             dzg_model_duals *du, dzg_ranging *rg)
+{
+    if (count > 0 && (!req || !rg)) return dzg_set_error(DZG_E_ARG, "model batch: req or rg is NULL");
+    return model_solve_batch(models, count, opts, res, du, true, req, rg);
 }

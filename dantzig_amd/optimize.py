@@ -4,7 +4,9 @@ The core always maximises: Minimize negates the objective on the way in and the 
 on the way out (optimize.py:114-117, :21-27).  A model with an integer variable is solved by
 branch and bound (rust.solve_mip); Solution.mip then reports the search in the user's sense.
 solve(duals=True) adds dual values, reduced costs and an optimality certificate, in the user's sense
-too: Solution.dual(constraint), Solution.reduced_cost(variable), Solution.certificate."""
+too: Solution.dual(constraint), Solution.reduced_cost(variable), Solution.certificate.
+solve(ranging=True) adds how far those slopes hold: Solution.rhs_range(constraint) and
+Solution.objective_range(variable)."""
 from __future__ import annotations
 
 import abc
@@ -32,8 +34,16 @@ class Certificate:
     z_diff: float
 
 
+@dataclass(frozen=True)
+class Range:
+    """The closed interval [lo, hi] of a constraint's b or of a variable's objective coefficient over
+    which the optimal basis holds (-inf / +inf where nothing blocks); the current value is inside."""
+    lo: float
+    hi: float
+
+
 class Solution:
-    def __init__(self, *, solution: rs.PySolution, sense: str, constraints=None) -> None:
+    def __init__(self, *, solution: rs.PySolution, sense: str, constraints=None, objective=None) -> None:
         if sense not in _SENSES:
             raise ValueError(f"sense is {sense!r}; a Solution is built for {_SENSES[0]!r} or {_SENSES[1]!r}")
         self._solution = solution
@@ -44,6 +54,8 @@ class Solution:
         for constraint in constraints or []:
             self._rows.setdefault(id(constraint), (constraint, row))
             row += len(constraint.rust_inequalities())
+        # ranging: the model's objective (the coefficients the ranges are about), user's sense
+        self._objective = objective
 
     def _duals(self) -> "rs.PyDuals":
         duals = getattr(self._solution, "duals", None)
@@ -68,6 +80,37 @@ class Solution:
         (bound rows left out), in the user's sense."""
         value = self._duals().var_rc[variable.to_rust_variable().id]
         return -value if self._sense == "minimize" else value
+
+    def _ranging(self) -> "rs.PyRanging":
+        ranging = getattr(self._solution, "ranging", None)
+        if ranging is None:
+            raise RuntimeError("this Solution carries no ranges: ask for them with solve(ranging=True)")
+        return ranging
+
+    def rhs_range(self, constraint: Constraint) -> Range:
+        """The values of the constraint's own b, in its written form linexpr <=, >= or == b, over which
+        the optimal basis holds: inside it the objective moves by dual(constraint) per unit of b."""
+        ranging = self._ranging()
+        entry = self._rows.get(id(constraint))
+        if entry is None:
+            raise KeyError("the constraint is not part of the solved model")
+        group = list(self._rows).index(id(constraint))
+        # the user's b from the first row: b as written if its sign is +1, the negated row's -b otherwise
+        b = constraint._signs[0] * constraint.rust_inequalities()[0]._b
+        return Range(b + ranging.group_lo[group], b + ranging.group_hi[group])
+
+    def objective_range(self, variable: Variable) -> Range:
+        """The values of the objective coefficient of `variable` over which the optimal basis holds:
+        inside it the solution stays and the objective moves by solution[variable] per unit."""
+        ranging = self._ranging()
+        key = variable.to_rust_variable().id
+        if key not in ranging.var_lo:
+            raise KeyError("the variable is not part of the solved model")
+        coef = self._objective.linexpr.map_ids_to_coefs().get(key, 0.0)
+        lo, hi = ranging.var_lo[key], ranging.var_hi[key]
+        if self._sense == "minimize":  # the core's coefficient is -coef: its step t is -(the user's)
+            lo, hi = -hi, -lo
+        return Range(coef + lo, coef + hi)
 
     @property
     def certificate(self) -> Certificate:
@@ -132,15 +175,33 @@ class Optimize(abc.ABC):
     def _rust_problem(self):
         return self._core_objective().to_rust_affexpr(), list(self.yield_rust_inequalities())
 
-    def solve(self, *, duals: bool = False) -> Solution:
+    def _row_groups(self) -> list:
+        """One group of rows per constraint: its rows with Constraint._signs as coefficients, so that
+        the group's step is the change of the constraint's own b."""
+        groups, seen, row = [], set(), 0
+        for constraint in self.constraints:
+            n = len(constraint.rust_inequalities())
+            if id(constraint) not in seen:  # (a constraint added twice: Solution keeps its first rows)
+                seen.add(id(constraint))
+                groups.append([(row + k, sign) for k, sign in enumerate(constraint._signs)])
+            row += n
+        return groups
+
+    def solve(self, *, duals: bool = False, ranging: bool = False) -> Solution:
         """Solve on the GPU.  Raises exceptions.UnboundedError / InfeasibleError.  duals=True: the
         Solution also answers dual(), reduced_cost() and certificate (LPs only: ValueError for a
-        model with an integer variable)."""
+        model with an integer variable).  ranging=True (implies duals): also rhs_range() and
+        objective_range(); NotImplementedError where the solve's route has no ranging."""
         objective, constraints = self._rust_problem()
         if rs._has_integer(objective, constraints):
+            if ranging:
+                raise ValueError("ranging=True: ranges are not defined for a model with integer variables")
             if duals:
                 raise ValueError("duals=True: dual values are not defined for a model with integer variables")
             return Solution(solution=rs.solve_mip(objective, constraints), sense=self.sense)
+        if ranging:
+            return Solution(solution=rs.solve(objective, constraints, ranging=self._row_groups()),
+                            sense=self.sense, constraints=list(self.constraints), objective=self.objective)
         if duals:
             return Solution(solution=rs.solve(objective, constraints, duals=True), sense=self.sense,
                             constraints=list(self.constraints))
@@ -163,18 +224,23 @@ class Maximize(Optimize):
     sense = property(lambda self: "maximize")
 
 
-def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False) -> list:
+def solve_many(problems, *, duals: bool = False, ranging: bool = False,
+               return_exceptions: bool = False) -> list:
     """[p.solve() for p in problems] in one batched call (rust.solve_many): the small models share
     one launch on the GPU, one workgroup per model, bit for bit what p.solve() returns.  A model
     that is unbounded or infeasible raises the exception p.solve() raises, with the model's index
     in the message, after the whole batch is done; with return_exceptions=True the exception
-    instance stands in that model's place.  duals=True: every Solution is p.solve(duals=True)'s."""
+    instance stands in that model's place.  duals=True: every Solution is p.solve(duals=True)'s;
+    ranging=True: p.solve(ranging=True)'s."""
     problems = list(problems)
     for i, p in enumerate(problems):
         if not isinstance(p, Optimize):
             raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
+    duals = duals or ranging
     raw = rs.solve_many([p._rust_problem() for p in problems], duals=duals,
+                        ranging=[p._row_groups() for p in problems] if ranging else False,
                         return_exceptions=return_exceptions)
     return [r if isinstance(r, Exception)
-            else Solution(solution=r, sense=p.sense, constraints=list(p.constraints) if duals else None)
+            else Solution(solution=r, sense=p.sense, constraints=list(p.constraints) if duals else None,
+                          objective=p.objective if ranging else None)
             for p, r in zip(problems, raw)]

@@ -187,12 +187,28 @@ class PyDuals:
             setattr(self, k, kw.get(k))
 
 
+class PyRanging:
+    """Ranges of one solve(..., ranging=...), in the core sense (the model is maximised, every row is
+    linexpr <= b): var_lo / var_hi keyed by Variable.id, the interval of the step t on that
+    variable's objective coefficient over which the optimal basis holds; group_lo / group_hi per
+    requested group of rows, the interval of the step t when every row r of the group has its b
+    moved by coefficient * t.  *_var: the blocking variable of the standard form, -1 if none."""
+    __slots__ = ("var_lo", "var_hi", "var_lo_var", "var_hi_var", "group_lo", "group_hi",
+                 "group_lo_var", "group_hi_var")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
 class PySolution:
-    __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape", "mip", "duals")
+    __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape", "mip", "duals",
+                 "ranging")
 
     def __init__(self, objective_value: float, values: dict, iterations: int = 0,
                  numerics: str = "", shape=(0, 0), mip: "MipInfo | None" = None,
                  duals: "PyDuals | None" = None):
+        self.ranging = None             # None unless solve(..., ranging=...)
         self._objective_value = objective_value
         self._values = values
         self.iterations = iterations    # extras the reference does not expose
@@ -277,6 +293,42 @@ class _DualBuffers:
                        dual_infeasibility=float(core.dual_infeas), z_diff=float(core.z_diff))
 
 
+class _RangingBuffers:
+    """One dzg_model_ranging_req over every variable of the lowered model and the given groups of
+    rows (True: every inequality by itself), with the dzg_ranging it fills."""
+
+    def __init__(self, arrays: dict, order, groups, pivot_tol: float = 0.0):
+        if groups is True:
+            groups = [[(r, 1.0)] for r in range(arrays["ncons"])]
+        self.groups = [list(g) for g in groups]
+        self.buf = _ffi.RangingBuffers([{}] * len(order), [{}] * len(self.groups), pivot_tol)
+        self.var = _ffi.i64(list(range(len(order))) + [0])
+        ptr_, idx, coef = [0], [], []
+        for g in self.groups:
+            for r, k in g:
+                idx.append(int(r))
+                coef.append(float(k))
+            ptr_.append(len(idx))
+        self.row_ptr, self.row_idx = _ffi.i64(ptr_), _ffi.i64(idx + [0])
+        self.row_coef = _ffi.f64(coef + [0.0])
+        self.nvar, self.pivot_tol = len(order), float(pivot_tol)
+
+    def fill(self, req: "_ffi.ModelRangingReq", out: "_ffi.Ranging") -> None:
+        req.nvar, req.var = self.nvar, _ffi.ptr(self.var)
+        req.nrow, req.row_ptr = len(self.groups), _ffi.ptr(self.row_ptr)
+        req.row_idx, req.row_coef = _ffi.ptr(self.row_idx), _ffi.ptr(self.row_coef)
+        req.pivot_tol = self.pivot_tol
+        self.buf.fill_out(out)
+
+    def pyranging(self, order) -> PyRanging:
+        c, r = self.buf.side(0), self.buf.side(1)
+        by_id = lambda a, cast: {v.id: cast(a[i]) for i, v in enumerate(order)}  # noqa: E731
+        return PyRanging(var_lo=by_id(c[0], float), var_hi=by_id(c[1], float),
+                         var_lo_var=by_id(c[2], int), var_hi_var=by_id(c[3], int),
+                         group_lo=[float(v) for v in r[0]], group_hi=[float(v) for v in r[1]],
+                         group_lo_var=[int(v) for v in r[2]], group_hi_var=[int(v) for v in r[3]])
+
+
 def _outcome(res, values, order, where: str = "", stacklevel: int = 4):
     """The PySolution of one dzg_model_result, or the exception the reference raises for it."""
     rc = int(res.status)
@@ -300,12 +352,24 @@ def _outcome(res, values, order, where: str = "", stacklevel: int = 4):
                       (int(res.m), int(res.n)))
 
 
-def solve(objective: PyAffExpr, constraints, duals: bool = False) -> PySolution:
+def _want_ranging(ranging) -> bool:
+    return ranging is not False and ranging is not None
+
+
+def solve(objective: PyAffExpr, constraints, duals: bool = False, ranging=False,
+          pivot_tol: float = 0.0) -> PySolution:
     """Maximise `objective` subject to `constraints` on the GPU (src/lib.rs:16-27).  duals=True
-    (dzg_model_solve_duals): the same solution with .duals, a PyDuals."""
+    (dzg_model_solve_duals): the same solution with .duals, a PyDuals.  ranging=True, or a list of
+    groups [(row, coefficient), ...] of inequalities (dzg_model_solve_ranging): also .ranging, a
+    PyRanging over every variable and every group (True: every inequality by itself); implies
+    duals.  NotImplementedError when the solve ends on a route without ranging (CSC storage)."""
     if not isinstance(objective, PyAffExpr):
         raise TypeError("objective must be a PyAffExpr")
     constraints = list(constraints)
+    want_ranging = _want_ranging(ranging)
+    if want_ranging and _has_integer(objective, constraints):
+        raise ValueError("ranging=True: ranges are not defined for a model with integer variables")
+    duals = duals or want_ranging
     if duals and _has_integer(objective, constraints):
         raise ValueError("duals=True: dual values are not defined for a model with integer variables")
     arrays, order = lower(objective, constraints)
@@ -318,6 +382,13 @@ def solve(objective: PyAffExpr, constraints, duals: bool = False) -> PySolution:
     if duals:
         buf, cdu = _DualBuffers(arrays), _ffi.ModelDuals()
         buf.fill(cdu)
+    if want_ranging:
+        rbuf, creq, crg = _RangingBuffers(arrays, order, ranging, pivot_tol), _ffi.ModelRangingReq(), _ffi.Ranging()
+        rbuf.fill(creq, crg)
+        rc = _ffi.lib().dzg_model_solve_ranging(C.byref(md), C.byref(opts), C.byref(creq), C.byref(res),
+                                                C.byref(cdu), C.byref(crg))
+        _ffi.check_ranging(rc, "dzg_model_solve_ranging")
+    elif duals:
         rc = _ffi.lib().dzg_model_solve_duals(C.byref(md), C.byref(opts), C.byref(res), C.byref(cdu))
         _ffi.check(rc, "dzg_model_solve_duals")
     else:
@@ -328,6 +399,8 @@ def solve(objective: PyAffExpr, constraints, duals: bool = False) -> PySolution:
         raise out
     if duals:
         out.duals = buf.pyduals(cdu, order)
+    if want_ranging and out.duals is not None:
+        out.ranging = rbuf.pyranging(order)
     return out
 
 
@@ -412,7 +485,8 @@ def solve_mip(objective: PyAffExpr, constraints, *, node_log: int = 0, **mip_opt
     return out
 
 
-def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False) -> list:
+def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float = 0.0,
+               return_exceptions: bool = False) -> list:
     """solve() for every (objective, constraints) pair of `problems`, in one dzg_model_solve_batch
     call: the models that solve() would run in STRICT numerics on at most 128 rows share one batch
     on the GPU (one workgroup per model), the others are solved one at a time.  Results keep the
@@ -421,14 +495,19 @@ def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False
     return_exceptions=True the exception instance stands in that model's place instead.  Models with
     an integer variable are solved one by one through solve_mip(), after the batch.  duals=True
     (dzg_model_solve_batch_duals): every solution carries .duals as solve(..., duals=True) gives
-    it; a model with an integer variable is then a ValueError."""
+    it; a model with an integer variable is then a ValueError.  ranging=True, or one list of row
+    groups per problem (dzg_model_solve_batch_ranging): every solution carries .ranging as
+    solve(..., ranging=...) gives it; implies duals."""
     problems = [(objective, list(constraints)) for objective, constraints in problems]
+    want_ranging = _want_ranging(ranging)
+    duals = duals or want_ranging
     for i, (objective, _) in enumerate(problems):
         if not isinstance(objective, PyAffExpr):
             raise TypeError(f"problems[{i}]: objective must be a PyAffExpr")
     mip = [_has_integer(objective, constraints) for objective, constraints in problems]
     if duals and any(mip):
-        raise ValueError(f"problems[{mip.index(True)}]: duals=True: dual values are not defined for a "
+        raise ValueError(f"problems[{mip.index(True)}]: {'ranging' if want_ranging else 'duals'}=True: "
+                         f"{'ranges' if want_ranging else 'dual values'} are not defined for a "
                          "model with integer variables")
     lp_idx = [i for i in range(len(problems)) if not mip[i]]
     out: list = [None] * len(problems)
@@ -445,6 +524,16 @@ def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False
         cdu = (_ffi.ModelDuals * max(count, 1))()
         for k, buf in enumerate(bufs):
             buf.fill(cdu[k])
+    if want_ranging:
+        groups = [True] * count if ranging is True else [list(ranging)[i] for i in lp_idx]
+        rbufs = [_RangingBuffers(arrays, order, g, pivot_tol) for (arrays, order), g in zip(lowered, groups)]
+        creq, crg = (_ffi.ModelRangingReq * max(count, 1))(), (_ffi.Ranging * max(count, 1))()
+        for k, rbuf in enumerate(rbufs):
+            rbuf.fill(creq[k], crg[k])
+        rc = _ffi.lib().dzg_model_solve_batch_ranging(models, C.c_int64(count), C.byref(opts), creq, results,
+                                                      cdu, crg)
+        _ffi.check_ranging(rc, "dzg_model_solve_batch_ranging")
+    elif duals:
         rc = _ffi.lib().dzg_model_solve_batch_duals(models, C.c_int64(count), C.byref(opts), results, cdu)
         _ffi.check(rc, "dzg_model_solve_batch_duals")
     else:
@@ -454,6 +543,8 @@ def solve_many(problems, *, duals: bool = False, return_exceptions: bool = False
         out[i] = _outcome(results[k], keep[k][1], lowered[k][1], f" (model {i})", stacklevel=3)
         if duals and not isinstance(out[i], Exception):
             out[i].duals = bufs[k].pyduals(cdu[k], lowered[k][1])
+            if want_ranging and out[i].duals is not None:
+                out[i].ranging = rbufs[k].pyranging(lowered[k][1])
     for i in range(len(problems)):
         if mip[i]:
             arrays, order = lower(*problems[i])

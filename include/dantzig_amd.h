@@ -440,6 +440,86 @@ int dzg_model_solve_batch_duals(const dzg_model *models, int64_t count, const dz
  * rows of the model's standard form (DZG_E_ARG otherwise). */
 int dzg_model_map_duals(const dzg_model *model, const double *y, int64_t m, dzg_model_duals *out);
 
+/* ---- Sensitivity ranging at the optimum (csrc/k_ranging.hip) ---------------------------- */
+
+/* How far the slopes of dzg_duals hold.  Core sense, at an OPTIMAL basis B with nonbasic set N; x is
+ * the carried basic solution by position, d the FRESH reduced costs by variable, both clamped at
+ * zero: xc_p = max(x_p, 0.0), dc_j = max(d_j, 0.0), so that 0 is inside every range.
+ *   cost direction g (sparse over the n variables; the cost becomes c + t g):
+ *     Y = B^-T g_B,  delta_k = a_j . Y - g_j  for the variable j at nonbasic position k
+ *   right-hand-side direction h (sparse over the m rows; the right-hand side becomes rhs + t h):
+ *     delta_p = (B^-1 h)_p  for basis position p
+ *   a position is a candidate when |delta| > pivot_tol, with value r = -(clamped / delta): delta > 0
+ *   gives r <= 0, a bound on lo; delta < 0 gives r >= 0, a bound on hi.  lo is the largest candidate
+ *   for lo (-inf if none), hi the smallest for hi (+inf if none); ties go to the lowest position.
+ *   *_var is the variable at the blocking position (the nonbasic one that would enter, the basic one
+ *   that would leave), -1 if none.
+ * For every t in [lo, hi] the basis stays optimal: the optimal value is objective + t (g . x) for a
+ * cost direction and objective + t (y . h) for a right-hand-side direction.
+ * Directions are in CSR form: direction i owns entries ptr[i] .. ptr[i+1]; the indices of one
+ * direction are distinct and in range, else DZG_E_ARG.  pivot_tol: 0 selects 1e-9; negative or NaN
+ * is DZG_E_ARG. */
+typedef struct {
+    int64_t ncost;
+    const int64_t *cost_ptr;   /* ncost + 1                                   */
+    const int64_t *cost_idx;   /* variables                                   */
+    const double *cost_val;
+    int64_t nrhs;
+    const int64_t *rhs_ptr;    /* nrhs + 1                                    */
+    const int64_t *rhs_idx;    /* rows                                        */
+    const double *rhs_val;
+    double pivot_tol;
+} dzg_ranging_req;
+typedef struct {               /* every pointer is optional: NULL = not wanted */
+    double *cost_lo, *cost_hi;            /* ncost */
+    int64_t *cost_lo_var, *cost_hi_var;   /* ncost */
+    double *rhs_lo, *rhs_hi;              /* nrhs  */
+    int64_t *rhs_lo_var, *rhs_hi_var;     /* nrhs  */
+} dzg_ranging;
+
+/* dzg_solver_duals first (same preconditions and side effects: status DZG_OPTIMAL, a FAST solver
+ * refactorises its final basis and needs its refactorisation workspace), then the ranges of `req`;
+ * `duals` (optional) is filled as dzg_solver_duals fills it.  STRICT: the reference's LU::solve per
+ * direction, the batch's bits.  FAST (dense, one GPU): from the fresh inverse, cost directions as one
+ * fp64-MFMA product per chunk of directions whose ratio test runs in the epilogue.  The carried
+ * state is not touched; two calls on the same state return the same bits.  CSC storage and sharded
+ * solvers: DZG_E_ARG, "ranging is not supported ..." -- a range cannot be read off the carried z. */
+int dzg_solver_ranging(dzg_solver *s, const dzg_ranging_req *req, dzg_duals *duals, dzg_ranging *out);
+/* dzg_batch_solve_duals, then one workgroup per (LP, direction) over the LPs that ended OPTIMAL.
+ * req and rg hold `count` entries; res and du (optional) are what dzg_batch_solve_duals fills, bit
+ * for bit.  An LP that did not end OPTIMAL gets NaN ranges and *_var = -1. */
+int dzg_batch_solve_ranging(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                            int64_t pivots_per_launch, const dzg_ranging_req *req, dzg_result *res,
+                            dzg_duals *du, dzg_ranging *rg);
+
+/* Ranging in the user's terms.  Cost direction i moves the objective coefficient of user variable
+ * var[i]: +1 on x+ and -1 on x- of the split Simplex::new makes.  Right-hand-side direction i is a
+ * group of user rows with coefficients, CSR: rows row_idx[row_ptr[i] .. row_ptr[i+1]).  A variable
+ * that appears nowhere in the model, an index out of range or repeated inside one group: DZG_E_ARG.
+ * The results are in the core sense (the model is maximised, rows are coef.x <= b) and *_var are
+ * variables of the standard form. */
+typedef struct {
+    int64_t nvar;
+    const int64_t *var;        /* nvar user variables                         */
+    int64_t nrow;
+    const int64_t *row_ptr;    /* nrow + 1                                    */
+    const int64_t *row_idx;    /* user rows                                   */
+    const double *row_coef;
+    double pivot_tol;
+} dzg_model_ranging_req;
+/* dzg_model_solve_duals / dzg_model_solve_batch_duals, then the ranges (rg->cost_* by requested
+ * variable, rg->rhs_* by requested group).  NaN ranges unless the status is DZG_OPTIMAL and the
+ * duals could be computed.  When dzg_solver_ranging itself fails after an OPTIMAL solve, the call
+ * returns its code with its text in dzg_last_error: DZG_E_ARG for a route without ranging (CSC
+ * storage), DZG_E_NOMEM, DZG_E_DEVICE (the final basis of a FAST run did not refactorise); res then
+ * still holds the solve's outcome. */
+int dzg_model_solve_ranging(const dzg_model *model, const dzg_opts *opts,
+                            const dzg_model_ranging_req *req, dzg_model_result *res,
+                            dzg_model_duals *du, dzg_ranging *rg);
+int dzg_model_solve_batch_ranging(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                  const dzg_model_ranging_req *req, dzg_model_result *res,
+                                  dzg_model_duals *du, dzg_ranging *rg);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
