@@ -44,11 +44,14 @@ EXPORTS = [
     "dzg_model_solve_batch_duals", "dzg_model_map_duals",
     "dzg_solver_ranging", "dzg_batch_solve_ranging", "dzg_model_solve_ranging",
     "dzg_model_solve_batch_ranging",
+    "dzg_solver_ray", "dzg_batch_solve_rays", "dzg_model_solve_rays", "dzg_model_solve_batch_rays",
+    "dzg_model_map_ray",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
 DUALS_FRESH, DUALS_CARRIED = 1, 2
 DUALS_SOURCE_NAMES = {DUALS_FRESH: "fresh", DUALS_CARRIED: "carried"}
+RAY_PRIMAL, RAY_FARKAS = 1, 2  # DZG_RAY_PRIMAL, DZG_RAY_FARKAS
 
 
 class Lp(C.Structure):
@@ -134,6 +137,17 @@ class Ranging(C.Structure):
     _fields_ = [("cost_lo", C.c_void_p), ("cost_hi", C.c_void_p), ("cost_lo_var", C.c_void_p),
                 ("cost_hi_var", C.c_void_p), ("rhs_lo", C.c_void_p), ("rhs_hi", C.c_void_p),
                 ("rhs_lo_var", C.c_void_p), ("rhs_hi_var", C.c_void_p)]
+
+
+class Ray(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("proven", C.c_int32), ("var", C.c_int64), ("pos", C.c_int64),
+                ("mu", C.c_double), ("value", C.c_double), ("violation", C.c_double),
+                ("d", C.c_void_p), ("y", C.c_void_p)]
+
+
+class ModelRay(C.Structure):
+    _fields_ = [("var", C.c_void_p), ("con", C.c_void_p), ("lb", C.c_void_p), ("ub", C.c_void_p),
+                ("core", Ray)]
 
 
 class ModelRangingReq(C.Structure):
@@ -253,6 +267,14 @@ def lib() -> C.CDLL:
                                                  C.c_void_p]
         _lib.dzg_model_solve_batch_ranging.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                        C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_solver_ray.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_solve_rays.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        _lib.dzg_model_solve_rays.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_model_solve_batch_rays.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]
+        _lib.dzg_model_map_ray.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
+                                           C.c_int64, C.c_void_p]
         _lib.dzg_mip_opts_default.restype = None
         _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -327,6 +349,15 @@ class RangingBuffers:
         n = self.nc if which == 0 else self.nr
         return (self.lo[which][:n].copy(), self.hi[which][:n].copy(), self.lo_var[which][:n].copy(),
                 self.hi_var[which][:n].copy())
+
+
+def check_ray(rc: int, what: str) -> int:
+    """check(), but a route without rays (the C call says so) is a NotImplementedError."""
+    if rc < 0:
+        msg = lib().dzg_last_error().decode()
+        if "rays are not supported" in msg:
+            raise NotImplementedError(f"{what}: {msg}")
+    return check(rc, what)
 
 
 def check_ranging(rc: int, what: str) -> int:

@@ -156,6 +156,7 @@ class CoreResult:
     state_drift: float = 0.0            # carried x, xbar, z, zbar vs the fresh inverse at the last refactorisation
     duals: "CoreDuals | None" = None    # solve_batch(duals=True): the LP's duals if it ended optimal
     ranging: "CoreRanging | None" = None  # solve_batch(ranging=...): the LP's ranges if it ended optimal
+    ray: "CoreRay | None" = None        # solve_batch(rays=True): the LP's ray if it ended unbounded or infeasible
 
 
 @dataclass
@@ -202,6 +203,35 @@ def _ranging_dirs(dirs, count: int) -> list:
     if dirs is None:
         return [{j: 1.0} for j in range(count)]
     return [dict(d) for d in dirs]
+
+
+@dataclass
+class CoreRay:
+    """What a solve that ended unbounded or infeasible shows for it, core sense (dzg_ray).  kind
+    "primal": d is a direction with [A | I] d = 0 that gains `value` per unit; kind "farkas": y are
+    row multipliers, d = y^T [A | I] the aggregated row and value = rhs0 . y.  var / pos: the
+    variable find_first_pivot chose and its position, mu its ratio.  violation: the largest entry of d
+    below zero, as a positive number (NaN if the vector holds a NaN).  proven: violation == 0 and
+    value > 0 (primal) or value < 0 (farkas)."""
+    kind: str
+    kind_code: int
+    proven: bool
+    var: int
+    pos: int
+    mu: float
+    value: float
+    violation: float
+    d: np.ndarray
+    y: np.ndarray
+
+
+_RAY_KIND_NAMES = {_ffi.RAY_PRIMAL: "primal", _ffi.RAY_FARKAS: "farkas"}
+
+
+def _core_ray(u, d, y) -> CoreRay:
+    return CoreRay(kind=_RAY_KIND_NAMES[int(u.kind)], kind_code=int(u.kind), proven=bool(u.proven),
+                   var=int(u.var), pos=int(u.pos), mu=float(u.mu), value=float(u.value),
+                   violation=float(u.violation), d=d, y=y)
 
 
 def _core_duals(u, y, d) -> CoreDuals:
@@ -342,6 +372,18 @@ class Solver:
                            "dzg_solver_ranging")
         return _core_ranging(buf, _core_duals(u, y[:m].copy(), d[:n].copy()))
 
+    def ray(self) -> CoreRay:
+        """dzg_solver_ray: the primal ray of the basis an UNBOUNDED solve stopped on, or the Farkas ray
+        of an INFEASIBLE one, recomputed from that basis with its sign conditions checked
+        (`.proven`).  A FAST solver refactorises the basis for it (create it with
+        refactor_interval != 0); CSC and sharded solvers: NotImplementedError."""
+        m, n = self._lp.m, self._lp.n
+        d, y = np.zeros(max(n, 1)), np.zeros(max(m, 1))
+        u = _ffi.Ray()
+        u.d, u.y = ptr(d), ptr(y)
+        _ffi.check_ray(_ffi.lib().dzg_solver_ray(self._h, C.byref(u)), "dzg_solver_ray")
+        return _core_ray(u, d[:n].copy(), y[:m].copy())
+
     def debug_inverse(self, row0: int, row1: int) -> tuple[np.ndarray, dict]:
         """Test hook (dzg_debug_basis_inverse): rows [row0, row1) of the basis inverse FAST keeps --
         row i is basis position row0 + i, column r constraint row r -- and
@@ -412,7 +454,8 @@ _PIVOT_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("entering", "<i8
 
 
 def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
-                duals: bool = False, ranging=False, pivot_tol: float = 0.0, **opts) -> list:
+                duals: bool = False, ranging=False, pivot_tol: float = 0.0, rays: bool = False,
+                **opts) -> list:
     """dzg_batch_solve: every LP of `lps` in STRICT numerics, one workgroup per LP, in one call.
 
     The whole batch is checked on the host first (ValueError: more than 128 rows, CSC input, FAST
@@ -423,13 +466,16 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
     CoreDuals for an LP that ended optimal and None otherwise.  ranging=True, or one request per LP
     as (cost_dirs, rhs_dirs) with the meaning of Solver.ranging (dzg_batch_solve_ranging): every
     result gains `.ranging`, a CoreRanging, and `.duals` as well; None for an LP that did not end
-    optimal."""
+    optimal.  rays=True (dzg_batch_solve_rays; composes with duals, not with ranging): every result
+    gains `.ray`, a CoreRay for an LP that ended unbounded or infeasible and None otherwise."""
     import time
 
     lps = list(lps)
     numerics = opts.get("numerics", AUTO)
     if numerics not in (STRICT, AUTO):
         raise ValueError("solve_batch runs STRICT numerics only (numerics=STRICT or AUTO)")
+    if rays and ranging is not False and ranging is not None:
+        raise ValueError("rays=True and ranging: the ranging call carries no ray; ask in two calls")
     for i, lp in enumerate(lps):
         if lp.block is not None:
             raise ValueError(f"lps[{i}]: a column-block LP cannot be batched")
@@ -479,8 +525,19 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         for i in range(count):
             du[i].y = y_all.ctypes.data + 8 * int(mo[i])
             du[i].d = d_all.ctypes.data + 8 * int(no[i])
+    if rays:
+        ns_r = [lp.n for lp in lps]
+        ro = np.concatenate([[0], np.cumsum(ns_r)]).astype(np.int64)
+        rd_all, ry_all = np.zeros(ro[-1] + 1), np.zeros(mo[-1] + 1)
+        ry = (_ffi.Ray * max(count, 1))()
+        for i in range(count):
+            ry[i].d = rd_all.ctypes.data + 8 * int(ro[i])
+            ry[i].y = ry_all.ctypes.data + 8 * int(mo[i])
     t0 = time.perf_counter()
-    if want_ranging:
+    if rays:
+        rc = _ffi.lib().dzg_batch_solve_rays(c_lps, C.c_int64(count), C.byref(o),
+                                             C.c_int64(int(pivots_per_launch)), res, du if duals else None, ry)
+    elif want_ranging:
         rc = _ffi.lib().dzg_batch_solve_ranging(c_lps, C.c_int64(count), C.byref(o),
                                                 C.c_int64(int(pivots_per_launch)), c_req, res, du, c_rg)
     elif duals:
@@ -490,7 +547,7 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         rc = _ffi.lib().dzg_batch_solve(c_lps, C.c_int64(count), C.byref(o),
                                         C.c_int64(int(pivots_per_launch)), res)
     wall_ms = (time.perf_counter() - t0) * 1e3
-    _ffi.check_ranging(rc, "dzg_batch_solve_ranging" if want_ranging else
+    _ffi.check_ranging(rc, "dzg_batch_solve_rays" if rays else "dzg_batch_solve_ranging" if want_ranging else
                        ("dzg_batch_solve_duals" if duals else "dzg_batch_solve"))
     out = []
     for i in range(count):
@@ -511,6 +568,8 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
                 du[i], y_all[a0:a1].copy(), d_all[int(no[i]):int(no[i + 1])].copy())
         if want_ranging and out[-1].duals is not None:
             out[-1].ranging = _core_ranging(bufs[i], out[-1].duals)
+        if rays and ry[i].kind != 0:
+            out[-1].ray = _core_ray(ry[i], rd_all[int(ro[i]):int(ro[i + 1])].copy(), ry_all[a0:a1].copy())
     return out
 
 

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "duals.h"
 #include "ranging.h"
+#include "rays.h"
 
 static thread_local std::string g_err;
 
@@ -133,6 +134,8 @@ struct dzg_solver {
            *du_d = nullptr, *du_out = nullptr;
     int *du_codes = nullptr;
     DzgCtl *du_ctl = nullptr; // STRICT: a control block that reads DZG_RUNNING for the LU kernels
+    // dzg_solver_ray (k_rays.hip): dx or dz, d by variable, the finish kernel's partial records
+    double *ry_vec = nullptr, *ry_d = nullptr, *ry_part = nullptr, *ry_h = nullptr, *ry_res = nullptr;
     // FAST, dense, one GPU: the three-launch chain (k_chain.hip)
     unsigned long long *chain_bar = nullptr; // barrier counters (cleared only by chain_recover)
     unsigned long long *chain_dbg = nullptr; // DZG_CHAIN_DEBUG=1: phase clocks of workgroup 0
@@ -1097,8 +1100,11 @@ static int refactor_stage_a(dzg_solver *s, int counts[2], bool *active, bool at_
     TRY(read_ctl(s));
     *active = s->h_ctl->status == DZG_RUNNING || s->h_ctl->status == DZG_ITER_LIMIT ||
               s->h_ctl->status == DZG_NEAR_TIE;
-    // (at_end: dzg_solver_duals wants the fresh inverse of the OPTIMAL basis)
-    if (at_end && s->h_ctl->status == DZG_OPTIMAL) *active = true;
+    // (at_end: dzg_solver_duals wants the fresh inverse of the OPTIMAL basis, dzg_solver_ray that of
+    // the basis an UNBOUNDED or INFEASIBLE solve stopped on)
+    if (at_end && (s->h_ctl->status == DZG_OPTIMAL || s->h_ctl->status == DZG_UNBOUNDED ||
+                   s->h_ctl->status == DZG_INFEASIBLE))
+        *active = true;
     if (!*active) return 0;
     if (counts[0] != s->h_ctl->ncompact)
         return fail(DZG_E_DEVICE, "refactor: structural basics != dense columns");
@@ -2587,6 +2593,163 @@ extern "C" int dzg_solver_ranging(dzg_solver *s, const dzg_ranging_req *req, dzg
     return 0;
 }
 
+// ---- unboundedness and infeasibility rays (k_rays.hip) ------------------------
+void dzg_ray_none(dzg_ray *ry)
+{
+    ry->kind = 0;
+    ry->proven = 0;
+    ry->var = ry->pos = -1;
+    ry->mu = ry->value = ry->violation = 0.0;
+}
+
+// find_first_pivot (src/simplex.rs:423-437) on the host
+static int first_pivot_host(const std::vector<double> &y, const std::vector<double> &ybar, int len)
+{
+    int best = -1;
+    double best_ratio = 0.0;
+    for (int k = 0; k < len; ++k) {
+        if (!(ybar[(size_t)k] > 0.0)) continue;
+        const double ratio = -y[(size_t)k] / ybar[(size_t)k];
+        if (best < 0 || ratio > best_ratio) {
+            best = k;
+            best_ratio = ratio;
+        }
+    }
+    return best;
+}
+
+extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
+{
+    if (!s || !out) return fail(DZG_E_ARG, "ray: NULL argument");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    const int status = s->h_ctl->status;
+    if (status != DZG_UNBOUNDED && status != DZG_INFEASIBLE)
+        return fail(DZG_E_ARG, "ray: the solver's status is neither DZG_UNBOUNDED nor DZG_INFEASIBLE");
+    const DzgDev &d = s->d;
+    if (d.csc || d.world > 1)
+        return fail(DZG_E_ARG, "rays are not supported on CSC storage or sharded solvers");
+    const bool fast = s->numerics == DZG_NUMERICS_FAST;
+    if (fast && !s->rf_piv)
+        return fail(DZG_E_ARG, "ray: a FAST solver needs its refactorisation workspace: create it "
+                               "with opts.refactor_interval != 0");
+    const int m = d.m, q = d.q, n = d.n;
+    const bool primal = status == DZG_UNBOUNDED;
+    hipStream_t st = s->st;
+    std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1));
+    if (m) HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
+    if (q) HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
+    const int len = primal ? q : m;
+    std::vector<double> side((size_t)(len ? len : 1)), sidebar((size_t)(len ? len : 1));
+    if (len) {
+        HIP_OK(hipMemcpy(side.data(), primal ? d.z : d.x, sizeof(double) * len, hipMemcpyDeviceToHost));
+        HIP_OK(hipMemcpy(sidebar.data(), primal ? d.zbar : d.xbar, sizeof(double) * len, hipMemcpyDeviceToHost));
+    }
+    const int pos = first_pivot_host(side, sidebar, len);
+    if (pos < 0 || m == 0) return fail(DZG_E_DEVICE, "ray: the final state has no first pivot");
+    const int var = primal ? nonbasis[(size_t)pos] : basis[(size_t)pos];
+
+    TRY(duals_workspace(s));
+    if (!s->ry_part) {
+        TRY(dev_alloc(s, &s->ry_vec, (size_t)std::max(m, q) + 2));
+        TRY(dev_alloc(s, &s->ry_d, (size_t)n));
+        TRY(dev_alloc(s, &s->ry_h, (size_t)m + 2)); TRY(dev_alloc(s, &s->ry_res, (size_t)m + 2));
+        TRY(dev_alloc(s, &s->ry_part, (size_t)DZG_RAY_BLOCKS * DZG_RAY_PART)); // set last: "reserved"
+    }
+    if (fast) {
+        // a fresh inverse of the final basis (the eta file emptied): dx is a_j through its columns,
+        // y its row `pos` in row space, each refined once against a double-double residual (the
+        // explicit inverse alone loses |M| |a| eps where the entering column nearly cancels a basic
+        // one); dz one column-wise pricing pass with y as v
+        TRY(refactor_now(s, true));
+        TRY(read_ctl(s));
+        if (s->h_ctl->status != status) { // k_ref_done met a singular block: the solve's outcome stays
+            HIP_OK(hipMemcpy(&d.ctl->status, &status, sizeof(int), hipMemcpyHostToDevice));
+            s->h_ctl->status = status;
+            return fail(DZG_E_DEVICE, "ray: the final basis did not refactorise (singular block)");
+        }
+        const int k = (int)s->h_ctl->ncompact;
+        if (primal) {
+            dzg_launch_ray_rhs(m, d.A, d.lda, s->var_col_host[(size_t)var], s->ry_h, st);
+            dzg_launch_ray_dx_fast(d, k, s->ry_h, 0, s->ry_vec, st);
+            dzg_launch_ray_resid_dx(d, s->ry_h, s->ry_vec, s->ry_res, st);
+            dzg_launch_ray_dx_fast(d, k, s->ry_res, 1, s->ry_vec, st);
+        } else {
+            dzg_launch_ray_rhs(m, nullptr, 0, pos, s->ry_h, st);
+            dzg_launch_ray_vt_fast(d, k, s->ry_h, 0, s->du_y, st);
+            dzg_launch_ray_resid_v(d, pos, s->du_y, s->ry_res, st);
+            dzg_launch_ray_vt_fast(d, k, s->ry_res, 1, s->du_y, st);
+            dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->ry_vec, st);
+        }
+    } else {
+        // the LU of every STRICT FTRAN / BTRAN on a copy of the device view whose control block reads
+        // DZG_RUNNING (the solver's own reads UNBOUNDED / INFEASIBLE and is left alone), then
+        // neg_t_dot in the reference's order
+        DzgDev dd = d;
+        dd.ctl = s->du_ctl;
+        dd.v = s->du_y;
+        dd.dx = s->ry_vec;
+        if (primal) {
+            dzg_launch_ray_rhs(m, d.A, d.lda, s->var_col_host[(size_t)var], s->ry_vec, st);
+            dzg_launch_strict_solve(dd, 0, st);
+        } else {
+            std::vector<int> codes((size_t)(q ? q : 1));
+            for (int k = 0; k < q; ++k) codes[(size_t)k] = s->var_col_host[(size_t)nonbasis[(size_t)k]];
+            if (q) HIP_OK(hipMemcpyAsync(s->du_codes, codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, st));
+            HIP_OK(hipStreamSynchronize(st)); // (codes is a local)
+            dzg_launch_ray_rhs(m, nullptr, 0, pos, s->du_y, st);
+            dzg_launch_strict_solve(dd, 1, st);
+            dzg_launch_price_raw(DZG_PRICE_SEQ, m, d.lda, d.A, s->du_codes, q, s->du_y, s->ry_vec, st);
+        }
+    }
+    dzg_launch_ray_finish(primal ? DZG_RAY_PRIMAL : DZG_RAY_FARKAS, m, q, pos, d.basis, d.nonbasis, s->ry_vec,
+                          s->du_c, s->du_rhs0, s->du_y, s->ry_d, s->ry_part, st);
+    std::vector<double> part((size_t)DZG_RAY_BLOCKS * DZG_RAY_PART), vec((size_t)(m ? m : 1), 0.0),
+        dv((size_t)(n ? n : 1), 0.0);
+    HIP_OK(hipMemcpyAsync(part.data(), s->ry_part, sizeof(double) * part.size(), hipMemcpyDeviceToHost, st));
+    // (the vector the reference's value is summed over: dx, or y)
+    HIP_OK(hipMemcpyAsync(vec.data(), primal ? s->ry_vec : s->du_y, sizeof(double) * m, hipMemcpyDeviceToHost, st));
+    if (n) HIP_OK(hipMemcpyAsync(dv.data(), s->ry_d, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    double viol = 0.0, bad = 0.0, sum = 0.0;
+    for (int b = 0; b < DZG_RAY_BLOCKS; ++b) { // workgroup order
+        const double *r = &part[(size_t)b * DZG_RAY_PART];
+        viol = std::max(viol, r[0]);
+        bad = std::max(bad, r[1]);
+        sum = sum + r[2];
+    }
+    double value;
+    if (fast) {
+        value = primal ? s->c_host[(size_t)var] - sum : sum;
+    } else if (primal) { // the reference's order: one rounded product and one rounded difference each
+        value = s->c_host[(size_t)var];
+        for (int p = 0; p < m; ++p) {
+            const double prod = s->c_host[(size_t)basis[(size_t)p]] * vec[(size_t)p];
+            value = value - prod;
+        }
+    } else {
+        value = 0.0;
+        for (int i = 0; i < m; ++i) {
+            const double prod = s->x0_host[(size_t)i] * vec[(size_t)i];
+            value = value + prod;
+        }
+    }
+    out->kind = primal ? DZG_RAY_PRIMAL : DZG_RAY_FARKAS;
+    out->var = var;
+    out->pos = pos;
+    out->mu = -side[(size_t)pos] / sidebar[(size_t)pos];
+    out->value = value;
+    out->violation = bad != 0.0 ? std::numeric_limits<double>::quiet_NaN() : viol;
+    out->proven = out->violation == 0.0 && (primal ? value > 0.0 : value < 0.0) ? 1 : 0;
+    if (out->d && n) std::memcpy(out->d, dv.data(), sizeof(double) * n);
+    if (out->y && m) {
+        if (primal) std::memset(out->y, 0, sizeof(double) * m);
+        else std::memcpy(out->y, vec.data(), sizeof(double) * m);
+    }
+    return 0;
+}
+
 // What a one-call solve wants beyond the result: the duals and, with `req`, the ranges of the solver
 // that produced it.  rg_rc: what dzg_solver_ranging returned for an OPTIMAL solve (0 otherwise).
 struct SolveExtras {
@@ -2594,6 +2757,7 @@ struct SolveExtras {
     const dzg_ranging_req *req = nullptr;
     dzg_ranging *rg = nullptr;
     int rg_rc = 0;
+    dzg_ray *ry = nullptr; // the ray of a solve that ended UNBOUNDED or INFEASIBLE (kind 0 otherwise)
 };
 
 // (status, result and, when asked for and the LP ended OPTIMAL, the duals and ranges of this solver)
@@ -2616,6 +2780,13 @@ static int finish_solver(dzg_solver *s, int rc, dzg_result *res, SolveExtras &ex
         // message in dzg_last_error
         if (res->status != DZG_OPTIMAL || dzg_solver_duals(s, ex.du) != 0) dzg_duals_none(ex.du, res->objective);
     }
+    if (rc2 == 0 && ex.ry) {
+        // as with the duals, the solve's outcome stands whatever becomes of the ray: a route without
+        // rays or a final basis that did not refactorise leaves kind = 0 and its message in
+        // dzg_last_error
+        const bool ended = res->status == DZG_UNBOUNDED || res->status == DZG_INFEASIBLE;
+        if (!ended || dzg_solver_ray(s, ex.ry) != 0) dzg_ray_none(ex.ry);
+    }
     dzg_solver_destroy(s);
     return rc2 != 0 ? rc2 : rc;
 }
@@ -2636,7 +2807,7 @@ static int solve_once(const dzg_lp *lp, const dzg_opts *o, dzg_result *res, Solv
 // dzg_core_solve; with ex.du / ex.rg also the duals / ranges of whichever solver produced the result
 static int core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, SolveExtras &ex)
 {
-    const bool fresh = ex.du || ex.rg; // the final basis will be refactorised
+    const bool fresh = ex.du || ex.rg || ex.ry; // the final basis will be refactorised
     if (!res) return fail(DZG_E_ARG, "res is NULL");
     if (!lp) return fail(DZG_E_ARG, "lp is NULL");
     dzg_opts o;
@@ -2715,6 +2886,16 @@ int dzg_core_solve_with_ranging(const dzg_lp *lp, const dzg_opts *opts, dzg_resu
     const int rc = core_solve(lp, opts, res, ex);
     if (rg_rc) *rg_rc = ex.rg_rc;
     return rc;
+}
+
+// (model.cpp) du is optional
+int dzg_core_solve_with_rays(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du,
+                             dzg_ray *ry)
+{
+    SolveExtras ex;
+    ex.du = du;
+    ex.ry = ry;
+    return core_solve(lp, opts, res, ex);
 }
 
 extern "C" int dzg_core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res)

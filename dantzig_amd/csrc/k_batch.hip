@@ -35,6 +35,7 @@
 #include "common.h"
 #include "duals.h"
 #include "ranging.h"
+#include "rays.h"
 
 int dzg_set_error(int code, const std::string &msg); // engine.hip
 int dzg_lp_valid(const dzg_lp *lp, std::string &why);
@@ -145,10 +146,12 @@ struct Section {
 // dzg_batch_solve; with `du` the duals of the LPs that end OPTIMAL follow in the same allocation
 // (k_duals.hip), after the solve and on sections of their own: the solve's layout does not move
 // With `req` / `rg` the ranges of the OPTIMAL LPs follow the duals (k_ranging.hip), in an allocation
-// of their own.
+// of their own.  With `ry` the rays of the LPs that end UNBOUNDED or INFEASIBLE follow (k_rays.hip), on
+// sections behind those of the duals.
 static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots_per_launch,
                        dzg_result *res, dzg_duals *du, bool want_duals, const dzg_ranging_req *req = nullptr,
-                       dzg_ranging *rg = nullptr, bool want_ranging = false)
+                       dzg_ranging *rg = nullptr, bool want_ranging = false, dzg_ray *ry = nullptr,
+                       bool want_rays = false)
 {
     std::vector<dzg_duals> du_own; // ranging needs the fresh d on the device; the caller may not want it
     if (want_ranging && !du && count > 0 && count < (1ll << 31)) {
@@ -164,6 +167,7 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
     if (count >= (1ll << 31)) return dzg_set_error(DZG_E_ARG, "batch: count out of range");
     if (pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "batch: pivots_per_launch < 0");
     if (count > 0 && want_ranging && (!req || !rg)) return dzg_set_error(DZG_E_ARG, "batch: req or rg is NULL");
+    if (count > 0 && want_rays && !ry) return dzg_set_error(DZG_E_ARG, "batch: ry is NULL");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
     if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_AUTO)
@@ -244,8 +248,9 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
                   s_count = section(sizeof(int) * kBuckets);
     // duals: c and the starting x go up, the OPTIMAL LPs' list goes up after the solve, y, d and the
     // scalars come down
+    // (the rays read the same descriptors, c and starting x)
     Section s_dlp, s_c, s_x0, s_dlist, s_y, s_d, s_scal;
-    if (want_duals) {
+    if (want_duals || want_rays) {
         s_dlp = section(sizeof(DzgDualsLp) * N);
         s_c = section(sizeof(double) * nvc);
         s_x0 = section(sizeof(double) * nm);
@@ -253,6 +258,16 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
         s_y = section(sizeof(double) * nm);
         s_d = section(sizeof(double) * nvc);
         s_scal = section(sizeof(double) * DZG_DUALS_SCAL * N);
+    }
+    const size_t duals_end = top;
+    // rays: the list of the LPs that ended UNBOUNDED or INFEASIBLE goes up after the solve, d, y and the
+    // scalars come down
+    Section s_rlist, s_rd, s_ry, s_rscal;
+    if (want_rays) {
+        s_rlist = section(sizeof(int) * N);
+        s_rd = section(sizeof(double) * nvc);
+        s_ry = section(sizeof(double) * nm);
+        s_rscal = section(sizeof(double) * DZG_RAY_SCAL * N);
     }
 
     std::vector<unsigned char> host(download_end, 0);
@@ -309,8 +324,8 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
     BHIP(hipMalloc((void **)&dev, top));
     BHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
     std::vector<unsigned char> dhost; // s_dlp .. s_x0 as uploaded, then s_y .. s_scal as downloaded
-    if (want_duals) {
-        dhost.assign(top - s_dlp.off, 0);
+    if (want_duals || want_rays) {
+        dhost.assign(duals_end - s_dlp.off, 0);
         DzgDualsLp *dl = (DzgDualsLp *)dhost.data();
         double *cc = (double *)(dhost.data() + (s_c.off - s_dlp.off));
         double *x0 = (double *)(dhost.data() + (s_x0.off - s_dlp.off));
@@ -414,8 +429,54 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
                 dzg_launch_duals_small(b, a, (const int *)(dev + s_dlist.off) + dseg[(size_t)b], cnt, st);
                 BHIP(hipGetLastError());
             }
-            BHIP(hipMemcpyAsync(dhost.data() + (s_y.off - s_dlp.off), dev + s_y.off, top - s_y.off,
+            BHIP(hipMemcpyAsync(dhost.data() + (s_y.off - s_dlp.off), dev + s_y.off, duals_end - s_y.off,
                                 hipMemcpyDeviceToHost, st));
+            BHIP(hipStreamSynchronize(st));
+        }
+    }
+
+    // ---- rays of the LPs that ended UNBOUNDED or INFEASIBLE: one workgroup each, bucket by bucket, on
+    // the final state as it lies on the device (g.dz is the solve's scratch)
+    std::vector<unsigned char> ryhost; // s_rd .. s_rscal as downloaded
+    if (want_rays) {
+        const int *stat = (const int *)hp(s_status);
+        std::vector<int> rlist;
+        std::vector<int> rseg(kBuckets + 1, 0);
+        for (int b = 0; b < kBuckets; ++b) {
+            for (int i = 0; i < N; ++i)
+                if ((stat[i] == DZG_UNBOUNDED || stat[i] == DZG_INFEASIBLE) && bucket_of(lps[i].m) == b)
+                    rlist.push_back(i);
+            rseg[(size_t)b + 1] = (int)rlist.size();
+        }
+        ryhost.assign(top - s_rd.off, 0);
+        if (!rlist.empty()) {
+            BHIP(hipMemcpyAsync(dev + s_rlist.off, rlist.data(), sizeof(int) * rlist.size(),
+                                hipMemcpyHostToDevice, st));
+            DzgRaysArgs a;
+            a.lp = (const DzgDualsLp *)(dev + s_dlp.off);
+            a.A = g.A;
+            a.var_col = g.var_col;
+            a.basis = g.basis;
+            a.nonbasis = g.nonbasis;
+            a.x = g.x;
+            a.xbar = g.xbar;
+            a.z = g.z;
+            a.zbar = g.zbar;
+            a.status = g.status;
+            a.c = (const double *)(dev + s_c.off);
+            a.rhs0 = (const double *)(dev + s_x0.off);
+            a.dz = g.dz;
+            a.d = (double *)(dev + s_rd.off);
+            a.y = (double *)(dev + s_ry.off);
+            a.scal = (double *)(dev + s_rscal.off);
+            for (int b = 0; b < kBuckets; ++b) {
+                const int cnt = rseg[(size_t)b + 1] - rseg[(size_t)b];
+                if (cnt == 0) continue;
+                a.mmax = mmax[b];
+                dzg_launch_rays_small(b, a, (const int *)(dev + s_rlist.off) + rseg[(size_t)b], cnt, st);
+                BHIP(hipGetLastError());
+            }
+            BHIP(hipMemcpyAsync(ryhost.data(), dev + s_rd.off, top - s_rd.off, hipMemcpyDeviceToHost, st));
             BHIP(hipStreamSynchronize(st));
         }
     }
@@ -583,6 +644,27 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
         r.price_pass_used = 0;
         r.price_rows_copy = 0;
         r.state_drift = 0.0;
+        if (want_rays) {
+            dzg_ray &u = ry[i];
+            const double *sc = (const double *)(ryhost.data() + (s_rscal.off - s_rd.off)) + (size_t)DZG_RAY_SCAL * i;
+            if ((r.status != DZG_UNBOUNDED && r.status != DZG_INFEASIBLE) || sc[0] < 0.0) {
+                dzg_ray_none(&u);
+            } else {
+                const bool primal = r.status == DZG_UNBOUNDED;
+                u.kind = primal ? DZG_RAY_PRIMAL : DZG_RAY_FARKAS;
+                u.var = (int64_t)sc[0];
+                u.pos = (int64_t)sc[1];
+                u.mu = sc[2];
+                u.value = sc[3];
+                u.violation = sc[4];
+                u.proven = u.violation == 0.0 && (primal ? u.value > 0.0 : u.value < 0.0) ? 1 : 0;
+                if (u.d && lp.n)
+                    std::memcpy(u.d, (const double *)ryhost.data() + d.vc_off, sizeof(double) * (size_t)lp.n);
+                if (u.y && m)
+                    std::memcpy(u.y, (const double *)(ryhost.data() + (s_ry.off - s_rd.off)) + d.m_off,
+                                sizeof(double) * (size_t)m);
+            }
+        }
         if (want_ranging) {
             if (r.status != DZG_OPTIMAL) {
                 dzg_ranging_none(&req[i], &rg[i]);
@@ -648,4 +730,12 @@ extern "C" int dzg_batch_solve_ranging(const dzg_lp *lps, int64_t count, const d
                                        dzg_duals *du, dzg_ranging *rg)
 {
     return batch_solve(lps, count, opts, pivots_per_launch, res, du, true, req, rg, true);
+}
+
+extern "C" int dzg_batch_solve_rays(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                                    int64_t pivots_per_launch, dzg_result *res, dzg_duals *du, dzg_ray *ry)
+{
+    if (count > 0 && !ry) return dzg_set_error(DZG_E_ARG, "batch: ry is NULL");
+    return batch_solve(lps, count, opts, pivots_per_launch, res, du, du != nullptr, nullptr, nullptr, false, ry,
+                       true);
 }

@@ -404,12 +404,82 @@ static bool map_ranging_req(const dzg_model *md, const Built &b, const dzg_model
     return dzg_ranging_req_valid(&out.req, b.m, b.n, why); // duplicates inside a group, pivot_tol
 }
 
+// engine.hip
+void dzg_ray_none(dzg_ray *ry);
+int dzg_core_solve_with_rays(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, dzg_duals *du,
+                             dzg_ray *ry);
+
+// The one place that maps a core ray to the user's model.  Rows as map_duals walks them (user rows
+// first, then the bound rows by their tag); a row's entry is the d of its slack for a primal ray and
+// its y for a Farkas ray.
+static void map_ray(const dzg_model *md, const Built &b, int kind, const double *d, const double *y,
+                    dzg_model_ray *out)
+{
+    std::vector<int64_t> slack_var((size_t)(b.m ? b.m : 1), -1);
+    for (int64_t i = 0; i < b.n; ++i)
+        if (b.var_col[(size_t)i] < 0) slack_var[(size_t)(-1 - b.var_col[(size_t)i])] = i;
+    auto row = [&](int64_t r) { return kind == DZG_RAY_PRIMAL ? d[slack_var[(size_t)r]] : y[r]; };
+    for (int64_t r = 0; r < md->ncons; ++r) out->con[r] = row(r);
+    for (int64_t u = 0; u < md->nvars; ++u) {
+        out->lb[u] = 0.0;
+        out->ub[u] = 0.0;
+        out->var[u] = b.pos_var[(size_t)u] >= 0 ? d[b.pos_var[(size_t)u]] - d[b.neg_var[(size_t)u]] : 0.0;
+    }
+    for (int64_t r = md->ncons; r < b.m; ++r) {
+        const int64_t tag = b.row_tag[(size_t)r];
+        if (tag < 0) continue;
+        double *dst = (tag & 1) ? out->lb : out->ub;
+        dst[tag / 2] = row(r);
+    }
+}
+
+static bool ray_arrays_ok(const dzg_model *md, const dzg_model_ray *ry)
+{
+    return ry && (md->ncons == 0 || ry->con) && (md->nvars == 0 || (ry->var && ry->lb && ry->ub));
+}
+
+extern "C" int dzg_model_map_ray(const dzg_model *md, int32_t kind, const double *d, const double *y,
+                                 int64_t m, int64_t n, dzg_model_ray *out)
+{
+    if (!out || !valid(md)) return dzg_set_error(DZG_E_ARG, "map ray: out is NULL or the model is malformed");
+    if (kind != DZG_RAY_PRIMAL && kind != DZG_RAY_FARKAS)
+        return dzg_set_error(DZG_E_ARG, "map ray: kind is neither DZG_RAY_PRIMAL nor DZG_RAY_FARKAS");
+    if (!ray_arrays_ok(md, out)) return dzg_set_error(DZG_E_ARG, "map ray: var, con, lb or ub is NULL");
+    Built b;
+    build(md, b, true);
+    if (m != b.m || n != b.n || (n > 0 && !d) || (kind == DZG_RAY_FARKAS && m > 0 && !y))
+        return dzg_set_error(DZG_E_ARG, "map ray: d and y must hold the " + std::to_string(b.n) +
+                                            " variables and " + std::to_string(b.m) +
+                                            " rows of the model's standard form");
+    map_ray(md, b, kind, d, y, out);
+    return 0;
+}
+
+// What a solve's core ray (scalars; d in `dv`, y in `yv`) becomes in the caller's dzg_model_ray; the
+// caller's d / y pointers stay the caller's.
+static void adopt_ray(const dzg_model *md, const Built &b, const dzg_ray &core, const double *dv,
+                      const double *yv, dzg_model_ray *ry)
+{
+    double *ud = ry->core.d, *uy = ry->core.y;
+    if (core.kind == 0) {
+        dzg_ray_none(&ry->core);
+        return;
+    }
+    ry->core = core;
+    ry->core.d = ud;
+    ry->core.y = uy;
+    if (ud && b.n) std::memcpy(ud, dv, sizeof(double) * (size_t)b.n);
+    if (uy && b.m) std::memcpy(uy, yv, sizeof(double) * (size_t)b.m);
+    map_ray(md, b, core.kind, dv, yv, ry);
+}
+
 static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res,
                        dzg_model_duals *du, bool want_duals, const dzg_model_ranging_req *mreq = nullptr,
-                       dzg_ranging *rg = nullptr)
+                       dzg_ranging *rg = nullptr, dzg_model_ray *ry = nullptr)
 {
     if (!res || !valid(md)) return DZG_E_ARG;
     if (want_duals && (!du || (md->ncons > 0 && !du->con_dual))) return DZG_E_ARG;
+    if (ry && !ray_arrays_ok(md, ry)) return DZG_E_ARG;
     Built b;
     build(md, b, true);
     CoreRanging cr;
@@ -452,8 +522,14 @@ static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_resu
         core.y = yv.data();
         core.d = du->core.d;
     }
+    std::vector<double> ray_d((size_t)(ry && b.n ? b.n : 1), 0.0), ray_y((size_t)(ry && b.m ? b.m : 1), 0.0);
+    dzg_ray ray_core;
+    std::memset(&ray_core, 0, sizeof(ray_core));
+    ray_core.d = ray_d.data();
+    ray_core.y = ray_y.data();
     int rg_rc = 0;
     const int rc = rg ? dzg_core_solve_with_ranging(&lp, opts, &r, &core, &cr.req, rg, &rg_rc)
+                 : ry ? dzg_core_solve_with_rays(&lp, opts, &r, want_duals ? &core : nullptr, &ray_core)
                       : dzg_core_solve_with_duals(&lp, opts, &r, want_duals ? &core : nullptr);
     res->status = rc < 0 ? rc : r.status;
     res->numerics_used = r.numerics_used;
@@ -464,6 +540,7 @@ static int model_solve(const dzg_model *md, const dzg_opts *opts, dzg_model_resu
     if (rc < 0) return rc;
     if (res->values) solution_values(md, b, basis.data(), x.data(), res->values);
     if (want_duals) adopt_duals(md, b, r.status, r.objective, core, yv.data(), du);
+    if (ry) adopt_ray(md, b, ray_core, ray_d.data(), ray_y.data(), ry);
     // (ranging failed after an OPTIMAL solve -- a route without ranging, no memory, a final basis
     // that did not refactorise: the call fails with that code, dzg_last_error holds
     // dzg_solver_ranging's text; res keeps the solve's outcome)
@@ -492,7 +569,8 @@ extern "C" int dzg_model_solve_duals(const dzg_model *md, const dzg_opts *opts, 
 // extracted exactly as dzg_model_solve extracts them.
 static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
                              dzg_model_result *res, dzg_model_duals *du, bool want_duals,
-                             const dzg_model_ranging_req *mreq = nullptr, dzg_ranging *rg = nullptr)
+                             const dzg_model_ranging_req *mreq = nullptr, dzg_ranging *rg = nullptr,
+                             dzg_model_ray *ry = nullptr)
 {
     if (count > 0 && want_duals && rg && !mreq) return dzg_set_error(DZG_E_ARG, "model batch: req is NULL");
     if (count < 0) return dzg_set_error(DZG_E_ARG, "model batch: count < 0");
@@ -504,6 +582,9 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
     for (int64_t i = 0; i < count; ++i)
         if (!valid(&models[i]))
             return dzg_set_error(DZG_E_ARG, "model batch: models[" + std::to_string(i) + "] is malformed");
+    for (int64_t i = 0; ry && i < count; ++i)
+        if (!ray_arrays_ok(&models[i], &ry[i]))
+            return dzg_set_error(DZG_E_ARG, "model batch: ry[" + std::to_string(i) + "]: var, con, lb or ub is NULL");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
     const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
@@ -531,6 +612,8 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
     std::vector<std::vector<double>> x(nb);
     std::vector<std::vector<double>> yv(want_duals ? nb : 0);
     std::vector<dzg_duals> cores(want_duals ? nb : 0);
+    std::vector<std::vector<double>> ray_d(ry ? nb : 0), ray_y(ry ? nb : 0);
+    std::vector<dzg_ray> rays(ry ? nb : 0);
     for (size_t k = 0; k < nb; ++k) {
         const Built &b = built[(size_t)batched[k]];
         dzg_lp &lp = lps[k];
@@ -562,9 +645,18 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
             breq[k] = crs[(size_t)batched[k]].req;
             brg[k] = rg[batched[k]];
         }
+        if (ry) {
+            ray_d[k].assign((size_t)(b.n ? b.n : 1), 0.0);
+            ray_y[k].assign((size_t)(b.m ? b.m : 1), 0.0);
+            std::memset(&rays[k], 0, sizeof(dzg_ray));
+            rays[k].d = ray_d[k].data();
+            rays[k].y = ray_y[k].data();
+        }
     }
     if (nb > 0) {
-        const int rc = rg ? dzg_batch_solve_ranging(lps.data(), (int64_t)nb, &o, 0, breq.data(), rs.data(),
+        const int rc = ry ? dzg_batch_solve_rays(lps.data(), (int64_t)nb, &o, 0, rs.data(),
+                                                 want_duals ? cores.data() : nullptr, rays.data())
+                     : rg ? dzg_batch_solve_ranging(lps.data(), (int64_t)nb, &o, 0, breq.data(), rs.data(),
                                                     cores.data(), brg.data())
                      : want_duals ? dzg_batch_solve_duals(lps.data(), (int64_t)nb, &o, 0, rs.data(), cores.data())
                                   : dzg_batch_solve(lps.data(), (int64_t)nb, &o, 0, rs.data());
@@ -587,11 +679,12 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
             if (out.values) solution_values(&models[i], b, basis[k].data(), x[k].data(), out.values);
             if (want_duals)
                 adopt_duals(&models[i], b, r.status, r.objective, cores[k], yv[k].data(), &du[i]);
+            if (ry) adopt_ray(&models[i], b, rays[k], ray_d[k].data(), ray_y[k].data(), &ry[i]);
             ++k;
             continue;
         }
         const int rc = model_solve(&models[i], opts, &out, want_duals ? &du[i] : nullptr, want_duals,
-                                   rg ? &mreq[i] : nullptr, rg ? &rg[i] : nullptr);
+                                   rg ? &mreq[i] : nullptr, rg ? &rg[i] : nullptr, ry ? &ry[i] : nullptr);
         if (rc < 0) return rc;
     }
     return 0;
@@ -625,4 +718,21 @@ extern "C" int dzg_model_solve_batch_ranging(const dzg_model *models, int64_t co
 {
     if (count > 0 && (!req || !rg)) return dzg_set_error(DZG_E_ARG, "model batch: req or rg is NULL");
     return model_solve_batch(models, count, opts, res, du, true, req, rg);
+}
+
+extern "C" int dzg_model_solve_rays(const dzg_model *md, const dzg_opts *opts, dzg_model_result *res,
+                                    dzg_model_duals *du, dzg_model_ray *ry)
+{
+    if (!ry) return dzg_set_error(DZG_E_ARG, "model rays: ry is NULL");
+    if (!res || !valid(md)) return dzg_set_error(DZG_E_ARG, "model rays: res is NULL or the model is malformed");
+    if (du && md->ncons > 0 && !du->con_dual) return dzg_set_error(DZG_E_ARG, "model rays: con_dual is NULL");
+    if (!ray_arrays_ok(md, ry)) return dzg_set_error(DZG_E_ARG, "model rays: var, con, lb or ub is NULL");
+    return model_solve(md, opts, res, du, du != nullptr, nullptr, nullptr, ry);
+}
+
+extern "C" int dzg_model_solve_batch_rays(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                          dzg_model_result *res, dzg_model_duals *du, dzg_model_ray *ry)
+{
+    if (count > 0 && !ry) return dzg_set_error(DZG_E_ARG, "model batch: ry is NULL");
+    return model_solve_batch(models, count, opts, res, du, du != nullptr, nullptr, nullptr, ry);
 }

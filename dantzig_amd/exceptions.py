@@ -3,7 +3,10 @@
 
 
 class SolveError(Exception):
-    """A solve ended without an optimal vertex."""
+    """A solve ended without an optimal vertex.  `ray` is None unless the solve was asked for rays
+    (solve(rays=True)): then an UnboundedError carries a PrimalRay and an InfeasibleError a FarkasRay
+    (dantzig_amd.optimize), each with `proven`, which says whether the verdict checks out."""
+    ray = None
 
 
 class UnboundedError(SolveError):

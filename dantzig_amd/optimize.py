@@ -14,6 +14,7 @@ from dataclasses import dataclass
 from typing import Union
 
 from . import rust as rs
+from .exceptions import SolveError
 from .model import AffExpr, Constraint, LinExpr, Variable
 
 _SENSES = ("minimize", "maximize")
@@ -40,6 +41,92 @@ class Range:
     which the optimal basis holds (-inf / +inf where nothing blocks); the current value is inside."""
     lo: float
     hi: float
+
+
+class _Ray:
+    """Common to PrimalRay and FarkasRay: the model's constraints (kept alive, found by identity) and
+    the first row of each, as Solution keeps them."""
+
+    def __init__(self, *, ray: "rs.PyRay", sense: str, constraints) -> None:
+        self._ray = ray
+        self._sense = sense
+        self._rows: dict = {}
+        row = 0
+        for constraint in constraints:
+            self._rows.setdefault(id(constraint), (constraint, row))
+            row += len(constraint.rust_inequalities())
+
+    def _first_row(self, constraint: Constraint) -> int:
+        entry = self._rows.get(id(constraint))
+        if entry is None:
+            raise KeyError("the constraint is not part of the solved model")
+        return entry[1]
+
+    @property
+    def violation(self) -> float:
+        """How far the ray's sign conditions are missed (0.0: not at all; NaN: the ray holds a NaN)."""
+        return self._ray.violation
+
+    @property
+    def proven(self) -> bool:
+        """True when the ray, as computed, proves the verdict: no violation and the right sign of
+        objective_rate / rhs_value.  False: the solver said so, the ray does not show it."""
+        return self._ray.proven
+
+
+class PrimalRay(_Ray):
+    """UnboundedError.ray of a solve(rays=True): a direction along which every feasible point can move
+    for ever while the objective improves."""
+
+    def direction(self, variable: Variable) -> float:
+        return self._ray.var.get(variable.to_rust_variable().id, 0.0)
+
+    def slack_rate(self, constraint: Constraint) -> list:
+        """How fast the slack of each row of `constraint` (linexpr <= b as lowered) grows along the
+        ray; negative: the row would be left."""
+        first = self._first_row(constraint)
+        return [self._ray.con[first + k] for k in range(len(constraint._signs))]
+
+    @property
+    def objective_rate(self) -> float:
+        """The change of the objective per unit of the ray, in the user's sense: positive under
+        Maximize, negative under Minimize for a proven ray."""
+        return -self._ray.value if self._sense == "minimize" else self._ray.value
+
+    def __repr__(self) -> str:
+        return f"PrimalRay(proven={self.proven}, objective_rate={self.objective_rate!r}, violation={self.violation!r})"
+
+
+class FarkasRay(_Ray):
+    """InfeasibleError.ray of a solve(rays=True): multipliers >= 0 on the rows `linexpr <= b` whose
+    combination has coefficient zero on every variable and a negative right-hand side."""
+
+    def multiplier(self, constraint: Constraint) -> float:
+        """The multiplier of `constraint` in its normal form linexpr <=, >= or == b: >= 0 for <=, <= 0
+        for >=, either sign for ==."""
+        first = self._first_row(constraint)
+        value = 0.0
+        for k, sign in enumerate(constraint._signs):
+            value += sign * self._ray.con[first + k]
+        return value
+
+    def bound_multipliers(self, variable: Variable) -> tuple:
+        """(lb, ub): the multipliers of the rows -x <= -lb and x <= ub of `variable`, 0.0 where the
+        bound is absent."""
+        vid = variable.to_rust_variable().id
+        return self._ray.lb.get(vid, 0.0), self._ray.ub.get(vid, 0.0)
+
+    def aggregated(self, variable: Variable) -> float:
+        """The coefficient of `variable` in the combined row (zero up to rounding for a proof)."""
+        return self._ray.var.get(variable.to_rust_variable().id, 0.0)
+
+    @property
+    def rhs_value(self) -> float:
+        """The right-hand side of the combined row; negative for a proven ray."""
+        return self._ray.value
+
+    def __repr__(self) -> str:
+        return f"FarkasRay(proven={self.proven}, rhs_value={self.rhs_value!r}, violation={self.violation!r})"
 
 
 class Solution:
@@ -187,12 +274,33 @@ class Optimize(abc.ABC):
             row += n
         return groups
 
-    def solve(self, *, duals: bool = False, ranging: bool = False) -> Solution:
+    def _wrap_ray(self, exc: Exception) -> Exception:
+        """The exception of a solve(rays=True) with its core ray in this model's terms."""
+        ray = getattr(exc, "ray", None)
+        if isinstance(ray, rs.PyRay):
+            cls = PrimalRay if ray.kind == "primal" else FarkasRay
+            exc.ray = cls(ray=ray, sense=self.sense, constraints=list(self.constraints))
+        return exc
+
+    def solve(self, *, duals: bool = False, ranging: bool = False, rays: bool = False) -> Solution:
         """Solve on the GPU.  Raises exceptions.UnboundedError / InfeasibleError.  duals=True: the
         Solution also answers dual(), reduced_cost() and certificate (LPs only: ValueError for a
         model with an integer variable).  ranging=True (implies duals): also rhs_range() and
-        objective_range(); NotImplementedError where the solve's route has no ranging."""
+        objective_range(); NotImplementedError where the solve's route has no ranging.  rays=True
+        (composes with duals; ValueError with ranging or an integer variable): the UnboundedError
+        carries `.ray`, a PrimalRay, the InfeasibleError a FarkasRay; `.ray.proven` says whether the
+        verdict checks out.  `.ray` stays None where the solve's route has no rays."""
         objective, constraints = self._rust_problem()
+        if rays and ranging:
+            raise ValueError("rays=True and ranging=True: the ranging call carries no ray; ask in two calls")
+        if rays:
+            if rs._has_integer(objective, constraints):
+                raise ValueError("rays=True: rays are not defined for a model with integer variables")
+            try:
+                return Solution(solution=rs.solve(objective, constraints, duals=duals, rays=True),
+                                sense=self.sense, constraints=list(self.constraints) if duals else None)
+            except SolveError as exc:
+                raise self._wrap_ray(exc)
         if rs._has_integer(objective, constraints):
             if ranging:
                 raise ValueError("ranging=True: ranges are not defined for a model with integer variables")
@@ -224,22 +332,31 @@ class Maximize(Optimize):
     sense = property(lambda self: "maximize")
 
 
-def solve_many(problems, *, duals: bool = False, ranging: bool = False,
+def solve_many(problems, *, duals: bool = False, ranging: bool = False, rays: bool = False,
                return_exceptions: bool = False) -> list:
     """[p.solve() for p in problems] in one batched call (rust.solve_many): the small models share
     one launch on the GPU, one workgroup per model, bit for bit what p.solve() returns.  A model
     that is unbounded or infeasible raises the exception p.solve() raises, with the model's index
     in the message, after the whole batch is done; with return_exceptions=True the exception
     instance stands in that model's place.  duals=True: every Solution is p.solve(duals=True)'s;
-    ranging=True: p.solve(ranging=True)'s."""
+    ranging=True: p.solve(ranging=True)'s; rays=True: every exception is p.solve(rays=True)'s, `.ray`
+    included."""
     problems = list(problems)
     for i, p in enumerate(problems):
         if not isinstance(p, Optimize):
             raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
+    if rays and ranging:
+        raise ValueError("rays=True and ranging=True: the ranging call carries no ray; ask in two calls")
     duals = duals or ranging
     raw = rs.solve_many([p._rust_problem() for p in problems], duals=duals,
                         ranging=[p._row_groups() for p in problems] if ranging else False,
-                        return_exceptions=return_exceptions)
+                        rays=rays, return_exceptions=return_exceptions or rays)
+    if rays:  # (the core rays become the models' before anything is raised)
+        raw = [p._wrap_ray(r) if isinstance(r, Exception) else r for p, r in zip(problems, raw)]
+        if not return_exceptions:
+            for r in raw:
+                if isinstance(r, Exception):
+                    raise r
     return [r if isinstance(r, Exception)
             else Solution(solution=r, sense=p.sense, constraints=list(p.constraints) if duals else None,
                           objective=p.objective if ranging else None)

@@ -201,6 +201,21 @@ class PyRanging:
             setattr(self, k, kw.get(k))
 
 
+class PyRay:
+    """The ray of one solve(..., rays=True) that ended unbounded (kind "primal") or infeasible (kind
+    "farkas"), in the core sense (the model is maximised, every row is linexpr <= b), as
+    dzg_model_map_ray lays it out: var / lb / ub keyed by Variable.id, con[r] per inequality in the
+    order they were passed.  primal: var is the direction, con / lb / ub how fast each row's slack
+    grows along it, value the objective's gain per unit.  farkas: con / lb / ub are the rows'
+    multipliers, var the aggregated coefficient of each variable, value the aggregated right-hand
+    side.  violation and proven: dzg_ray's."""
+    __slots__ = ("kind", "proven", "value", "violation", "mu", "var", "con", "lb", "ub")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
 class PySolution:
     __slots__ = ("_objective_value", "_values", "iterations", "numerics", "shape", "mip", "duals",
                  "ranging")
@@ -293,6 +308,30 @@ class _DualBuffers:
                        dual_infeasibility=float(core.dual_infeas), z_diff=float(core.z_diff))
 
 
+class _RayBuffers:
+    """The caller-owned arrays of one dzg_model_ray and the struct that points at them."""
+
+    def __init__(self, arrays: dict):
+        nv, nc = arrays["nvars"], arrays["ncons"]
+        self.var, self.con = np.zeros(max(nv, 1)), np.zeros(max(nc, 1))
+        self.lb, self.ub = np.zeros(max(nv, 1)), np.zeros(max(nv, 1))
+        self.ncons = nc
+
+    def fill(self, c: "_ffi.ModelRay") -> None:
+        c.var, c.con = _ffi.ptr(self.var), _ffi.ptr(self.con)
+        c.lb, c.ub = _ffi.ptr(self.lb), _ffi.ptr(self.ub)
+
+    def pyray(self, c: "_ffi.ModelRay", order) -> "PyRay | None":
+        core = c.core
+        if core.kind == 0:
+            return None
+        by_id = lambda a: {v.id: float(a[i]) for i, v in enumerate(order)}  # noqa: E731
+        return PyRay(kind="primal" if core.kind == _ffi.RAY_PRIMAL else "farkas", proven=bool(core.proven),
+                     value=float(core.value), violation=float(core.violation), mu=float(core.mu),
+                     var=by_id(self.var), con=[float(v) for v in self.con[:self.ncons]],
+                     lb=by_id(self.lb), ub=by_id(self.ub))
+
+
 class _RangingBuffers:
     """One dzg_model_ranging_req over every variable of the lowered model and the given groups of
     rows (True: every inequality by itself), with the dzg_ranging it fills."""
@@ -357,16 +396,22 @@ def _want_ranging(ranging) -> bool:
 
 
 def solve(objective: PyAffExpr, constraints, duals: bool = False, ranging=False,
-          pivot_tol: float = 0.0) -> PySolution:
+          pivot_tol: float = 0.0, rays: bool = False) -> PySolution:
     """Maximise `objective` subject to `constraints` on the GPU (src/lib.rs:16-27).  duals=True
     (dzg_model_solve_duals): the same solution with .duals, a PyDuals.  ranging=True, or a list of
     groups [(row, coefficient), ...] of inequalities (dzg_model_solve_ranging): also .ranging, a
     PyRanging over every variable and every group (True: every inequality by itself); implies
-    duals.  NotImplementedError when the solve ends on a route without ranging (CSC storage)."""
+    duals.  NotImplementedError when the solve ends on a route without ranging (CSC storage).
+    rays=True (dzg_model_solve_rays; composes with duals, not with ranging): the UnboundedError or
+    InfeasibleError this raises carries .ray, a PyRay (None on a route without rays)."""
     if not isinstance(objective, PyAffExpr):
         raise TypeError("objective must be a PyAffExpr")
     constraints = list(constraints)
     want_ranging = _want_ranging(ranging)
+    if rays and want_ranging:
+        raise ValueError("rays=True and ranging: the ranging call carries no ray; ask in two calls")
+    if rays and _has_integer(objective, constraints):
+        raise ValueError("rays=True: rays are not defined for a model with integer variables")
     if want_ranging and _has_integer(objective, constraints):
         raise ValueError("ranging=True: ranges are not defined for a model with integer variables")
     duals = duals or want_ranging
@@ -382,7 +427,13 @@ def solve(objective: PyAffExpr, constraints, duals: bool = False, ranging=False,
     if duals:
         buf, cdu = _DualBuffers(arrays), _ffi.ModelDuals()
         buf.fill(cdu)
-    if want_ranging:
+    if rays:
+        ybuf, cry = _RayBuffers(arrays), _ffi.ModelRay()
+        ybuf.fill(cry)
+        rc = _ffi.lib().dzg_model_solve_rays(C.byref(md), C.byref(opts), C.byref(res),
+                                             C.byref(cdu) if duals else None, C.byref(cry))
+        _ffi.check(rc, "dzg_model_solve_rays")
+    elif want_ranging:
         rbuf, creq, crg = _RangingBuffers(arrays, order, ranging, pivot_tol), _ffi.ModelRangingReq(), _ffi.Ranging()
         rbuf.fill(creq, crg)
         rc = _ffi.lib().dzg_model_solve_ranging(C.byref(md), C.byref(opts), C.byref(creq), C.byref(res),
@@ -396,6 +447,8 @@ def solve(objective: PyAffExpr, constraints, duals: bool = False, ranging=False,
         _ffi.check(rc, "dzg_model_solve")
     out = _outcome(res, values, order)
     if isinstance(out, Exception):
+        if rays:
+            out.ray = ybuf.pyray(cry, order)
         raise out
     if duals:
         out.duals = buf.pyduals(cdu, order)
@@ -486,7 +539,7 @@ def solve_mip(objective: PyAffExpr, constraints, *, node_log: int = 0, **mip_opt
 
 
 def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float = 0.0,
-               return_exceptions: bool = False) -> list:
+               rays: bool = False, return_exceptions: bool = False) -> list:
     """solve() for every (objective, constraints) pair of `problems`, in one dzg_model_solve_batch
     call: the models that solve() would run in STRICT numerics on at most 128 rows share one batch
     on the GPU (one workgroup per model), the others are solved one at a time.  Results keep the
@@ -497,14 +550,20 @@ def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float
     (dzg_model_solve_batch_duals): every solution carries .duals as solve(..., duals=True) gives
     it; a model with an integer variable is then a ValueError.  ranging=True, or one list of row
     groups per problem (dzg_model_solve_batch_ranging): every solution carries .ranging as
-    solve(..., ranging=...) gives it; implies duals."""
+    solve(..., ranging=...) gives it; implies duals.  rays=True (dzg_model_solve_batch_rays): every
+    UnboundedError / InfeasibleError carries .ray as solve(..., rays=True)'s does."""
     problems = [(objective, list(constraints)) for objective, constraints in problems]
     want_ranging = _want_ranging(ranging)
+    if rays and want_ranging:
+        raise ValueError("rays=True and ranging: the ranging call carries no ray; ask in two calls")
     duals = duals or want_ranging
     for i, (objective, _) in enumerate(problems):
         if not isinstance(objective, PyAffExpr):
             raise TypeError(f"problems[{i}]: objective must be a PyAffExpr")
     mip = [_has_integer(objective, constraints) for objective, constraints in problems]
+    if rays and any(mip):
+        raise ValueError(f"problems[{mip.index(True)}]: rays=True: rays are not defined for a model "
+                         "with integer variables")
     if duals and any(mip):
         raise ValueError(f"problems[{mip.index(True)}]: {'ranging' if want_ranging else 'duals'}=True: "
                          f"{'ranges' if want_ranging else 'dual values'} are not defined for a "
@@ -524,7 +583,15 @@ def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float
         cdu = (_ffi.ModelDuals * max(count, 1))()
         for k, buf in enumerate(bufs):
             buf.fill(cdu[k])
-    if want_ranging:
+    if rays:
+        ybufs = [_RayBuffers(arrays) for arrays, _ in lowered]
+        cry = (_ffi.ModelRay * max(count, 1))()
+        for k, ybuf in enumerate(ybufs):
+            ybuf.fill(cry[k])
+        rc = _ffi.lib().dzg_model_solve_batch_rays(models, C.c_int64(count), C.byref(opts), results,
+                                                   cdu if duals else None, cry)
+        _ffi.check(rc, "dzg_model_solve_batch_rays")
+    elif want_ranging:
         groups = [True] * count if ranging is True else [list(ranging)[i] for i in lp_idx]
         rbufs = [_RangingBuffers(arrays, order, g, pivot_tol) for (arrays, order), g in zip(lowered, groups)]
         creq, crg = (_ffi.ModelRangingReq * max(count, 1))(), (_ffi.Ranging * max(count, 1))()
@@ -541,6 +608,8 @@ def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float
         _ffi.check(rc, "dzg_model_solve_batch")
     for k, i in enumerate(lp_idx):
         out[i] = _outcome(results[k], keep[k][1], lowered[k][1], f" (model {i})", stacklevel=3)
+        if rays and isinstance(out[i], Exception):
+            out[i].ray = ybufs[k].pyray(cry[k], lowered[k][1])
         if duals and not isinstance(out[i], Exception):
             out[i].duals = bufs[k].pyduals(cdu[k], lowered[k][1])
             if want_ranging and out[i].duals is not None:

@@ -520,6 +520,78 @@ int dzg_model_solve_batch_ranging(const dzg_model *models, int64_t count, const 
                                   const dzg_model_ranging_req *req, dzg_model_result *res,
                                   dzg_model_duals *du, dzg_ranging *rg);
 
+/* ---- Unboundedness and infeasibility rays (csrc/k_rays.hip) ------------------------------- */
+
+/* What a solve that ended DZG_UNBOUNDED or DZG_INFEASIBLE can show for its verdict.  Core sense, the
+ * state the solver stopped in (basis B, nonbasic set N, carried x, xbar, z, zbar; the failed pivot
+ * was not executed), with find_first_pivot as the pivot rule has it.
+ *   DZG_UNBOUNDED -> kind DZG_RAY_PRIMAL:  pos = find_first_pivot(z, zbar), var = j = N[pos],
+ *     mu = -z[pos] / zbar[pos], dx = B^-1 a_j;  d[j] = 1, d[B[p]] = -dx[p], 0 for the other
+ *     nonbasics, so that [A | I] d = 0;  value = c[j] - sum_p c[B[p]] dx[p] (p ascending, each
+ *     product rounded, then subtracted);  violation = max_p max(dx[p], 0).  If d >= 0 and value > 0,
+ *     every feasible point can move along d for ever and gains `value` per unit.
+ *   DZG_INFEASIBLE -> kind DZG_RAY_FARKAS:  pos = find_first_pivot(x, xbar), var = i = B[pos],
+ *     mu = -x[pos] / xbar[pos], y = B^-T e_pos, dz = -N^T y;  d[N[k]] = -dz[k], d[i] = 1, 0 for the
+ *     other basics: d is the aggregated row y^T [A | I];  value = sum_i rhs0[i] y[i] (rows ascending,
+ *     each product rounded);  violation = max_k max(dz[k], 0).  d . x = value for every solution of
+ *     the equations, so d >= 0, x >= 0 and value < 0 cannot all hold.
+ *   violation is NaN if the vector it is taken over holds a NaN.
+ *   proven = violation == 0.0 and (value > 0 for PRIMAL, value < 0 for FARKAS): the sign conditions
+ *   on the vectors as computed; the equalities hold to the accuracy of one solve.  The pivot rule is
+ *   the reference's, quirks included: on degenerate data it can end UNBOUNDED or INFEASIBLE on an
+ *   LP that is neither, and proven = 0 is how that shows. */
+#define DZG_RAY_PRIMAL 1
+#define DZG_RAY_FARKAS 2
+typedef struct {
+    int32_t kind;      /* 0: none (any other status, or a route without rays) */
+    int32_t proven;
+    int64_t var, pos;  /* j and its nonbasic position / i and its basis position */
+    double mu, value, violation;
+    double *d;         /* n, optional */
+    double *y;         /* m, optional; FARKAS only, zeros for PRIMAL */
+} dzg_ray;
+
+/* The solver's status must be DZG_UNBOUNDED or DZG_INFEASIBLE, else DZG_E_ARG.  STRICT: the
+ * reference's LU::solve and neg_t_dot, the batch's bits.  FAST (dense, one GPU): the final basis is
+ * refactorised as for dzg_solver_duals (same workspace requirement, refactors and state_drift move
+ * as they do there), dx / y come from the fresh inverse, dz from one pricing pass, value is summed in
+ * fixed chunks.  The carried state, the status, the objective and the pivot count are not touched;
+ * two calls on the same state return the same bits.  CSC storage and sharded solvers: DZG_E_ARG,
+ * "rays are not supported ...". */
+int dzg_solver_ray(dzg_solver *s, dzg_ray *out);
+/* dzg_batch_solve (with `du`: dzg_batch_solve_duals), then k_rays_small over the LPs that ended
+ * UNBOUNDED or INFEASIBLE, in the same device allocation; ry[i].kind = 0 for the others.  res and du
+ * (optional) are what the existing calls fill, bit for bit. */
+int dzg_batch_solve_rays(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                         int64_t pivots_per_launch, dzg_result *res, dzg_duals *du, dzg_ray *ry);
+
+/* The ray in terms of the user's model (core sense: the model is maximised, rows are coef.x <= b).
+ *   PRIMAL: var[u] = d[x+_u] - d[x-_u] (0 if u appears nowhere); con[r], ub[u], lb[u] = d of the
+ *           slacks of user row r and of u's bound rows: how fast each row's slack grows along the ray.
+ *   FARKAS: con[r], ub[u], lb[u] = y of those rows (the walk of dzg_model_map_duals): the
+ *           multipliers of the contradiction;  var[u] = d[x+_u] - d[x-_u], the aggregated coefficient
+ *           of u (zero for a proof).
+ * ub / lb are 0 where the bound is absent. */
+typedef struct {
+    double *var;              /* nvars */
+    double *con;              /* ncons */
+    double *lb, *ub;          /* nvars */
+    dzg_ray core;             /* scalars; d / y optional, sized by res->n / res->m */
+} dzg_model_ray;
+/* dzg_model_solve / dzg_model_solve_batch (with `du`: their _duals forms) with the ray of whichever
+ * solver produced the result; res, du and the return value are exactly what those give.
+ * core.kind = 0 unless the status is DZG_UNBOUNDED or DZG_INFEASIBLE, and also on a route without
+ * rays (CSC storage) or when the final basis of a FAST run did not refactorise -- the solve's outcome
+ * stands and dzg_last_error says why.  All four arrays are required (ncons / nvars > 0). */
+int dzg_model_solve_rays(const dzg_model *model, const dzg_opts *opts, dzg_model_result *res,
+                         dzg_model_duals *du, dzg_model_ray *ry);
+int dzg_model_solve_batch_rays(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                               dzg_model_result *res, dzg_model_duals *du, dzg_model_ray *ry);
+/* Host only: fills var / con / lb / ub of `out` from d[0..n) and y[0..m) (y may be NULL for
+ * DZG_RAY_PRIMAL), m and n those of the model's standard form (DZG_E_ARG otherwise). */
+int dzg_model_map_ray(const dzg_model *model, int32_t kind, const double *d, const double *y, int64_t m,
+                      int64_t n, dzg_model_ray *out);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
