@@ -611,7 +611,34 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
     }
     HIP_OK(hipMemsetAsync(d.v, 0, sizeof(double) * ((size_t)m + 2), s->st));
     s->c_host.assign(lp->c, lp->c + n);
-    if (m > 0) s->x0_host.assign(lp->x, lp->x + m);
+    if (m > 0) {
+        // rhs0, the right-hand side of [A | I] x = rhs0 (the dual objective, the value of a Farkas
+        // ray): the starting x itself where every slack starts at the position of its own row
+        // (Simplex::new); B0 x0 for any other start (warm start, resumed solve), where x0 is indexed
+        // by position and says nothing about a row on its own.  A rank that holds only a block of
+        // the columns cannot form it and keeps x0 (such solvers return carried duals and no rays).
+        s->x0_host.assign(lp->x, lp->x + m);
+        bool own_rows = true;
+        for (int p = 0; p < m; ++p)
+            if (var_col[basis[p]] != -1 - p) own_rows = false;
+        if (!own_rows && !(o.a_is_block && d.world > 1)) {
+            std::vector<double> rhs((size_t)m, 0.0);
+            for (int p = 0; p < m; ++p) {
+                const int code = var_col[basis[p]];
+                const double xp = lp->x[p];
+                if (code < 0) {
+                    rhs[(size_t)(-1 - code)] += xp;
+                } else if (lp->a) {
+                    const double *col = lp->a + (size_t)code * (size_t)lp->lda;
+                    for (int r = 0; r < m; ++r) rhs[(size_t)r] = std::fma(col[r], xp, rhs[(size_t)r]);
+                } else {
+                    for (int64_t e = lp->col_ptr[code]; e < lp->col_ptr[code + 1]; ++e)
+                        rhs[(size_t)lp->row_idx[e]] = std::fma(lp->val[e], xp, rhs[(size_t)lp->row_idx[e]]);
+                }
+            }
+            s->x0_host.swap(rhs);
+        }
+    }
     s->var_col_host.assign(var_col.begin(), var_col.begin() + n);
     s->constant = lp->constant;
 

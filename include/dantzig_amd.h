@@ -388,7 +388,11 @@ int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts
  *   d[j] = a_j . y - c[j]          the reduced cost of nonbasic variable j (for the slack of row i
  *                                  that is y[i]); exactly 0.0 for a basic variable (n entries)
  *   primal_obj                     the solver's objective
- *   dual_obj = constant + sum_i rhs0[i] * y[i]     (rhs0: the x the solve started with)
+ *   dual_obj = constant + sum_i rhs0[i] * y[i]     (rhs0: the right-hand side of the rows.  That is
+ *                                  the x the solve started with where every slack starts at the
+ *                                  position of its own row; a solver handle started from any other
+ *                                  basis forms rhs0 = B0 x0 when it is created.  The batch calls
+ *                                  take the starting x as it is.)
  *   primal_infeas = max(0, -min x) over the carried x,   dual_infeas = max(0, -min_j d[j])
  *   z_diff = |z_carried - d_N|_inf / max(1, |d_N|_inf)
  * source DZG_DUALS_FRESH: y and d were recomputed on the device from the final basis -- STRICT: the
