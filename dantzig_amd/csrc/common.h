@@ -821,11 +821,19 @@ void dzg_launch_lockstep_allgather(double *const *ptrs, int world, int which, lo
 #define DZG_CHAIN_AGCAP 16384 // compact width up to which the chain runs (the gathered column in LDS)
 #define DZG_CHAIN_BAR_WORDS (16 * 10) // barrier counters (chain_barrier.h: CH_BAR_WORDS)
 int dzg_chain_resident_per_cu(void); // workgroups of the chain kernels the runtime places on one CU
+// the instantiations of the two chain kernels a launcher chooses from (k_chain.hip, chain_pick)
+enum {
+    DZG_CHAIN_GENERIC = 0,   // 16 register-held passes, both lane widths, fold / candidates at run time
+    DZG_CHAIN_P1_NARROW = 1, // one pass, k <= 512 (k_chain_post: no fold, <= 256 candidates)
+    DZG_CHAIN_P4_NARROW = 2, // four passes, k <= 512
+    DZG_CHAIN_P4_WIDE = 3,   // four passes, both lane widths
+};
+// instances != 0: the launcher may choose an instantiation (one GPU, a refreshed d.k_hint); 0: generic
 void dzg_launch_chain_pre(const DzgDev &d, int grid, unsigned long long *bar,
-                          unsigned long long *dbg, const double *xrecv, hipStream_t st);
+                          unsigned long long *dbg, const double *xrecv, hipStream_t st, int instances = 0);
 void dzg_launch_chain_post(const DzgDev &d, int grid, unsigned long long *bar,
                            unsigned long long *dbg, int only_partials, int nrz, const double *xrecv,
-                           hipStream_t st, int fold = 0, int price_small = 0);
+                           hipStream_t st, int fold = 0, int price_small = 0, int instances = 0);
 
 // k_rowshard.hip: column sharding with the basis side sharded by rows too (opts.shard_rows)
 void dzg_launch_rs_propose(const DzgDev &d, int mode, int nrz, double *xsend, hipStream_t st);

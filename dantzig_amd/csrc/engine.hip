@@ -144,6 +144,8 @@ struct dzg_solver {
                                              // launches (DZG_CHAIN_KCAP lowers it: tests)
     bool batch_chain = false;                // the batch in flight runs the chain
     bool chain_fold = true;                  // k_chain_post finishes the row-wise pricing pass itself
+    bool chain_instances = true;             // the chain launchers choose among the kernels' instantiations
+                                             // (DZG_CHAIN_INSTANCES=0, the A/B switch: generic always)
                                              // (DZG_CHAIN_NO_FOLD=1 at creation: the separate launch)
     int64_t chain_fallbacks = 0;             // barrier failures recovered from (chain_recover)
     long long chain_retry_iter = 0;          // the chain stays off until this pivot count
@@ -795,6 +797,7 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
                     }
                 }
                 if (const char *nf = std::getenv("DZG_CHAIN_NO_FOLD")) s->chain_fold = nf[0] != '1';
+                if (const char *ci = std::getenv("DZG_CHAIN_INSTANCES")) s->chain_instances = ci[0] != '0';
                 TRY(dev_alloc(s, &s->chain_bar, (size_t)DZG_CHAIN_BAR_WORDS));
                 HIP_OK(hipMemsetAsync(s->chain_bar, 0, sizeof(unsigned long long) * DZG_CHAIN_BAR_WORDS, s->st));
             }
@@ -959,7 +962,8 @@ static void enqueue_chain_iteration(dzg_solver *s, int slot)
     Prof pf{s, slot};
     const int pk = price_kernel_for(s);
     pf.begin(DZG_K_FTRAN);
-    dzg_launch_chain_pre(d, s->chain_grid, s->chain_bar, s->chain_dbg, nullptr, st); // status, primal FTRAN + ratio, BTRAN row
+    dzg_launch_chain_pre(d, s->chain_grid, s->chain_bar, s->chain_dbg, nullptr, st, // status, primal FTRAN + ratio, BTRAN row
+                         s->chain_instances);
     pf.end(DZG_K_FTRAN);
     // k below ~480 for the whole batch: one fused kernel prices row-wise AND finishes (dz, ratio
     // candidates) per column tile -- no partial sums in memory, nothing to fold.  Otherwise, while
@@ -973,7 +977,7 @@ static void enqueue_chain_iteration(dzg_solver *s, int slot)
     dzg_launch_chain_post(d, s->chain_grid, s->chain_bar, s->chain_dbg, 0,
                           small ? dzg_price_small_partials(d)
                                 : (fold ? s->chain_grid : price_partials_for(s, pk)),
-                          nullptr, st, fold, small);
+                          nullptr, st, fold, small, s->chain_instances);
     pf.end(DZG_K_UPDATE);
     pf.begin(DZG_K_BASIS_UPDATE);
     if (++s->since_flush >= DZG_RMAX) {

@@ -59,7 +59,44 @@
 // trips are taken side by side instead of one behind the other.
 // ---------------------------------------------------------------------------------
 #define CH_NW (CH_THREADS / 64)
-#define CH_MAXP 16 // FTRAN passes (rows per lane group) whose partial sums wait in registers
+#define CH_MAXP 16 // FTRAN passes (rows per lane group) whose partial sums wait in registers: the generic kernels'
+
+// ---------------------------------------------------------------------------------
+// Instantiations.  The two chain kernels are compiled once in full -- CH_MAXP passes, both lane
+// widths of FTRAN's rows, the FOLD head and both candidate paths chosen at run time: the GENERIC
+// kernels, which run any launch -- and a few times with only what a launch can need, chosen by the
+// host per batch (dzg_chain_pick below) from what it knows before the batch starts:
+//   MAXP    register-held passes of chain_dot_head / chain_dot_tail.  Any value computes any share:
+//           passes beyond MAXP take chain_dot_tail's trailing loop (whole rows, the same sums).
+//   NARROW  the batch's bound on the compact width is known and <= 512: 16 lanes per row only.
+//   NOFOLD  (k_chain_post) fold == 0 and nrz <= 256: neither the FOLD head nor the many-candidates
+//           path exists.
+// No formula, order of a sum, barrier or LDS buffer depends on the instantiation.
+// ---------------------------------------------------------------------------------
+template <bool NARROW>
+__device__ __forceinline__ bool chain_wide(int k)
+{
+    if constexpr (NARROW)
+        return false;
+    else
+        return k > 512;
+}
+template <bool NOFOLD>
+__device__ __forceinline__ int chain_fold_on(int fold)
+{
+    if constexpr (NOFOLD)
+        return 0;
+    else
+        return fold;
+}
+template <bool NOFOLD>
+__device__ __forceinline__ bool chain_one_wave(int nrz)
+{
+    if constexpr (NOFOLD)
+        return true;
+    else
+        return nrz <= 256;
+}
 
 __device__ __forceinline__ void chain_rows(int m, int &r0, int &r1)
 {
@@ -300,10 +337,12 @@ __device__ __forceinline__ void chain_beta_fetch(const DzgDev &d, int neta, int 
 
 // FTRAN on this workgroup's rows, first half (needs the gathered column only): lane group `grp` of
 // wave `wave` takes row r0 + (pass * CH_NW + wave) * RPW + grp; the partial sums of the first
-// CH_MAXP passes stay in registers across the barrier beta is waited for.
-template <int LPR>
+// MAXP passes stay in registers across the barrier beta is waited for.  (A pass beyond the
+// workgroup's share is masked off lane by lane in fast_gemv_row_head; a block-uniform branch over it,
+// as chain_dot_tail has, was measured and withdrawn: profiles/chain_instances.txt.)
+template <int LPR, int MAXP>
 __device__ __forceinline__ void chain_dot_head(const DzgDev &d, int r0, int r1, int k,
-                                               const double *s_ag, double (&accs)[CH_MAXP])
+                                               const double *s_ag, double (&accs)[MAXP])
 {
     constexpr int RPW = 64 / LPR;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -316,7 +355,7 @@ __device__ __forceinline__ void chain_dot_head(const DzgDev &d, int r0, int r1, 
     const int variant = d.ftran_variant >= 0 ? d.ftran_variant : (k >= d.ftran_nt_k ? 2 : 0);
     if (LPR == 64 && variant == 1) {
 #pragma unroll
-        for (int pass = 0; pass < CH_MAXP; ++pass) {
+        for (int pass = 0; pass < MAXP; ++pass) {
             const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
             accs[pass] = fast_gemv_row_head<LPR, 1>(i < r1 ? i : d.m, d.m, k2, d.binv, d.ldb, s_ag, sub);
         }
@@ -324,24 +363,24 @@ __device__ __forceinline__ void chain_dot_head(const DzgDev &d, int r0, int r1, 
     }
     if (LPR == 64 && variant == 2) {
 #pragma unroll
-        for (int pass = 0; pass < CH_MAXP; ++pass) {
+        for (int pass = 0; pass < MAXP; ++pass) {
             const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
             accs[pass] = fast_gemv_row_head<LPR, 2>(i < r1 ? i : d.m, d.m, k2, d.binv, d.ldb, s_ag, sub);
         }
         return;
     }
 #pragma unroll
-    for (int pass = 0; pass < CH_MAXP; ++pass) {
+    for (int pass = 0; pass < MAXP; ++pass) {
         const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
         accs[pass] = fast_gemv_row_head<LPR>(i < r1 ? i : d.m, d.m, k2, d.binv, d.ldb, s_ag, sub);
     }
 }
 
 // second half: the eta file's share and the sum over the lanes; row sums land in s_dx[row - r0]
-template <int LPR>
+template <int LPR, int MAXP>
 __device__ __forceinline__ void chain_dot_tail(const DzgDev &d, int r0, int r1, int k, int neta,
                                                const double *s_ag, const double *s_beta,
-                                               const double (&accs)[CH_MAXP], double *s_dx)
+                                               const double (&accs)[MAXP], double *s_dx)
 {
     constexpr int RPW = 64 / LPR;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -349,7 +388,7 @@ __device__ __forceinline__ void chain_dot_tail(const DzgDev &d, int r0, int r1, 
     const int k2 = (k + 1) & ~1;
     const int npass = (r1 - r0 + CH_NW * RPW - 1) / (CH_NW * RPW);
 #pragma unroll
-    for (int pass = 0; pass < CH_MAXP; ++pass) {
+    for (int pass = 0; pass < MAXP; ++pass) {
         if (pass < npass) { // (block-uniform)
             const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
             const int ii = i < r1 ? i : d.m;
@@ -357,7 +396,7 @@ __device__ __forceinline__ void chain_dot_tail(const DzgDev &d, int r0, int r1, 
             if (ii < d.m && sub == 0) s_dx[i - r0] = acc;
         }
     }
-    for (int pass = CH_MAXP; pass < npass; ++pass) { // very tall shares: the whole row now
+    for (int pass = MAXP; pass < npass; ++pass) { // shares taller than MAXP passes: the whole row now
         const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
         const int ii = i < r1 ? i : d.m;
         const double acc = fast_gemv_row<LPR>(ii, d.m, k2, neta, d.binv, d.ldb, s_ag, d.U, d.ldw, s_beta, sub);
@@ -372,7 +411,7 @@ __device__ __forceinline__ void chain_dot_tail(const DzgDev &d, int r0, int r1, 
 // SHARD (column sharding with the matrix replicated, one process per GPU): the z-side first pivot
 // comes from the merge of every rank's proposal (xrecv: the first exchange's records) -- all ranks
 // see the same records in the same order and apply the same rule, so they take the same decision.
-template <bool SHARD>
+template <bool SHARD, int MAXP, bool NARROW>
 __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsigned long long *bar,
                                                           unsigned long long *dbg,
                                                           const double *__restrict__ xrecv)
@@ -431,7 +470,8 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
     ts.site(DZG_SITE_PRE_STATUS, t_status);
     const int slot = kind == DZG_STEP_PRIMAL ? 0 : 1;
     ts.mark(slot); // 0: first touches + status
-    if (k > CH_AGCAP || c.fp_count > 256) { // the host runs the seven launches before this can happen
+    // the host runs the seven launches -- and picks no NARROW kernel -- before this can happen
+    if (k > CH_AGCAP || c.fp_count > 256 || (NARROW && k > 512)) {
         if (lead) ctl->status = DZG_PANIC;
         return;
     }
@@ -466,8 +506,8 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
             if (SHARD) ctl->enter_src = w_rec;
         }
         __syncthreads(); // the gathered column is complete
-        double accs[CH_MAXP];
-        if (k > 512)
+        double accs[MAXP];
+        if (chain_wide<NARROW>(k)) // (block-uniform; NARROW: compile-time false)
             chain_dot_head<64>(d, r0, r1, k, s_ag, accs);
         else
             chain_dot_head<16>(d, r0, r1, k, s_ag, accs);
@@ -477,7 +517,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         ts.mark(slot); // 3: barrier
         chain_beta_fetch(d, neta, code, s_beta);
         __syncthreads();
-        if (k > 512)
+        if (chain_wide<NARROW>(k))
             chain_dot_tail<64>(d, r0, r1, k, neta, s_ag, s_beta, accs, s_dx);
         else
             chain_dot_tail<16>(d, r0, r1, k, neta, s_ag, s_beta, accs, s_dx);
@@ -600,12 +640,13 @@ __device__ __forceinline__ double chain_fold_dz(const DzgDev &d, int code, int G
 // candidates are reduced per workgroup and cross one more device-wide barrier (a primal step needs
 // none), and dz_r of the entering position is re-derived by every workgroup.  One launch and its
 // cold first touches less per pivot; the same sums and candidates, bit for bit.
-template <bool SHARD>
+template <bool SHARD, int MAXP, bool NARROW, bool NOFOLD>
 __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsigned long long *bar,
                                                            const DzgPivotArgs pa, int only_partials,
                                                            int nrz, unsigned long long *dbg,
-                                                           const double *__restrict__ xrecv, int fold)
+                                                           const double *__restrict__ xrecv, int fold_arg)
 {
+    const int fold = chain_fold_on<NOFOLD>(fold_arg); // (block-uniform; NOFOLD: compile-time 0)
     __shared__ double s_ag[CH_AGCAP];
     __shared__ double s_beta[R_], s_dx[CH_THREADS];
     __shared__ double s_dxp;
@@ -623,7 +664,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
     // ---- first touches, side by side: the pricing pass's candidates, this thread's row and column
     DzgCand2 mine = dzg_cand2_none();
     ChainSpec sp;
-    const bool one_wave = nrz <= 256; // (block-uniform) the candidates fit one wave's registers
+    const bool one_wave = chain_one_wave<NOFOLD>(nrz); // (block-uniform) the candidates fit one wave's registers
     if (SHARD || fold) {
         // (the candidates travel in the exchange records / are formed below)
     } else if (!only_partials && one_wave) {
@@ -806,8 +847,8 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
             // itself (the arithmetic of the row's owner, so the same bits) and then needs nobody
             // else's result for the step lengths
             const int k2 = (k + 1) & ~1;
-            double accs[CH_MAXP], accp;
-            if (k > 512) {
+            double accs[MAXP], accp;
+            if (chain_wide<NARROW>(k)) { // (block-uniform; NARROW: compile-time false)
                 chain_dot_head<64>(d, r0, r1, k, s_ag, accs);
                 accp = fast_gemv_row_head<64>(wave == CH_NW - 1 ? p : m, m, k2, d.binv, d.ldb, s_ag, lane);
             } else {
@@ -821,7 +862,7 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
             ts.mark(slot); // 3: barrier
             chain_beta_fetch(d, neta, cj, s_beta);
             __syncthreads();
-            if (k > 512) {
+            if (chain_wide<NARROW>(k)) {
                 chain_dot_tail<64>(d, r0, r1, k, neta, s_ag, s_beta, accs, s_dx);
                 if (wave == CH_NW - 1) {
                     const double acc = fast_gemv_row_tail<64>(accp, p, m, neta, d.U, d.ldw, s_beta, lane);
@@ -973,43 +1014,114 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
 
 static_assert(CH_BAR_WORDS == DZG_CHAIN_BAR_WORDS, "barrier counter block");
 
+// ---------------------------------------------------------------------------------
+// Which instantiation runs a launch: the ONE rule both launchers and the test entry point share.
+// Returned: DZG_CHAIN_* of common.h.  Everything the rule reads is known to the host before the
+// batch is enqueued and is handed to the kernel unchanged, so a kernel never meets what it lacks:
+//   passes  a workgroup's share is chain_rows' `per` rows, a pass covers 8 * 64 / LPR of them, and
+//           LPR is 16 only when the whole batch stays at k <= 512; MAXP too small would still be
+//           right (chain_dot_tail's trailing loop), only slower, so the rule takes the smallest
+//           instantiation that covers the share and the generic kernel when none does.
+//   narrow  the host's bound on k for the batch (d.k_hint = ncompact + batch, the bound
+//           dzg_price_small relies on) is known and <= 512.  0 = nobody refreshed the bound (the
+//           phases are driven from outside): generic.  (k_chain_pre ends a NARROW launch that
+//           meets k > 512 with DZG_PANIC rather than computing with it.)
+//   nofold  fold == 0 and nrz <= 256, the values the kernel is launched with.
+// A column-sharded rank (shard != 0) runs the generic kernels: it has instantiations of its own
+// (SHARD) and no specialised twins.
+// ---------------------------------------------------------------------------------
+static int chain_pick(int m, int grid, int k_bound, int fold, int nrz, int shard, int post)
+{
+    if (shard || grid < 1 || m < 0 || k_bound <= 0) return DZG_CHAIN_GENERIC;
+    const int per = ((m + grid - 1) / grid + 3) & ~3; // chain_rows
+    const bool narrow = k_bound <= 512;
+    const int rows_per_pass = CH_NW * (narrow ? 64 / 16 : 64 / 64);
+    const int need = (per + rows_per_pass - 1) / rows_per_pass;
+    const bool nofold = fold == 0 && nrz <= 256;
+    if (narrow) {
+        if (need <= 1 && (!post || nofold)) return DZG_CHAIN_P1_NARROW;
+        if (need <= 4) return DZG_CHAIN_P4_NARROW;
+        return DZG_CHAIN_GENERIC;
+    }
+    return need <= 4 ? DZG_CHAIN_P4_WIDE : DZG_CHAIN_GENERIC;
+}
+
+// Test hook (include/dantzig_amd.h): the rule above, as properties.  Pure host code.
+extern "C" int dzg_debug_chain_instance(int32_t m, int32_t grid, int32_t k_bound, int32_t fold, int32_t nrz,
+                                        int32_t shard, int32_t post)
+{
+    switch (chain_pick(m, grid, k_bound, fold, nrz, shard, post)) {
+    case DZG_CHAIN_P1_NARROW: return 1 | 0x100 | (post ? 0x200 : 0);
+    case DZG_CHAIN_P4_NARROW: return 4 | 0x100;
+    case DZG_CHAIN_P4_WIDE: return 4;
+    default: return CH_MAXP;
+    }
+}
+
 // Residency of the chain kernels as the runtime computes it (registers, LDS, 512 threads): the
-// smallest count over the four instantiations; 0 = some kernel does not fit a CU at all.
+// smallest count over every instantiation a launcher can choose; 0 = some kernel does not fit a CU
+// at all.  (The barrier needs every workgroup of a launch resident, whichever kernel runs it.)
 int dzg_chain_resident_per_cu(void)
 {
+    const void *kernels[] = {
+        reinterpret_cast<const void *>(k_chain_pre<false, CH_MAXP, false>),
+        reinterpret_cast<const void *>(k_chain_pre<true, CH_MAXP, false>),
+        reinterpret_cast<const void *>(k_chain_pre<false, 1, true>),
+        reinterpret_cast<const void *>(k_chain_pre<false, 4, true>),
+        reinterpret_cast<const void *>(k_chain_pre<false, 4, false>),
+        reinterpret_cast<const void *>(k_chain_post<false, CH_MAXP, false, false>),
+        reinterpret_cast<const void *>(k_chain_post<true, CH_MAXP, false, false>),
+        reinterpret_cast<const void *>(k_chain_post<false, 1, true, true>),
+        reinterpret_cast<const void *>(k_chain_post<false, 4, true, false>),
+        reinterpret_cast<const void *>(k_chain_post<false, 4, false, false>),
+    };
     int least = 1 << 20, n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_chain_pre<false>, CH_THREADS, 0) != hipSuccess) return 0;
-    least = n < least ? n : least;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_chain_pre<true>, CH_THREADS, 0) != hipSuccess) return 0;
-    least = n < least ? n : least;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_chain_post<false>, CH_THREADS, 0) != hipSuccess) return 0;
-    least = n < least ? n : least;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_chain_post<true>, CH_THREADS, 0) != hipSuccess) return 0;
-    least = n < least ? n : least;
+    for (const void *kern : kernels) {
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, CH_THREADS, 0) != hipSuccess) return 0;
+        least = n < least ? n : least;
+    }
     return least;
 }
 
-// xrecv != nullptr: a column-sharded rank (replicated matrix), records of the exchange just done
+// xrecv != nullptr: a column-sharded rank (replicated matrix), records of the exchange just done.
+// instances == 0 (DZG_CHAIN_INSTANCES=0, the A/B switch): the generic kernels always.
 void dzg_launch_chain_pre(const DzgDev &d, int grid, unsigned long long *bar,
-                          unsigned long long *dbg, const double *xrecv, hipStream_t st)
+                          unsigned long long *dbg, const double *xrecv, hipStream_t st, int instances)
 {
+    const int which = instances ? chain_pick(d.m, grid, d.k_hint, 0, 0, xrecv != nullptr, 0) : DZG_CHAIN_GENERIC;
     if (xrecv)
-        hipLaunchKernelGGL(k_chain_pre<true>, dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+        hipLaunchKernelGGL((k_chain_pre<true, CH_MAXP, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+    else if (which == DZG_CHAIN_P1_NARROW)
+        hipLaunchKernelGGL((k_chain_pre<false, 1, true>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+    else if (which == DZG_CHAIN_P4_NARROW)
+        hipLaunchKernelGGL((k_chain_pre<false, 4, true>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+    else if (which == DZG_CHAIN_P4_WIDE)
+        hipLaunchKernelGGL((k_chain_pre<false, 4, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
     else
-        hipLaunchKernelGGL(k_chain_pre<false>, dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+        hipLaunchKernelGGL((k_chain_pre<false, CH_MAXP, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
 }
 
 void dzg_launch_chain_post(const DzgDev &d, int grid, unsigned long long *bar,
                            unsigned long long *dbg, int only_partials, int nrz, const double *xrecv,
-                           hipStream_t st, int fold, int price_small)
+                           hipStream_t st, int fold, int price_small, int instances)
 {
     DzgPivotArgs pa = dzg_pivot_args(d);
     pa.price_small = price_small;
+    const int which = instances ? chain_pick(d.m, grid, d.k_hint, fold, nrz, xrecv != nullptr, 1) : DZG_CHAIN_GENERIC;
     if (xrecv)
-        hipLaunchKernelGGL(k_chain_post<true>, dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
+        hipLaunchKernelGGL((k_chain_post<true, CH_MAXP, false, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
                            pa, only_partials, nrz, dbg, xrecv, 0);
+    else if (which == DZG_CHAIN_P1_NARROW)
+        hipLaunchKernelGGL((k_chain_post<false, 1, true, true>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
+                           pa, only_partials, nrz, dbg, xrecv, fold);
+    else if (which == DZG_CHAIN_P4_NARROW)
+        hipLaunchKernelGGL((k_chain_post<false, 4, true, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
+                           pa, only_partials, nrz, dbg, xrecv, fold);
+    else if (which == DZG_CHAIN_P4_WIDE)
+        hipLaunchKernelGGL((k_chain_post<false, 4, false, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
+                           pa, only_partials, nrz, dbg, xrecv, fold);
     else
-        hipLaunchKernelGGL(k_chain_post<false>, dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
+        hipLaunchKernelGGL((k_chain_post<false, CH_MAXP, false, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar,
                            pa, only_partials, nrz, dbg, xrecv, fold);
 }
 

@@ -843,6 +843,16 @@ int dzg_debug_cand_reduce(int32_t device, int32_t form, int64_t ncases, const do
                           const double *h, const int32_t *count, double *out_r, int32_t *out_k,
                           double *out_h);
 
+/* Test hook (tests/test_gpu_chain_instances.py): which instantiation of the chain kernels
+ * (csrc/k_chain.hip, chain_pick) the launchers choose for m rows on `grid` workgroups, the host's
+ * bound `k_bound` on the compact width for the batch (0: unknown), the launch's `fold` and `nrz`, a
+ * column-sharded rank (`shard`), and k_chain_pre (`post` = 0) or k_chain_post (1).  Returns the
+ * register-held FTRAN passes of the chosen kernel in bits 0..7 (16: the generic kernel), bit 8: it
+ * has the 16-lanes-per-row arms only (k <= 512), bit 9: it has neither the fold head nor the path
+ * for more than 256 candidates.  Pure host code: no device is touched. */
+int dzg_debug_chain_instance(int32_t m, int32_t grid, int32_t k_bound, int32_t fold, int32_t nrz,
+                             int32_t shard, int32_t post);
+
 /* Deterministic max-loc merge: largest ratio wins, lowest global position on ties --
  * the sequential first-wins rule of src/simplex.rs:432-435,456-459.  Returns the index
  * of the winning record, or -1 when every record is empty. */
