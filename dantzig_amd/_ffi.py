@@ -46,6 +46,7 @@ EXPORTS = [
     "dzg_model_solve_batch_ranging",
     "dzg_solver_ray", "dzg_batch_solve_rays", "dzg_model_solve_rays", "dzg_model_solve_batch_rays",
     "dzg_model_map_ray",
+    "dzg_batch_solve_fast", "dzg_model_solve_batch_fast",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -255,6 +256,9 @@ def lib() -> C.CDLL:
         _lib.dzg_debug_chain_instance.argtypes = [C.c_int32] * 7
         _lib.dzg_batch_solve.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.dzg_model_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_solve_fast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                              C.c_void_p]
+        _lib.dzg_model_solve_batch_fast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.dzg_solver_duals.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_batch_solve_duals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p]

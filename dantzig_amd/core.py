@@ -573,6 +573,82 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
     return out
 
 
+def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
+                     refactor_every: int = 0, **opts) -> list:
+    """dzg_batch_solve_fast: every LP of `lps` in FAST numerics, one workgroup per LP with the
+    explicit basis inverse in LDS, in one call.
+
+    The same host checks as solve_batch run first (ValueError: more than 128 rows, CSC input, a
+    column-block LP, vectors that do not match (m, n)).  Keywords: numerics (FAST; AUTO, the default:
+    FAST that stops at the first near tie, the LPs it gave up on re-solved by the STRICT batch in the
+    same call; STRICT: solve_batch's path), near_tie_action, tie_tol, max_iter, epsilon.  Result i
+    is LP i's CoreResult; `.numerics` says which numerics produced it, and near_ties, first_near_tie,
+    min_margin, margins, max_pivot_error and refactors mean what they mean for a single FAST solve.
+    pivots_per_launch 0 = 128; refactor_every 0 = 64 pivots between two rebuilds of the inverse."""
+    import time
+
+    lps = list(lps)
+    allowed = {"numerics", "near_tie_action", "tie_tol", "max_iter", "epsilon", "device"}
+    unknown = set(opts) - allowed
+    if unknown:
+        raise ValueError(f"solve_batch_fast takes {sorted(allowed)}, not {sorted(unknown)}")
+    if opts.get("numerics", AUTO) not in (STRICT, FAST, AUTO):
+        raise ValueError("solve_batch_fast: numerics is STRICT, FAST or AUTO")
+    if int(pivots_per_launch) < 0 or int(refactor_every) < 0:
+        raise ValueError("solve_batch_fast: pivots_per_launch and refactor_every are >= 0")
+    for i, lp in enumerate(lps):
+        if lp.block is not None:
+            raise ValueError(f"lps[{i}]: a column-block LP cannot be batched")
+        if lp.a is None and lp.n_struct > 0:
+            raise ValueError(f"lps[{i}]: CSC input cannot be batched (dense `a` only)")
+        if lp.m > _ffi.BATCH_MAX_ROWS:
+            raise ValueError(f"lps[{i}]: {lp.m} rows; the batch takes at most {_ffi.BATCH_MAX_ROWS}")
+    marshalled = [_c_lp(lp) for lp in lps]
+    count = len(lps)
+    c_lps = (_ffi.Lp * max(count, 1))(*[c for c, _ in marshalled])
+    mo = np.concatenate([[0], np.cumsum([lp.m for lp in lps])]).astype(np.int64)
+    qo = np.concatenate([[0], np.cumsum([lp.n - lp.m for lp in lps])]).astype(np.int64)
+    basis, x, xbar = np.zeros(mo[-1] + 1, np.int64), np.zeros(mo[-1] + 1), np.zeros(mo[-1] + 1)
+    nonbasis, z, zbar = np.zeros(qo[-1] + 1, np.int64), np.zeros(qo[-1] + 1), np.zeros(qo[-1] + 1)
+    cap = int(log_cap) if log else 0
+    logs = np.zeros((count, max(cap, 1)), dtype=_PIVOT_DTYPE)
+    margins = np.full((count, max(cap, 1)), np.inf)
+    res = (_ffi.Result * max(count, 1))()
+    for i in range(count):
+        r = res[i]
+        r.basis = basis.ctypes.data + 8 * int(mo[i])
+        r.x = x.ctypes.data + 8 * int(mo[i])
+        r.xbar = xbar.ctypes.data + 8 * int(mo[i])
+        r.nonbasis = nonbasis.ctypes.data + 8 * int(qo[i])
+        r.z = z.ctypes.data + 8 * int(qo[i])
+        r.zbar = zbar.ctypes.data + 8 * int(qo[i])
+        r.log = logs.ctypes.data + logs.strides[0] * i if cap > 0 else None
+        r.margins = margins.ctypes.data + margins.strides[0] * i if cap > 0 else None
+        r.log_cap = cap
+    o = _ffi.default_opts(**opts)
+    t0 = time.perf_counter()
+    rc = _ffi.lib().dzg_batch_solve_fast(c_lps, C.c_int64(count), C.byref(o), C.c_int64(int(pivots_per_launch)),
+                                         C.c_int64(int(refactor_every)), res)
+    wall_ms = (time.perf_counter() - t0) * 1e3
+    _ffi.check(rc, "dzg_batch_solve_fast")
+    out = []
+    for i in range(count):
+        r = res[i]
+        cnt = int(min(r.iterations, cap))
+        arr = logs[i, :cnt]
+        pivots = list(zip(arr["kind"].tolist(), arr["entering"].tolist(), arr["leaving"].tolist(),
+                          arr["mu"].tolist()))
+        a0, a1, b0, b1 = int(mo[i]), int(mo[i + 1]), int(qo[i]), int(qo[i + 1])
+        fast = r.numerics_used != STRICT
+        out.append(CoreResult(
+            status=STATUS_NAMES.get(r.status, str(r.status)), status_code=r.status,
+            numerics="fast" if fast else "strict", iterations=int(r.iterations), objective=float(r.objective),
+            basis=basis[a0:a1].copy(), nonbasis=nonbasis[b0:b1].copy(), x=x[a0:a1].copy(),
+            xbar=xbar[a0:a1].copy(), z=z[b0:b1].copy(), zbar=zbar[b0:b1].copy(), pivots=pivots,
+            solve_ms=wall_ms, margins=margins[i, :cnt].copy() if fast and log else None, **_counters(r)))
+    return out
+
+
 def core_solve_full_csc(m: int, n: int, col_ptr, row_idx, val, c, constant, basis, nonbasis, x, z,
                         log_cap: int = 1 << 16, **opts) -> CoreResult:
     """dzg_core_solve_full_csc: Level 1 on the reference's own `Simplex` fields -- ONE CSC over all n

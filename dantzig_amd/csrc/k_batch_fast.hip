@@ -1,0 +1,815 @@
+// k_batch_fast.hip -- many small LPs at once in FAST numerics: one workgroup owns one LP, keeps the
+// explicit basis inverse W = B^-1 (m x m doubles) in LDS and follows the reference's loop
+// (src/simplex.rs:274-343) pivot for pivot, every decision through fast_decide.h on a control block
+// of the LP's own: margins, near_ties, first_near_tie, min_margin and the STOP / COUNT actions mean
+// what they mean in the single-LP FAST solver.  dzg_batch_solve_fast with AUTO numerics runs STOP and
+// hands every LP that ends DZG_NEAR_TIE, DZG_SINGULAR or DZG_PANIC to the STRICT batch (k_batch.hip).
+//
+//   layout      W[p * ld + r] = (B^-1)[basis position p][constraint row r], ld = m | 1.  BTRAN reads
+//               row p with lanes along r (contiguous); FTRAN gives every thread a row and walks the
+//               columns, so at a fixed column the lanes are ld doubles apart: with ld odd the 32 lanes
+//               of a ds_read_b64 group fall on 32 different 8-byte bank pairs.  128 rows: 128 x 129 x 8
+//               = 132 096 B of the CU's 160 KiB; then acol[m], dx[m], piv[m] and the control block.
+//   refactor    at the start of every launch and every `refactor_every` pivots inside one: an all-slack
+//               basis is a permutation (W[p][r] = 1 where basis[p] is row r's slack); otherwise B is
+//               gathered into W and inverted in place by Gauss-Jordan with partial pivoting (first
+//               maximum of |.|, lowest row on ties), the row swaps undone as column swaps at the end.
+//               A zero or non-finite pivot ends the LP with DZG_SINGULAR.  The health monitor
+//               (max_pivot_err, hence tau) restarts with the fresh inverse, as in k_refactor.hip.  The
+//               carried x, xbar, z, zbar are NOT replaced (k_drift.hip explains why); state_drift is not
+//               computed here and stays 0.
+//   iteration   first-pivot scans (dzg_first_pivot_entry, runner-up carried) -> fast_status ->
+//               primal: FTRAN + ratio test on x -> BTRAN + pricing;  dual: BTRAN + pricing + ratio test
+//               on z -> FTRAN;  step lengths (dzg_safe_divide), x / xbar / z / zbar, swap, then
+//               row p <- row p / dx_p, row i <- row i - dx_i * row p.
+//   FTRAN       dx_i = sum_j W[i][j] a_q[j], j ascending in four interleaved partial sums, or column c
+//               of W for the slack of row c.
+//   pricing     dz_k = -a_k . v, v = row p of W: a slack column is one negation; a structural column is
+//               read by PL = 16 / 32 / 64 lanes along its rows (m <= 16 / <= 32 / above), each lane
+//               summing its rows in ascending order, then an xor tree.  Stored entries only.
+// Every sum's order depends on m alone, every decision is taken by all threads from the same data:
+// an LP's result is bit-identical wherever it sits in a batch.
+//
+// Launches are bounded exactly as in k_batch.hip: at most `ppl` pivots per LP, then the state is in
+// global memory and the workgroup appends its LP to the next round's list if it is still running.
+// Nothing waits on another workgroup.
+#include <algorithm>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "batch_strict.h"
+#include "common.h"
+#include "fast_decide.h"
+
+int dzg_set_error(int code, const std::string &msg); // engine.hip
+int dzg_lp_valid(const dzg_lp *lp, std::string &why);
+
+namespace {
+
+// One LP of the batch: sizes and its offsets into the packed arrays (elements, not bytes).
+struct FLp {
+    long long a_off;   // A: m x ns column-major, lda = m
+    long long vc_off;  // var_col: n
+    long long m_off;   // basis, x, xbar: m
+    long long q_off;   // nonbasis, z, zbar, dz: n - m
+    long long log_off; // pivot log and margins: log_cap
+    long long log_cap;
+    int m, n, ns, pad;
+};
+
+// What an LP carries from launch to launch beside its vectors.
+struct FState {
+    DzgCtl ctl;
+    double max_err_life;  // largest max_pivot_err ever seen (the control block's restarts at a refactorisation)
+    long long refactors;  // inversions of a basis that was not all slack
+};
+
+struct FArgs {
+    const FLp *lp;
+    const double *A;
+    const int *var_col;
+    int *basis, *nonbasis;
+    double *x, *xbar, *z, *zbar, *dz;
+    FState *state;
+    int *log_kind, *log_enter, *log_leave;
+    double *log_mu, *log_margin;
+    double eps;
+    int ppl;            // pivots per launch
+    int refactor_every; // pivots between two inversions inside a launch
+    int mmax;           // largest m of the bucket: sizes the LDS carve-up
+};
+
+constexpr int kCtlBytes = (int)((sizeof(DzgCtl) + 15) / 16 * 16);
+
+inline size_t fast_lds_bytes(int mmax)
+{
+    // W, acol, dx | control block | piv, flags
+    return sizeof(double) * ((size_t)mmax * (mmax + 1) + 2 * (size_t)mmax) + kCtlBytes +
+           (sizeof(int) * ((size_t)mmax + 4) + 15) / 16 * 16;
+}
+
+__device__ __forceinline__ double shfl_xor_f64(double v, int off)
+{
+    const int lo = __shfl_xor(__double2loint(v), off, DZG_WAVE);
+    const int hi = __shfl_xor(__double2hiint(v), off, DZG_WAVE);
+    return __hiloint2double(hi, lo);
+}
+
+// W := B^-1 of the basis in global memory.  Returns 0, or 1 when a pivot was zero or not finite;
+// `inverted` says whether an elimination ran (0: all-slack basis).  Every thread gets the same values.
+template <int BLOCK, int PL>
+__device__ int build_inverse(double *W, int ld, int m, const double *A, const int *var_col,
+                             const int *basis, double *colk, int *piv, int *s_flag, int &inverted)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) {
+        s_flag[0] = 0; // a structural column is basic
+        s_flag[1] = 0; // singular
+    }
+    __syncthreads();
+    for (int p = threadIdx.x; p < m; p += BLOCK)
+        if (var_col[basis[p]] >= 0) s_flag[0] = 1;
+    __syncthreads();
+    inverted = s_flag[0];
+    if (!inverted) { // B is a permutation matrix: its inverse is its transpose
+        for (int e = threadIdx.x; e < m * m; e += BLOCK) {
+            const int p = e / m, r = e - p * m;
+            W[p * ld + r] = (-1 - var_col[basis[p]]) == r ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        return 0;
+    }
+    // stored entries only, as dzg_bs::gather: an explicit -0.0 of A arrives as +0.0
+    for (int e = threadIdx.x; e < m * m; e += BLOCK) {
+        const int c = e / m, r = e - c * m; // basis position c, constraint row r
+        const int code = var_col[basis[c]];
+        double v;
+        if (code >= 0) {
+            v = A[(long long)code * m + r];
+            v = v != 0.0 ? v : 0.0;
+        } else {
+            v = (-1 - code) == r ? 1.0 : 0.0;
+        }
+        W[r * ld + c] = v;
+    }
+    __syncthreads();
+    for (int k = 0; k < m; ++k) {
+        if (wave == 0) {
+            DzgCand best;
+            best.r = 0.0;
+            best.k = -1;
+            for (int r = k + lane; r < m; r += 64) best = dzg_better(best, dzg_bs::abs_cand(W[r * ld + k], r));
+            best = dzg_wave_best(best);
+            const int pr = best.k < 0 ? k : best.k;
+            if (lane == 0) piv[k] = pr;
+            if (pr != k) {
+                for (int j = lane; j < m; j += 64) {
+                    const double a = W[k * ld + j];
+                    W[k * ld + j] = W[pr * ld + j];
+                    W[pr * ld + j] = a;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+            const double pivot = W[k * ld + k];
+            const bool bad = !(pivot != 0.0) || isinf(pivot) || isnan(pivot);
+            if (bad) {
+                if (lane == 0) s_flag[1] = 1;
+            } else {
+                for (int i = lane; i < m; i += 64) { // column k leaves the matrix: the multipliers
+                    colk[i] = W[i * ld + k];
+                    W[i * ld + k] = i == k ? 1.0 : 0.0;
+                }
+                __builtin_amdgcn_wave_barrier();
+                for (int j = lane; j < m; j += 64) W[k * ld + j] = W[k * ld + j] / pivot;
+            }
+        }
+        __syncthreads();
+        if (s_flag[1]) return 1;
+        for (int i = threadIdx.x / PL; i < m; i += BLOCK / PL) { // PL lanes along a row
+            if (i == k) continue;
+            const double f = colk[i];
+            for (int j = threadIdx.x % PL; j < m; j += PL) {
+                const double adj = f * W[k * ld + j];
+                W[i * ld + j] = W[i * ld + j] - adj;
+            }
+        }
+        __syncthreads();
+    }
+    // P B = L U was inverted: B^-1 = (P B)^-1 P, the row swaps applied to the columns, last first
+    for (int i = threadIdx.x; i < m; i += BLOCK) {
+        for (int k = m - 1; k >= 0; --k) {
+            const int pr = piv[k];
+            if (pr == k) continue;
+            const double a = W[i * ld + k];
+            W[i * ld + k] = W[i * ld + pr];
+            W[i * ld + pr] = a;
+        }
+    }
+    __syncthreads();
+    return 0;
+}
+
+// dx = W a_q into dxs (LDS); with RATIO the primal ratio test's candidates (src/simplex.rs:439-461)
+template <int BLOCK, bool RATIO>
+__device__ __forceinline__ void ftran(const double *W, int ld, int m, const double *A, int code,
+                                      double *acol, double *dxs, const double *x, const double *xbar,
+                                      double mu, double tau, DzgCand2 &best)
+{
+    if (code >= 0) {
+        for (int i = threadIdx.x; i < m; i += BLOCK) acol[i] = A[(long long)code * m + i];
+        __syncthreads();
+    }
+    for (int i = threadIdx.x; i < m; i += BLOCK) {
+        double acc;
+        if (code >= 0) {
+            const double *row = W + i * ld;
+            double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+            int j = 0;
+            for (; j + 3 < m; j += 4) {
+                s0 = s0 + row[j] * acol[j];
+                s1 = s1 + row[j + 1] * acol[j + 1];
+                s2 = s2 + row[j + 2] * acol[j + 2];
+                s3 = s3 + row[j + 3] * acol[j + 3];
+            }
+            if (j < m) s0 = s0 + row[j] * acol[j];
+            if (j + 1 < m) s1 = s1 + row[j + 1] * acol[j + 1];
+            if (j + 2 < m) s2 = s2 + row[j + 2] * acol[j + 2];
+            acc = (s0 + s1) + (s2 + s3);
+        } else {
+            acc = W[i * ld + (-1 - code)];
+        }
+        dxs[i] = acc;
+        if (RATIO) {
+            const double xi = x[i], scaled = mu * xbar[i];
+            const double den = xi + scaled;
+            DzgCand2 cnd;
+            cnd.r = dzg_div(acc, den);
+            cnd.k = i;
+            cnd.h = -__builtin_inf();
+            if (cnd.r > 0.0) best = dzg_better2(best, cnd);
+            if (dzg_noise_zero(den, xi, scaled, tau)) best.h = __builtin_inf();
+        }
+    }
+}
+
+// ratio-test candidate of one nonbasic position (src/simplex.rs:449-455), as k_price_kernels.h forms it
+__device__ __forceinline__ void price_candidate_v(DzgCand2 &best, double dzk, int pos, double mu, double tau,
+                                                  double zk, double zbk)
+{
+    const double scaled = mu * zbk;
+    const double den = zk + scaled;
+    DzgCand2 c;
+    c.r = dzg_div(dzk, den);
+    c.k = pos;
+    c.h = -__builtin_inf();
+    if (c.r > 0.0) best = dzg_better2(best, c);
+    if (dzg_noise_zero(den, zk, scaled, tau)) best.h = __builtin_inf();
+}
+
+// dz = collect_columns(nonbasis).neg_t_dot(v) into global memory, v = row p of W; with RATIO the dual
+// ratio test's candidates
+template <int BLOCK, int PL, bool RATIO>
+__device__ __forceinline__ void price(const double *v, int m, int q, const double *A, const int *var_col,
+                                      const int *nonbasis, double *dz, const double *z, const double *zbar,
+                                      double mu, double tau, DzgCand2 &best)
+{
+    const int sub = threadIdx.x % PL, grp = threadIdx.x / PL;
+    constexpr int NG = BLOCK / PL;
+    // every lane of a wave runs the same number of rounds: the xor tree needs all PL lanes of a group
+    for (int k0 = 0; k0 < q; k0 += NG) {
+        const int k = k0 + grp;
+        double acc = 0.0;
+        if (k < q) {
+            const int code = var_col[nonbasis[k]];
+            if (code < 0) {
+                acc = -v[-1 - code]; // every lane of the group: the tree is skipped below
+            } else {
+                const double *col = A + (long long)code * m;
+                for (int r = sub; r < m; r += PL) {
+                    const double a = col[r];
+                    if (a != 0.0) acc = acc + a * -v[r];
+                }
+#pragma unroll
+                for (int off = PL / 2; off > 0; off >>= 1) acc = acc + shfl_xor_f64(acc, off);
+            }
+            if (sub == 0) {
+                dz[k] = acc;
+                if (RATIO) price_candidate_v(best, acc, k, mu, tau, z[k], zbar[k]);
+            }
+        }
+    }
+}
+
+template <int BLOCK, int PL>
+__global__ __launch_bounds__(BLOCK) void k_batch_fast(FArgs g, const int *__restrict__ list,
+                                                      int *__restrict__ next_list,
+                                                      int *__restrict__ next_count)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_mem[];
+    const int id = list[blockIdx.x];
+    const FLp L = g.lp[id];
+    const int m = L.m, q = L.n - L.m, mmax = g.mmax;
+    const int ld = m | 1;
+    double *W = s_mem;                                   // m x ld, inside mmax x (mmax + 1)
+    double *acol = s_mem + (long long)mmax * (mmax + 1); // mmax
+    double *dxs = acol + mmax;                           // mmax
+    DzgCtl *sc = (DzgCtl *)(dxs + mmax);
+    int *piv = (int *)((char *)sc + kCtlBytes);          // mmax
+    int *s_flag = piv + mmax;                            // 4
+    const double *A = g.A + L.a_off;
+    const int *var_col = g.var_col + L.vc_off;
+    int *basis = g.basis + L.m_off, *nonbasis = g.nonbasis + L.q_off;
+    double *x = g.x + L.m_off, *xbar = g.xbar + L.m_off;
+    double *z = g.z + L.q_off, *zbar = g.zbar + L.q_off, *dz = g.dz + L.q_off;
+    FState *gs = g.state + id;
+    const bool lead = threadIdx.x == 0;
+
+    for (int i = threadIdx.x; i < (int)(sizeof(DzgCtl) / sizeof(int)); i += BLOCK)
+        ((int *)sc)[i] = ((const int *)&gs->ctl)[i];
+    double max_err_life = gs->max_err_life;
+    long long refactors = gs->refactors, since = 0;
+    __syncthreads();
+
+    int status = DZG_RUNNING;
+    bool fresh = false; // W was built and no pivot has run on it yet
+    for (int step = 0; step < g.ppl; ++step) {
+        if (step == 0 || (g.refactor_every > 0 && since >= g.refactor_every)) {
+            int inverted = 0;
+            const int bad = m > 0 ? build_inverse<BLOCK, PL>(W, ld, m, A, var_col, basis, acol, piv, s_flag, inverted) : 0;
+            refactors += inverted;
+            since = 0;
+            fresh = true;
+            if (lead) { // the monitor restarts with the fresh inverse
+                sc->max_pivot_err = 0.0;
+                if (sc->tie_tol >= 0.0) sc->tau = sc->tie_tol;
+                if (bad) sc->status = DZG_SINGULAR;
+            }
+            __syncthreads();
+            if (bad) {
+                status = DZG_SINGULAR;
+                break;
+            }
+        }
+        DzgCtl c = *sc;
+        const double tau = c.tau;
+        // ---- status(), src/simplex.rs:274-306
+        DzgCand2 bz = dzg_cand2_none(), bx = dzg_cand2_none();
+        for (int k = threadIdx.x; k < q; k += BLOCK) dzg_first_pivot_entry(bz, z[k], zbar[k], k, tau);
+        for (int i = threadIdx.x; i < m; i += BLOCK) dzg_first_pivot_entry(bx, x[i], xbar[i], i, tau);
+        const DzgCand2 cj = dzg_block_best2(bz);
+        const DzgCand2 ci = dzg_block_best2(bx);
+        int kind = -1;
+        double mu = 0.0;
+        if (!fast_status(sc, c, lead, cj, ci, g.eps, m, false, kind, &mu)) {
+            __syncthreads();
+            status = sc->status;
+            break;
+        }
+        int p, r;
+        DzgCand2 best = dzg_cand2_none();
+        if (kind == DZG_STEP_PRIMAL) { // :308-318
+            r = cj.k;
+            ftran<BLOCK, true>(W, ld, m, A, var_col[nonbasis[r]], acol, dxs, x, xbar, mu, tau, best);
+            const DzgCand2 cw = dzg_block_best2(best);
+            if (!fast_ratio_outcome(sc, c, lead, cw, DZG_UNBOUNDED)) {
+                __syncthreads();
+                status = sc->status;
+                break;
+            }
+            p = cw.k;
+            price<BLOCK, PL, false>(W + p * ld, m, q, A, var_col, nonbasis, dz, z, zbar, mu, tau, best);
+        } else { // :320-330
+            p = ci.k;
+            price<BLOCK, PL, true>(W + p * ld, m, q, A, var_col, nonbasis, dz, z, zbar, mu, tau, best);
+            const DzgCand2 cw = dzg_block_best2(best);
+            if (!fast_ratio_outcome(sc, c, lead, cw, DZG_INFEASIBLE)) {
+                __syncthreads();
+                status = sc->status;
+                break;
+            }
+            r = cw.k;
+            DzgCand2 unused = dzg_cand2_none();
+            ftran<BLOCK, false>(W, ld, m, A, var_col[nonbasis[r]], acol, dxs, x, xbar, mu, tau, unused);
+        }
+        __syncthreads(); // dxs (LDS) and dz (global) are complete
+        // ---- pivot, src/simplex.rs:253-268: step lengths, finiteness assert (:466)
+        const double dxp = dxs[p], dzr = dz[r];
+        int ok = 1;
+        const double t = dzg_safe_divide(x[p], dxp, &ok);
+        const double s = dzg_safe_divide(z[r], dzr, &ok);
+        const double tbar = dzg_safe_divide(xbar[p], dxp, &ok);
+        const double sbar = dzg_safe_divide(zbar[r], dzr, &ok);
+        if (!ok) { // the pivot was chosen, not executed
+            if (lead) sc->status = DZG_PANIC;
+            status = DZG_PANIC;
+            break;
+        }
+        // the pivot element is known twice: dx_p from FTRAN, -dz_r from BTRAN + pricing
+        double max_err = c.max_pivot_err;
+        {
+            const double a1 = fabs(dxp), a2 = fabs(dzr);
+            const double den = a1 > a2 ? a1 : a2;
+            const double err = den > 0.0 ? fabs(dxp + dzr) / den : 0.0;
+            if (err > max_err) max_err = err;
+        }
+        if (max_err > max_err_life) max_err_life = max_err;
+        const int i_var = basis[p], j_var = nonbasis[r];
+        // row p of the new inverse, into acol (the entering column is spent)
+        for (int j = threadIdx.x; j < m; j += BLOCK) acol[j] = W[p * ld + j] / dxp;
+        __syncthreads(); // every thread has read x[p], z[r], basis[p], nonbasis[r], row p
+        if (lead) {
+            const long long it = c.iter;
+            if (it < L.log_cap) {
+                g.log_kind[L.log_off + it] = kind;
+                g.log_enter[L.log_off + it] = j_var;
+                g.log_leave[L.log_off + it] = i_var;
+                g.log_mu[L.log_off + it] = mu;
+                g.log_margin[L.log_off + it] = c.margin;
+            }
+            basis[p] = j_var; // swap, :243-247
+            nonbasis[r] = i_var;
+            sc->enter_pos = r;
+            sc->leave_pos = p;
+            sc->enter_var = j_var;
+            sc->leave_var = i_var;
+            sc->t = t;
+            sc->s = s;
+            sc->tbar = tbar;
+            sc->sbar = sbar;
+            sc->max_pivot_err = max_err;
+            // near-tie record of this pivot; the tolerance follows the health monitor
+            if (c.margin < c.min_margin) sc->min_margin = c.margin;
+            if (c.tie_seen) {
+                sc->near_ties = c.near_ties + 1;
+                if (c.first_near_tie < 0) sc->first_near_tie = it;
+            }
+            if (c.tie_tol >= 0.0) {
+                const double adaptive = 64.0 * max_err;
+                sc->tau = adaptive > c.tie_tol ? adaptive : c.tie_tol;
+            }
+            sc->iter = it + 1;
+        }
+        for (int i = threadIdx.x; i < m; i += BLOCK) {
+            const double d = dxs[i];
+            const double a = t * d, b = tbar * d;
+            x[i] = (i == p) ? t : x[i] - a;
+            xbar[i] = (i == p) ? tbar : xbar[i] - b;
+        }
+        for (int k = threadIdx.x; k < q; k += BLOCK) {
+            const double d = dz[k];
+            const double a = s * d, b = sbar * d;
+            z[k] = (k == r) ? s : z[k] - a;
+            zbar[k] = (k == r) ? sbar : zbar[k] - b;
+        }
+        for (int i = threadIdx.x / PL; i < m; i += BLOCK / PL) { // PL lanes along a row
+            const double f = dxs[i];
+            for (int j = threadIdx.x % PL; j < m; j += PL) {
+                const double adj = f * acol[j];
+                W[i * ld + j] = (i == p) ? acol[j] : W[i * ld + j] - adj;
+            }
+        }
+        ++since;
+        __syncthreads(); // the next status() reads the updated vectors and control block
+        // FAST health: the two values of the pivot element disagree beyond repair.  A stale inverse
+        // is rebuilt; one that drifts on its first pivot is ill-conditioned: DZG_SINGULAR
+        if (max_err > 1e-4) {
+            if (fresh) {
+                if (lead) sc->status = DZG_SINGULAR;
+                status = DZG_SINGULAR;
+                break;
+            }
+            since = g.refactor_every > 0 ? g.refactor_every : since;
+        }
+        fresh = false;
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < (int)(sizeof(DzgCtl) / sizeof(int)); i += BLOCK)
+        ((int *)&gs->ctl)[i] = ((const int *)sc)[i];
+    if (lead) {
+        gs->max_err_life = max_err_life;
+        gs->refactors = refactors;
+        if (status == DZG_RUNNING) next_list[atomicAdd(next_count, 1)] = id;
+    }
+}
+
+using dzg_bs::bucket_of;
+using dzg_bs::kBuckets;
+using dzg_bs::kMaxGrid;
+
+void launch_bucket(int b, const FArgs &g, const int *list, int n, int *next_list, int *next_count,
+                   hipStream_t st)
+{
+    const size_t lds = fast_lds_bytes(g.mmax);
+    if (b == 3) { // more than 64 KiB of dynamic LDS: say so once (a runtime that needs no telling ignores it)
+        static const hipError_t attr =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_batch_fast<256, 64>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds_bytes(DZG_BATCH_MAX_ROWS));
+        (void)attr;
+    }
+    for (int c0 = 0; c0 < n; c0 += kMaxGrid[b]) {
+        const int grid = std::min(kMaxGrid[b], n - c0);
+        // one wave per LP up to 32 rows (no barrier has a second wave to wait for), then 2 and 4
+        if (b == 0)
+            hipLaunchKernelGGL((k_batch_fast<64, 16>), dim3(grid), dim3(64), lds, st, g, list + c0, next_list,
+                               next_count);
+        else if (b == 1)
+            hipLaunchKernelGGL((k_batch_fast<64, 32>), dim3(grid), dim3(64), lds, st, g, list + c0, next_list,
+                               next_count);
+        else if (b == 2)
+            hipLaunchKernelGGL((k_batch_fast<128, 64>), dim3(grid), dim3(128), lds, st, g, list + c0, next_list,
+                               next_count);
+        else
+            hipLaunchKernelGGL((k_batch_fast<256, 64>), dim3(grid), dim3(256), lds, st, g, list + c0, next_list,
+                               next_count);
+    }
+}
+
+#define FHIP(expr)                                                                              \
+    do {                                                                                        \
+        hipError_t e_ = (expr);                                                                 \
+        if (e_ != hipSuccess)                                                                   \
+            return dzg_set_error(DZG_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+struct Section {
+    size_t off = 0, bytes = 0;
+};
+
+} // namespace
+
+#define DZG_BATCH_FAST_DEFAULT_PPL 128
+#define DZG_BATCH_FAST_DEFAULT_REFACTOR 64
+
+// The FAST batch itself: `o.near_tie_action` and `o.tie_tol` as given.
+static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o, int64_t pivots_per_launch,
+                            int64_t refactor_every_arg, dzg_result *res)
+{
+    const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
+    const double eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
+    const int ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
+                                                : DZG_BATCH_FAST_DEFAULT_PPL);
+    const int refactor_every = (int)(refactor_every_arg > 0 ? std::min<int64_t>(refactor_every_arg, 1 << 30)
+                                                            : DZG_BATCH_FAST_DEFAULT_REFACTOR);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+        return dzg_set_error(DZG_E_DEVICE, "no HIP device visible: dantzig_amd has no CPU path");
+    if (o.device < 0 || o.device >= ndev) return dzg_set_error(DZG_E_ARG, "opts.device out of range");
+    FHIP(hipSetDevice(o.device));
+
+    // ---- packed layout: one arena, sections 16-B aligned
+    const int N = (int)count;
+    std::vector<FLp> desc((size_t)N);
+    long long na = 0, nvc = 0, nm = 0, nq = 0, nlog = 0;
+    int mmax[kBuckets] = {0, 0, 0, 0};
+    std::vector<int> bucket_n(kBuckets, 0);
+    for (int i = 0; i < N; ++i) {
+        const dzg_lp &lp = lps[i];
+        FLp &d = desc[(size_t)i];
+        d.m = (int)lp.m;
+        d.n = (int)lp.n;
+        d.ns = (int)lp.n_struct;
+        d.pad = 0;
+        d.a_off = na;
+        d.vc_off = nvc;
+        d.m_off = nm;
+        d.q_off = nq;
+        d.log_off = nlog;
+        d.log_cap = res[i].log && res[i].log_cap > 0 ? std::min<long long>(res[i].log_cap, max_iter) : 0;
+        na += (long long)lp.m * lp.n_struct;
+        nvc += lp.n;
+        nm += lp.m;
+        nq += lp.n - lp.m;
+        nlog += d.log_cap;
+        const int b = bucket_of(lp.m);
+        mmax[b] = std::max(mmax[b], (int)lp.m);
+        bucket_n[(size_t)b]++;
+    }
+    size_t top = 0;
+    auto section = [&](size_t bytes) {
+        Section s;
+        s.off = top;
+        s.bytes = bytes;
+        top += (bytes + 15) / 16 * 16;
+        return s;
+    };
+    // upload-only, then state (uploaded and downloaded), then log (downloaded), then scratch
+    const Section s_desc = section(sizeof(FLp) * N), s_a = section(sizeof(double) * na),
+                  s_vc = section(sizeof(int) * nvc), s_list = section(sizeof(int) * N);
+    const size_t state0 = top;
+    const Section s_basis = section(sizeof(int) * nm), s_nonbasis = section(sizeof(int) * nq),
+                  s_x = section(sizeof(double) * nm), s_xbar = section(sizeof(double) * nm),
+                  s_z = section(sizeof(double) * nq), s_zbar = section(sizeof(double) * nq),
+                  s_state = section(sizeof(FState) * N);
+    const size_t upload_end = top;
+    const Section s_lk = section(sizeof(int) * nlog), s_le = section(sizeof(int) * nlog),
+                  s_ll = section(sizeof(int) * nlog), s_lmu = section(sizeof(double) * nlog),
+                  s_lmg = section(sizeof(double) * nlog);
+    const size_t download_end = top;
+    const Section s_dz = section(sizeof(double) * nq), s_list2 = section(sizeof(int) * N),
+                  s_count = section(sizeof(int) * kBuckets);
+
+    std::vector<unsigned char> host(download_end, 0);
+    auto hp = [&](const Section &s) { return host.data() + s.off; };
+    std::memcpy(hp(s_desc), desc.data(), sizeof(FLp) * N);
+    {
+        double *a = (double *)hp(s_a);
+        int *vc = (int *)hp(s_vc), *bs = (int *)hp(s_basis), *nb = (int *)hp(s_nonbasis);
+        double *x = (double *)hp(s_x), *xb = (double *)hp(s_xbar), *z = (double *)hp(s_z),
+               *zb = (double *)hp(s_zbar);
+        FState *fs = (FState *)hp(s_state);
+        for (int i = 0; i < N; ++i) {
+            const dzg_lp &lp = lps[i];
+            const FLp &d = desc[(size_t)i];
+            const int64_t m = lp.m, q = lp.n - lp.m;
+            for (int64_t j = 0; j < lp.n_struct; ++j)
+                std::memcpy(a + d.a_off + j * m, lp.a + j * lp.lda, sizeof(double) * (size_t)m);
+            for (int64_t v = 0; v < lp.n; ++v)
+                vc[d.vc_off + v] = lp.var_col ? (int)lp.var_col[v]
+                                              : (v < lp.n_struct ? (int)v : (int)(-1 - (v - lp.n_struct)));
+            for (int64_t k = 0; k < m; ++k) {
+                bs[d.m_off + k] = (int)lp.basis[k];
+                x[d.m_off + k] = lp.x[k];
+                xb[d.m_off + k] = lp.xbar ? lp.xbar[k] : 1.0; // Simplex::new, src/simplex.rs:219-220
+            }
+            for (int64_t k = 0; k < q; ++k) {
+                nb[d.q_off + k] = (int)lp.nonbasis[k];
+                z[d.q_off + k] = lp.z[k];
+                zb[d.q_off + k] = lp.zbar ? lp.zbar[k] : 1.0;
+            }
+            DzgCtl &c0 = fs[i].ctl; // as dzg_solver_create starts a FAST solver's
+            c0.status = DZG_RUNNING;
+            c0.iter_stop = max_iter;
+            c0.enter_pos = c0.leave_pos = -1;
+            c0.del_ce = c0.del_last = -1;
+            c0.rl_listed = -1;
+            c0.tie_tol = c0.tau = o.tie_tol;
+            c0.margin = c0.min_margin = __builtin_inf();
+            c0.first_near_tie = c0.tie_skip_iter = -1;
+            c0.tie_mode = o.near_tie_action == DZG_NEAR_TIE_STOP ? 1 : 0;
+        }
+        // the first round's lists: LP indices grouped by bucket
+        int *list = (int *)hp(s_list);
+        std::vector<int> fill(kBuckets, 0);
+        for (int b = 1; b < kBuckets; ++b) fill[(size_t)b] = fill[(size_t)b - 1] + bucket_n[(size_t)b - 1];
+        for (int i = 0; i < N; ++i) list[fill[(size_t)bucket_of(lps[i].m)]++] = i;
+    }
+
+    unsigned char *dev = nullptr;
+    hipStream_t st = nullptr;
+    struct Guard {
+        unsigned char **dev;
+        hipStream_t *st;
+        ~Guard()
+        {
+            if (*dev) (void)hipFree(*dev);
+            if (*st) (void)hipStreamDestroy(*st);
+        }
+    } guard{&dev, &st};
+    FHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    FHIP(hipMalloc((void **)&dev, top));
+    FHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
+
+    FArgs g;
+    g.lp = (const FLp *)(dev + s_desc.off);
+    g.A = (const double *)(dev + s_a.off);
+    g.var_col = (const int *)(dev + s_vc.off);
+    g.basis = (int *)(dev + s_basis.off);
+    g.nonbasis = (int *)(dev + s_nonbasis.off);
+    g.x = (double *)(dev + s_x.off);
+    g.xbar = (double *)(dev + s_xbar.off);
+    g.z = (double *)(dev + s_z.off);
+    g.zbar = (double *)(dev + s_zbar.off);
+    g.dz = (double *)(dev + s_dz.off);
+    g.state = (FState *)(dev + s_state.off);
+    g.log_kind = (int *)(dev + s_lk.off);
+    g.log_enter = (int *)(dev + s_le.off);
+    g.log_leave = (int *)(dev + s_ll.off);
+    g.log_mu = (double *)(dev + s_lmu.off);
+    g.log_margin = (double *)(dev + s_lmg.off);
+    g.eps = eps;
+    g.ppl = ppl;
+    g.refactor_every = refactor_every;
+    g.mmax = 0;
+
+    // ---- rounds: every bucket's running LPs, then one readback of the bucket counters
+    int *cur = (int *)(dev + s_list.off), *nxt = (int *)(dev + s_list2.off);
+    int *counts = (int *)(dev + s_count.off);
+    std::vector<int> seg(kBuckets, 0);
+    for (int b = 1; b < kBuckets; ++b) seg[(size_t)b] = seg[(size_t)b - 1] + bucket_n[(size_t)b - 1];
+    std::vector<int> live(bucket_n);
+    for (;;) {
+        bool any = false;
+        FHIP(hipMemsetAsync(counts, 0, sizeof(int) * kBuckets, st));
+        for (int b = 0; b < kBuckets; ++b) {
+            if (live[(size_t)b] == 0) continue;
+            any = true;
+            FArgs gb = g;
+            gb.mmax = mmax[b];
+            launch_bucket(b, gb, cur + seg[(size_t)b], live[(size_t)b], nxt + seg[(size_t)b], counts + b, st);
+            FHIP(hipGetLastError());
+        }
+        if (!any) break;
+        int h_counts[kBuckets];
+        FHIP(hipMemcpyAsync(h_counts, counts, sizeof(h_counts), hipMemcpyDeviceToHost, st));
+        FHIP(hipStreamSynchronize(st));
+        for (int b = 0; b < kBuckets; ++b) live[(size_t)b] = h_counts[b];
+        std::swap(cur, nxt);
+    }
+    FHIP(hipMemcpyAsync(host.data() + state0, dev + state0, download_end - state0, hipMemcpyDeviceToHost, st));
+    FHIP(hipStreamSynchronize(st));
+
+    // ---- results
+    const int *bs = (const int *)hp(s_basis), *nb = (const int *)hp(s_nonbasis);
+    const double *x = (const double *)hp(s_x), *xb = (const double *)hp(s_xbar),
+                 *z = (const double *)hp(s_z), *zb = (const double *)hp(s_zbar);
+    const FState *fs = (const FState *)hp(s_state);
+    const int *lk = (const int *)hp(s_lk), *le = (const int *)hp(s_le), *ll = (const int *)hp(s_ll);
+    const double *lmu = (const double *)hp(s_lmu), *lmg = (const double *)hp(s_lmg);
+    for (int i = 0; i < N; ++i) {
+        const dzg_lp &lp = lps[i];
+        const FLp &d = desc[(size_t)i];
+        const DzgCtl &c = fs[i].ctl;
+        dzg_result &r = res[i];
+        const int64_t m = lp.m, q = lp.n - lp.m;
+        r.status = c.status;
+        r.numerics_used = DZG_NUMERICS_FAST;
+        r.iterations = c.iter;
+        double sum = 0.0; // objective_value, src/simplex.rs:345-352, basis-position order
+        int64_t dense = 0;
+        for (int64_t p = 0; p < m; ++p) {
+            const int var = bs[d.m_off + p];
+            const double prod = lp.c[var] * x[d.m_off + p];
+            sum = sum + prod;
+            const int64_t code = lp.var_col ? lp.var_col[var] : (var < lp.n_struct ? var : -1);
+            if (code >= 0) ++dense;
+        }
+        r.objective = lp.constant + sum;
+        for (int64_t k = 0; k < m; ++k) {
+            if (r.basis) r.basis[k] = bs[d.m_off + k];
+            if (r.x) r.x[k] = x[d.m_off + k];
+            if (r.xbar) r.xbar[k] = xb[d.m_off + k];
+        }
+        for (int64_t k = 0; k < q; ++k) {
+            if (r.nonbasis) r.nonbasis[k] = nb[d.q_off + k];
+            if (r.z) r.z[k] = z[d.q_off + k];
+            if (r.zbar) r.zbar[k] = zb[d.q_off + k];
+        }
+        const long long cnt = std::min<long long>(r.iterations, d.log_cap);
+        for (long long k = 0; k < cnt; ++k) {
+            r.log[k].kind = lk[d.log_off + k];
+            r.log[k].reserved = 0;
+            r.log[k].entering = le[d.log_off + k];
+            r.log[k].leaving = ll[d.log_off + k];
+            r.log[k].mu = lmu[d.log_off + k];
+            if (r.margins) r.margins[k] = lmg[d.log_off + k];
+        }
+        for (int k = 0; k < DZG_K_COUNT; ++k) {
+            r.kernel_ms[k] = 0.0;
+            r.kernel_launches[k] = 0;
+        }
+        r.price_bytes = 0.0;
+        r.solve_ms = 0.0;
+        r.max_pivot_error = fs[i].max_err_life;
+        r.near_ties = c.near_ties;
+        r.first_near_tie = c.first_near_tie;
+        r.min_margin = c.min_margin;
+        r.dense_columns = dense;
+        r.refactors = fs[i].refactors;
+        r.chain_fallbacks = 0;
+        r.price_pass_used = 0;
+        r.price_rows_copy = 0;
+        r.state_drift = 0.0; // not measured by the batched solver
+    }
+    return 0;
+}
+
+extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                                    int64_t pivots_per_launch, int64_t refactor_every, dzg_result *res)
+{
+    // ---- host checks first: malformed input is DZG_E_ARG on any machine
+    if (count < 0) return dzg_set_error(DZG_E_ARG, "batch: count < 0");
+    if (count > 0 && (!lps || !res)) return dzg_set_error(DZG_E_ARG, "batch: lps or res is NULL");
+    if (count >= (1ll << 31)) return dzg_set_error(DZG_E_ARG, "batch: count out of range");
+    if (pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "batch: pivots_per_launch < 0");
+    if (refactor_every < 0) return dzg_set_error(DZG_E_ARG, "batch: refactor_every < 0");
+    dzg_opts o;
+    if (opts) o = *opts; else dzg_opts_default(&o);
+    if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_FAST && o.numerics != DZG_NUMERICS_AUTO)
+        return dzg_set_error(DZG_E_ARG, "batch: opts.numerics");
+    if (o.numerics == DZG_NUMERICS_STRICT) return dzg_batch_solve(lps, count, &o, pivots_per_launch, res);
+    for (int64_t i = 0; i < count; ++i) {
+        const dzg_lp *lp = &lps[i];
+        std::string why;
+        const std::string at = "batch: lps[" + std::to_string(i) + "]: ";
+        if (!dzg_lp_valid(lp, why)) return dzg_set_error(DZG_E_ARG, at + why);
+        if (lp->m > DZG_BATCH_MAX_ROWS)
+            return dzg_set_error(DZG_E_ARG, at + "m > DZG_BATCH_MAX_ROWS (" + std::to_string(DZG_BATCH_MAX_ROWS) + ")");
+        if (lp->n_struct > 0 && !lp->a) return dzg_set_error(DZG_E_ARG, at + "CSC input is not batched");
+        if (lp->n - lp->m > (1ll << 30)) return dzg_set_error(DZG_E_ARG, at + "too many columns");
+    }
+    if (count == 0) return 0;
+    const bool is_auto = o.numerics == DZG_NUMERICS_AUTO;
+    if (is_auto) o.near_tie_action = DZG_NEAR_TIE_STOP;
+    const int rc = batch_solve_fast(lps, count, o, pivots_per_launch, refactor_every, res);
+    if (rc < 0 || !is_auto) return rc;
+    // ---- AUTO: only the reference's own arithmetic can arbitrate a tie -- the LPs FAST gave up on
+    // are solved again from their first pivot by the STRICT batch, into the same result slots
+    std::vector<int64_t> redo;
+    for (int64_t i = 0; i < count; ++i)
+        if (res[i].status == DZG_NEAR_TIE || res[i].status == DZG_SINGULAR || res[i].status == DZG_PANIC)
+            redo.push_back(i);
+    if (redo.empty()) return 0;
+    std::vector<dzg_lp> lps2(redo.size());
+    std::vector<dzg_result> res2(redo.size());
+    for (size_t k = 0; k < redo.size(); ++k) {
+        lps2[k] = lps[redo[k]];
+        res2[k] = res[redo[k]];
+    }
+    dzg_opts os = o;
+    os.numerics = DZG_NUMERICS_STRICT;
+    const int rc2 = dzg_batch_solve(lps2.data(), (int64_t)redo.size(), &os, 0, res2.data());
+    if (rc2 < 0) return rc2;
+    for (size_t k = 0; k < redo.size(); ++k) res[redo[k]] = res2[k];
+    return 0;
+}

@@ -570,7 +570,7 @@ extern "C" int dzg_model_solve_duals(const dzg_model *md, const dzg_opts *opts, 
 static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
                              dzg_model_result *res, dzg_model_duals *du, bool want_duals,
                              const dzg_model_ranging_req *mreq = nullptr, dzg_ranging *rg = nullptr,
-                             dzg_model_ray *ry = nullptr)
+                             dzg_model_ray *ry = nullptr, bool fast = false)
 {
     if (count > 0 && want_duals && rg && !mreq) return dzg_set_error(DZG_E_ARG, "model batch: req is NULL");
     if (count < 0) return dzg_set_error(DZG_E_ARG, "model batch: count < 0");
@@ -653,7 +653,12 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
             rays[k].y = ray_y[k].data();
         }
     }
-    if (nb > 0) {
+    if (nb > 0 && fast) { // (plain solves only) the shared batch in FAST numerics under the AUTO policy
+        dzg_opts of = o;
+        of.numerics = DZG_NUMERICS_AUTO;
+        const int rc = dzg_batch_solve_fast(lps.data(), (int64_t)nb, &of, 0, 0, rs.data());
+        if (rc < 0) return rc;
+    } else if (nb > 0) {
         const int rc = ry ? dzg_batch_solve_rays(lps.data(), (int64_t)nb, &o, 0, rs.data(),
                                                  want_duals ? cores.data() : nullptr, rays.data())
                      : rg ? dzg_batch_solve_ranging(lps.data(), (int64_t)nb, &o, 0, breq.data(), rs.data(),
@@ -694,6 +699,12 @@ extern "C" int dzg_model_solve_batch(const dzg_model *models, int64_t count, con
                                      dzg_model_result *res)
 {
     return model_solve_batch(models, count, opts, res, nullptr, false);
+}
+
+extern "C" int dzg_model_solve_batch_fast(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                                          dzg_model_result *res)
+{
+    return model_solve_batch(models, count, opts, res, nullptr, false, nullptr, nullptr, nullptr, true);
 }
 
 extern "C" int dzg_model_solve_batch_duals(const dzg_model *models, int64_t count, const dzg_opts *opts,

@@ -333,24 +333,28 @@ class Maximize(Optimize):
 
 
 def solve_many(problems, *, duals: bool = False, ranging: bool = False, rays: bool = False,
-               return_exceptions: bool = False) -> list:
+               return_exceptions: bool = False, fast: bool = False) -> list:
     """[p.solve() for p in problems] in one batched call (rust.solve_many): the small models share
     one launch on the GPU, one workgroup per model, bit for bit what p.solve() returns.  A model
     that is unbounded or infeasible raises the exception p.solve() raises, with the model's index
     in the message, after the whole batch is done; with return_exceptions=True the exception
     instance stands in that model's place.  duals=True: every Solution is p.solve(duals=True)'s;
     ranging=True: p.solve(ranging=True)'s; rays=True: every exception is p.solve(rays=True)'s, `.ray`
-    included."""
+    included.  fast=True: the shared batch runs FAST numerics and falls back to STRICT, model by
+    model, where a decision of the pivot rule comes within rounding of a tie (rust.solve_many); not
+    yet together with duals, ranging or rays (ValueError)."""
     problems = list(problems)
     for i, p in enumerate(problems):
         if not isinstance(p, Optimize):
             raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
+    if fast and (duals or ranging or rays):
+        raise ValueError("fast=True does not combine with duals, ranging or rays yet")
     if rays and ranging:
         raise ValueError("rays=True and ranging=True: the ranging call carries no ray; ask in two calls")
     duals = duals or ranging
     raw = rs.solve_many([p._rust_problem() for p in problems], duals=duals,
                         ranging=[p._row_groups() for p in problems] if ranging else False,
-                        rays=rays, return_exceptions=return_exceptions or rays)
+                        rays=rays, return_exceptions=return_exceptions or rays, **({"fast": True} if fast else {}))
     if rays:  # (the core rays become the models' before anything is raised)
         raw = [p._wrap_ray(r) if isinstance(r, Exception) else r for p, r in zip(problems, raw)]
         if not return_exceptions:

@@ -539,7 +539,7 @@ def solve_mip(objective: PyAffExpr, constraints, *, node_log: int = 0, **mip_opt
 
 
 def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float = 0.0,
-               rays: bool = False, return_exceptions: bool = False) -> list:
+               rays: bool = False, return_exceptions: bool = False, fast: bool = False) -> list:
     """solve() for every (objective, constraints) pair of `problems`, in one dzg_model_solve_batch
     call: the models that solve() would run in STRICT numerics on at most 128 rows share one batch
     on the GPU (one workgroup per model), the others are solved one at a time.  Results keep the
@@ -551,9 +551,14 @@ def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float
     it; a model with an integer variable is then a ValueError.  ranging=True, or one list of row
     groups per problem (dzg_model_solve_batch_ranging): every solution carries .ranging as
     solve(..., ranging=...) gives it; implies duals.  rays=True (dzg_model_solve_batch_rays): every
-    UnboundedError / InfeasibleError carries .ray as solve(..., rays=True)'s does."""
+    UnboundedError / InfeasibleError carries .ray as solve(..., rays=True)'s does.  fast=True
+    (dzg_model_solve_batch_fast): the shared batch runs FAST numerics under the AUTO policy -- a model
+    whose pivot rule comes within rounding of a tie is re-solved in STRICT inside the same call; not
+    yet together with duals, ranging or rays (ValueError)."""
     problems = [(objective, list(constraints)) for objective, constraints in problems]
     want_ranging = _want_ranging(ranging)
+    if fast and (duals or want_ranging or rays):
+        raise ValueError("fast=True does not combine with duals, ranging or rays yet")
     if rays and want_ranging:
         raise ValueError("rays=True and ranging: the ranging call carries no ray; ask in two calls")
     duals = duals or want_ranging
@@ -603,6 +608,9 @@ def solve_many(problems, *, duals: bool = False, ranging=False, pivot_tol: float
     elif duals:
         rc = _ffi.lib().dzg_model_solve_batch_duals(models, C.c_int64(count), C.byref(opts), results, cdu)
         _ffi.check(rc, "dzg_model_solve_batch_duals")
+    elif fast:
+        rc = _ffi.lib().dzg_model_solve_batch_fast(models, C.c_int64(count), C.byref(opts), results)
+        _ffi.check(rc, "dzg_model_solve_batch_fast")
     else:
         rc = _ffi.lib().dzg_model_solve_batch(models, C.c_int64(count), C.byref(opts), results)
         _ffi.check(rc, "dzg_model_solve_batch")

@@ -380,6 +380,27 @@ int dzg_batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
 int dzg_model_solve_batch(const dzg_model *models, int64_t count, const dzg_opts *opts,
                           dzg_model_result *res);
 
+/* ---- The same batches in FAST numerics (csrc/k_batch_fast.hip) ---------------------------- */
+
+/* dzg_batch_solve's arguments and checks; one workgroup per LP keeps the explicit basis inverse in
+ * LDS and follows the reference pivot for pivot, flagging every decision within rounding of a tie.
+ * opts->numerics: FAST honours near_tie_action and tie_tol (max_iter, epsilon as dzg_batch_solve);
+ * AUTO, and opts == NULL, runs FAST with near_tie_action = STOP, and every LP that ends
+ * DZG_NEAR_TIE, DZG_SINGULAR or DZG_PANIC is solved again from its first pivot by dzg_batch_solve in
+ * the same call (res[i].numerics_used says which numerics produced res[i]; auto_strict_rows is not
+ * consulted); STRICT is dzg_batch_solve.  pivots_per_launch 0 = 128, refactor_every 0 = 64: the
+ * inverse is rebuilt from the basis at the start of every launch and every refactor_every pivots
+ * inside one (res[i].refactors counts the rebuilds of a basis that was not all slack); negative:
+ * DZG_E_ARG.  res[i] also carries margins (optional, like log), max_pivot_error, near_ties,
+ * first_near_tie and min_margin with dzg_solver_result's meaning; state_drift is not measured and
+ * stays 0.  An LP's result does not depend on its place in the batch. */
+int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                         int64_t pivots_per_launch, int64_t refactor_every, dzg_result *res);
+/* dzg_model_solve_batch's routing: the models that would share its STRICT batch share one
+ * dzg_batch_solve_fast call with AUTO numerics; the others go through dzg_model_solve unchanged. */
+int dzg_model_solve_batch_fast(const dzg_model *models, int64_t count, const dzg_opts *opts,
+                               dzg_model_result *res);
+
 /* ---- Dual values and reduced costs at the optimum (csrc/k_duals.hip) ------------------ */
 
 /* In the core sense (maximise c.x + constant, [A | I] x = rhs, x >= 0), at an OPTIMAL basis B with

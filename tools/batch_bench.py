@@ -11,6 +11,15 @@ the whole set on 16 threads; and whether every batch result equals the oracle's 
 (status, iterations, pivot log with mu, basis, nonbasis, x, xbar, z, zbar, objective).
 
     python tools/batch_bench.py [--workloads abc] [--no-oracle] [--no-sequential] [--ppl P] [--max-iter N]
+
+--fast compares the STRICT batch with the FAST batch under the AUTO policy (dzg_batch_solve_fast:
+FAST that stops at a near tie, those LPs re-solved in STRICT inside the call) instead: both solve
+the workload alternately in one process, three times each (--repeats), and the line reports each
+side's minimum wall time and its spread (max - min), their ratio, how many LPs AUTO handed to
+STRICT, whether every result that stayed FAST with near_ties == 0 has the STRICT result's status
+and pivot log, and the 16-thread oracle's rate.
+
+    python tools/batch_bench.py --fast [--workloads abc] [--repeats 3] [--out profiles/batch_fast_bench.jsonl]
 """
 from __future__ import annotations
 
@@ -98,6 +107,53 @@ def run(name: str, args) -> dict:
     return out
 
 
+def run_fast(name: str, args) -> dict:
+    count, kind, m, ns = WORKLOADS[name]
+    data = [make(1_000_000 * (ord(name) - 96) + i, kind, m, ns) for i in range(count)]
+    lps = [core.CoreLP.from_inequality_form(a, b, c) for a, b, c in data]
+    kw = dict(log_cap=args.log_cap, max_iter=args.max_iter)
+    fkw = dict(kw, numerics=core.AUTO, pivots_per_launch=args.fast_ppl, refactor_every=args.refactor_every)
+    core.solve_batch(lps[:64], pivots_per_launch=args.ppl, **kw)  # warm-up
+    core.solve_batch_fast(lps[:64], **fkw)
+    strict_s, fast_s = [], []
+    for _ in range(args.repeats):
+        strict = core.solve_batch(lps, pivots_per_launch=args.ppl, **kw)
+        strict_s.append(strict[0].solve_ms / 1e3)
+        fast = core.solve_batch_fast(lps, **fkw)
+        fast_s.append(fast[0].solve_ms / 1e3)
+    pivots = sum(r.iterations for r in strict)
+    stayed = [i for i, r in enumerate(fast) if r.numerics == "fast"]
+    clean = [i for i in stayed if fast[i].near_ties == 0]
+    off = [i for i in clean if fast[i].status != strict[i].status
+           or [p[:3] for p in fast[i].pivots] != [p[:3] for p in strict[i].pivots]]
+    off += [i for i, r in enumerate(fast) if r.numerics == "strict" and not same(r, strict[i])]
+    s_min, f_min = min(strict_s), min(fast_s)
+    s_spread, f_spread = max(strict_s) - s_min, max(fast_s) - f_min
+    out = dict(workload=name, mode="fast-vs-strict", lps=count, kind=kind, m=m, n_struct=ns, repeats=args.repeats,
+               total_pivots=pivots, strict_wall_s=[round(t, 4) for t in strict_s],
+               fast_wall_s=[round(t, 4) for t in fast_s], strict_min_s=round(s_min, 4),
+               strict_spread_s=round(s_spread, 4), fast_min_s=round(f_min, 4), fast_spread_s=round(f_spread, 4),
+               strict_pivots_per_s=round(pivots / s_min, 1), fast_pivots_per_s=round(pivots / f_min, 1),
+               fast_over_strict=round(s_min / f_min, 2),
+               fast_beats_strict_by_more_than_the_spread=bool(s_min - f_min > max(s_spread, f_spread)),
+               resolved_in_strict=count - len(stayed), stayed_fast_clean=len(clean),
+               max_refactors=max(r.refactors for r in fast), max_pivot_error=max(r.max_pivot_error for r in fast),
+               log_equal_to_strict=not off, mismatches=len(off), first_mismatch=off[:1])
+    if not args.no_oracle:
+        def one(abc):
+            return ora.simplex_solve(ora.stdform_from_dense(*abc), max_iter=args.max_iter, log_cap=args.log_cap)
+        t0 = time.perf_counter()
+        with ThreadPoolExecutor(max_workers=16) as ex:  # ctypes releases the GIL
+            want = list(ex.map(one, data))
+        t = time.perf_counter() - t0
+        opiv = sum(w.iterations for w in want)
+        out.update(oracle_threads=16, oracle_s=round(t, 3), oracle_pivots_per_s=round(opiv / t, 1),
+                   fast_vs_oracle_pivots=round((pivots / f_min) / (opiv / t), 2),
+                   strict_vs_oracle_pivots=round((pivots / s_min) / (opiv / t), 2),
+                   strict_bit_equal_to_oracle=all(same(g, w) for g, w in zip(strict, want)))
+    return out
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--workloads", default="abc")
@@ -109,15 +165,19 @@ def main() -> int:
                     help="per-LP pivot cap, the same on every side (degenerate 0/1 LPs can cycle: the "
                          "reference's rule has no anti-cycling)")
     ap.add_argument("--out", default=None, help="also append the JSON lines to this file")
+    ap.add_argument("--fast", action="store_true", help="STRICT against FAST/AUTO, alternately (see above)")
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--fast-ppl", type=int, default=0, help="--fast: the FAST batch's pivots per launch")
+    ap.add_argument("--refactor-every", type=int, default=0)
     args = ap.parse_args()
     ok = True
     for name in args.workloads:
-        line = json.dumps(run(name, args))
+        line = json.dumps(run_fast(name, args) if args.fast else run(name, args))
         print(line, flush=True)
         if args.out:
             with open(args.out, "a") as f:
                 f.write(line + "\n")
-        ok = ok and '"bit_equal_to_oracle": false' not in line
+        ok = ok and '"bit_equal_to_oracle": false' not in line and '"log_equal_to_strict": false' not in line
     return 0 if ok else 1
 
 
