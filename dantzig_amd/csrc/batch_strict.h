@@ -3,6 +3,8 @@
 // operation order are described at the top of k_batch.hip; both kernels run exactly this code, so
 // a node LP gives what the same LP gives through dzg_batch_solve, bit for bit.
 //
+// The host side of both (buckets, launches, rounds) is batch_host.h.
+//
 // LDS carve-up (lds_bytes(mmax)): W = mmax x (mmax + 1) doubles, then dx[mmax], v[mmax], one int.
 #pragma once
 
@@ -291,21 +293,7 @@ __device__ int strict_steps(const LpState &S, double *s_mem, int mmax, long long
     return status;
 }
 
-// Row buckets: one launch each, LDS and workgroup size sized for the bucket.
-constexpr int kBucketRows[] = {16, 32, 64, DZG_BATCH_MAX_ROWS};
-constexpr int kBuckets = 4;
-// Workgroups per launch at most: what one launch's pivots_per_launch pivots may cost is bounded by
-// how many workgroups must take turns on a CU.  128 rows: 134 KB of LDS, one workgroup per CU, 256
-// per launch (16 pivots x 2.3 ms measured = 37 ms per launch); 64 rows: four per CU.
-constexpr int kMaxGrid[] = {4096, 4096, 2048, 256};
-
-inline int bucket_of(int64_t m)
-{
-    for (int b = 0; b < kBuckets; ++b)
-        if (m <= kBucketRows[b]) return b;
-    return -1;
-}
-
+// The row buckets, their grid caps and block sizes are in batch_host.h.
 inline size_t lds_bytes(int mmax)
 {
     return sizeof(double) * ((size_t)mmax * (mmax + 1) + 2 * (size_t)mmax) + 16;

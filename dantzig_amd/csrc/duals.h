@@ -2,21 +2,17 @@
 // (k_batch.hip) and the solver handle (engine.hip).  Definitions: DESIGN.md section 7d.
 #pragma once
 
+#include "batch_host.h"
 #include "common.h"
 
-// One LP of a batch as k_duals_small reads it: offsets (elements) into the packed arrays of the
-// batch upload.  c, d are indexed by variable (n entries, at vc_off like var_col); rhs0, y by row.
-struct DzgDualsLp {
-    long long a_off, vc_off, m_off, q_off;
-    double constant;
-    int m, n;
-};
+// k_duals_small reads the batch's own descriptors (DzgBatchLp, batch_host.h): c, d are indexed by
+// variable (n entries, at vc_off like var_col); rhs0, y by row (at m_off).
 
 // per LP: dual_obj, primal_infeas, dual_infeas, max |z - d_N|, max |d_N|
 #define DZG_DUALS_SCAL 5
 
 struct DzgDualsArgs {
-    const DzgDualsLp *lp;
+    const DzgBatchLp *lp;
     const double *A;
     const int *var_col;
     const int *basis, *nonbasis; // the final state of the batch

@@ -30,33 +30,21 @@
 // Every sum's order depends on m alone, every decision is taken by all threads from the same data:
 // an LP's result is bit-identical wherever it sits in a batch.
 //
-// Launches are bounded exactly as in k_batch.hip: at most `ppl` pivots per LP, then the state is in
-// global memory and the workgroup appends its LP to the next round's list if it is still running.
-// Nothing waits on another workgroup.
+// Launches are bounded as in k_batch.hip: at most `ppl` pivots per LP, then the state is in global
+// memory and the workgroup appends its LP to the next round's list if it is still running.  Nothing
+// waits on another workgroup.  The host driver (checks, packing, rounds, results) is batch_host.h's,
+// the one k_batch.hip runs.
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "batch_host.h"
 #include "batch_strict.h"
 #include "common.h"
 #include "fast_decide.h"
 
-int dzg_set_error(int code, const std::string &msg); // engine.hip
-int dzg_lp_valid(const dzg_lp *lp, std::string &why);
-
 namespace {
-
-// One LP of the batch: sizes and its offsets into the packed arrays (elements, not bytes).
-struct FLp {
-    long long a_off;   // A: m x ns column-major, lda = m
-    long long vc_off;  // var_col: n
-    long long m_off;   // basis, x, xbar: m
-    long long q_off;   // nonbasis, z, zbar, dz: n - m
-    long long log_off; // pivot log and margins: log_cap
-    long long log_cap;
-    int m, n, ns, pad;
-};
 
 // What an LP carries from launch to launch beside its vectors.
 struct FState {
@@ -66,7 +54,7 @@ struct FState {
 };
 
 struct FArgs {
-    const FLp *lp;
+    const DzgBatchLp *lp;
     const double *A;
     const int *var_col;
     int *basis, *nonbasis;
@@ -288,7 +276,7 @@ __global__ __launch_bounds__(BLOCK) void k_batch_fast(FArgs g, const int *__rest
 {
     extern __shared__ __attribute__((aligned(16))) double s_mem[];
     const int id = list[blockIdx.x];
-    const FLp L = g.lp[id];
+    const DzgBatchLp L = g.lp[id];
     const int m = L.m, q = L.n - L.m, mmax = g.mmax;
     const int ld = m | 1;
     double *W = s_mem;                                   // m x ld, inside mmax x (mmax + 1)
@@ -473,9 +461,7 @@ __global__ __launch_bounds__(BLOCK) void k_batch_fast(FArgs g, const int *__rest
     }
 }
 
-using dzg_bs::bucket_of;
-using dzg_bs::kBuckets;
-using dzg_bs::kMaxGrid;
+namespace bh = dzg_bh;
 
 void launch_bucket(int b, const FArgs &g, const int *list, int n, int *next_list, int *next_count,
                    hipStream_t st)
@@ -487,279 +473,118 @@ void launch_bucket(int b, const FArgs &g, const int *list, int n, int *next_list
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds_bytes(DZG_BATCH_MAX_ROWS));
         (void)attr;
     }
-    for (int c0 = 0; c0 < n; c0 += kMaxGrid[b]) {
-        const int grid = std::min(kMaxGrid[b], n - c0);
-        // one wave per LP up to 32 rows (no barrier has a second wave to wait for), then 2 and 4
+    bh::for_each_chunk(b, n, [&](int c0, int grid) {
+        const dim3 block(bh::kBlock[b]);
+        // the pricing lanes per column follow the bucket's rows: 16, 32, then the whole wave
         if (b == 0)
-            hipLaunchKernelGGL((k_batch_fast<64, 16>), dim3(grid), dim3(64), lds, st, g, list + c0, next_list,
+            hipLaunchKernelGGL((k_batch_fast<64, 16>), dim3(grid), block, lds, st, g, list + c0, next_list,
                                next_count);
         else if (b == 1)
-            hipLaunchKernelGGL((k_batch_fast<64, 32>), dim3(grid), dim3(64), lds, st, g, list + c0, next_list,
+            hipLaunchKernelGGL((k_batch_fast<64, 32>), dim3(grid), block, lds, st, g, list + c0, next_list,
                                next_count);
         else if (b == 2)
-            hipLaunchKernelGGL((k_batch_fast<128, 64>), dim3(grid), dim3(128), lds, st, g, list + c0, next_list,
+            hipLaunchKernelGGL((k_batch_fast<128, 64>), dim3(grid), block, lds, st, g, list + c0, next_list,
                                next_count);
         else
-            hipLaunchKernelGGL((k_batch_fast<256, 64>), dim3(grid), dim3(256), lds, st, g, list + c0, next_list,
+            hipLaunchKernelGGL((k_batch_fast<256, 64>), dim3(grid), block, lds, st, g, list + c0, next_list,
                                next_count);
-    }
+    });
 }
 
-#define FHIP(expr)                                                                              \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return dzg_set_error(DZG_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+// The control block a FAST LP starts with, as dzg_solver_create starts a FAST solver's.
+void start_ctl(DzgCtl &c0, const dzg_opts &o, long long max_iter)
+{
+    c0.status = DZG_RUNNING;
+    c0.iter_stop = max_iter;
+    c0.enter_pos = c0.leave_pos = -1;
+    c0.del_ce = c0.del_last = -1;
+    c0.rl_listed = -1;
+    c0.tie_tol = c0.tau = o.tie_tol;
+    c0.margin = c0.min_margin = __builtin_inf();
+    c0.first_near_tie = c0.tie_skip_iter = -1;
+    c0.tie_mode = o.near_tie_action == DZG_NEAR_TIE_STOP ? 1 : 0;
+}
 
-struct Section {
-    size_t off = 0, bytes = 0;
-};
+// What FAST reports beyond unpack_common: its counters, the margins and the structural columns of
+// the final basis.
+void write_fast(const dzg_lp &lp, const DzgBatchLp &d, const FState &fs, const int *basis, const double *lmg,
+                dzg_result &r)
+{
+    const DzgCtl &c = fs.ctl;
+    int64_t dense = 0;
+    for (int64_t p = 0; p < lp.m; ++p) {
+        const int var = basis[d.m_off + p];
+        const int64_t code = lp.var_col ? lp.var_col[var] : (var < lp.n_struct ? var : -1);
+        if (code >= 0) ++dense;
+    }
+    const long long cnt = std::min<long long>(r.iterations, d.log_cap);
+    if (r.margins)
+        for (long long k = 0; k < cnt; ++k) r.margins[k] = lmg[d.log_off + k];
+    r.max_pivot_error = fs.max_err_life;
+    r.near_ties = c.near_ties;
+    r.first_near_tie = c.first_near_tie;
+    r.min_margin = c.min_margin;
+    r.dense_columns = dense;
+    r.refactors = fs.refactors;
+}
 
 } // namespace
 
 #define DZG_BATCH_FAST_DEFAULT_PPL 128
 #define DZG_BATCH_FAST_DEFAULT_REFACTOR 64
 
-// The FAST batch itself: `o.near_tie_action` and `o.tie_tol` as given.
+// The FAST batch itself: `o.near_tie_action` and `o.tie_tol` as given.  The driver is batch_host.h's,
+// as in k_batch.hip; the state block and the margins are FAST's own sections.
 static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o, int64_t pivots_per_launch,
                             int64_t refactor_every_arg, dzg_result *res)
 {
     const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
-    const double eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
-    const int ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
-                                                : DZG_BATCH_FAST_DEFAULT_PPL);
-    const int refactor_every = (int)(refactor_every_arg > 0 ? std::min<int64_t>(refactor_every_arg, 1 << 30)
-                                                            : DZG_BATCH_FAST_DEFAULT_REFACTOR);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return dzg_set_error(DZG_E_DEVICE, "no HIP device visible: dantzig_amd has no CPU path");
-    if (o.device < 0 || o.device >= ndev) return dzg_set_error(DZG_E_ARG, "opts.device out of range");
-    FHIP(hipSetDevice(o.device));
+    if (const int rc = bh::use_device(o.device)) return rc;
 
-    // ---- packed layout: one arena, sections 16-B aligned
     const int N = (int)count;
-    std::vector<FLp> desc((size_t)N);
-    long long na = 0, nvc = 0, nm = 0, nq = 0, nlog = 0;
-    int mmax[kBuckets] = {0, 0, 0, 0};
-    std::vector<int> bucket_n(kBuckets, 0);
-    for (int i = 0; i < N; ++i) {
-        const dzg_lp &lp = lps[i];
-        FLp &d = desc[(size_t)i];
-        d.m = (int)lp.m;
-        d.n = (int)lp.n;
-        d.ns = (int)lp.n_struct;
-        d.pad = 0;
-        d.a_off = na;
-        d.vc_off = nvc;
-        d.m_off = nm;
-        d.q_off = nq;
-        d.log_off = nlog;
-        d.log_cap = res[i].log && res[i].log_cap > 0 ? std::min<long long>(res[i].log_cap, max_iter) : 0;
-        na += (long long)lp.m * lp.n_struct;
-        nvc += lp.n;
-        nm += lp.m;
-        nq += lp.n - lp.m;
-        nlog += d.log_cap;
-        const int b = bucket_of(lp.m);
-        mmax[b] = std::max(mmax[b], (int)lp.m);
-        bucket_n[(size_t)b]++;
-    }
-    size_t top = 0;
-    auto section = [&](size_t bytes) {
-        Section s;
-        s.off = top;
-        s.bytes = bytes;
-        top += (bytes + 15) / 16 * 16;
-        return s;
-    };
-    // upload-only, then state (uploaded and downloaded), then log (downloaded), then scratch
-    const Section s_desc = section(sizeof(FLp) * N), s_a = section(sizeof(double) * na),
-                  s_vc = section(sizeof(int) * nvc), s_list = section(sizeof(int) * N);
-    const size_t state0 = top;
-    const Section s_basis = section(sizeof(int) * nm), s_nonbasis = section(sizeof(int) * nq),
-                  s_x = section(sizeof(double) * nm), s_xbar = section(sizeof(double) * nm),
-                  s_z = section(sizeof(double) * nq), s_zbar = section(sizeof(double) * nq),
-                  s_state = section(sizeof(FState) * N);
-    const size_t upload_end = top;
-    const Section s_lk = section(sizeof(int) * nlog), s_le = section(sizeof(int) * nlog),
-                  s_ll = section(sizeof(int) * nlog), s_lmu = section(sizeof(double) * nlog),
-                  s_lmg = section(sizeof(double) * nlog);
-    const size_t download_end = top;
-    const Section s_dz = section(sizeof(double) * nq), s_list2 = section(sizeof(int) * N),
-                  s_count = section(sizeof(int) * kBuckets);
+    const bh::Packed P = bh::pack(lps, res, N, max_iter);
+    bh::Layout L(P);
+    const size_t s_state = L.ar.add(sizeof(FState) * N);
+    L.end_upload();
+    const size_t s_lmg = L.ar.add(sizeof(double) * P.nlog);
+    L.end_download();
 
-    std::vector<unsigned char> host(download_end, 0);
-    auto hp = [&](const Section &s) { return host.data() + s.off; };
-    std::memcpy(hp(s_desc), desc.data(), sizeof(FLp) * N);
-    {
-        double *a = (double *)hp(s_a);
-        int *vc = (int *)hp(s_vc), *bs = (int *)hp(s_basis), *nb = (int *)hp(s_nonbasis);
-        double *x = (double *)hp(s_x), *xb = (double *)hp(s_xbar), *z = (double *)hp(s_z),
-               *zb = (double *)hp(s_zbar);
-        FState *fs = (FState *)hp(s_state);
-        for (int i = 0; i < N; ++i) {
-            const dzg_lp &lp = lps[i];
-            const FLp &d = desc[(size_t)i];
-            const int64_t m = lp.m, q = lp.n - lp.m;
-            for (int64_t j = 0; j < lp.n_struct; ++j)
-                std::memcpy(a + d.a_off + j * m, lp.a + j * lp.lda, sizeof(double) * (size_t)m);
-            for (int64_t v = 0; v < lp.n; ++v)
-                vc[d.vc_off + v] = lp.var_col ? (int)lp.var_col[v]
-                                              : (v < lp.n_struct ? (int)v : (int)(-1 - (v - lp.n_struct)));
-            for (int64_t k = 0; k < m; ++k) {
-                bs[d.m_off + k] = (int)lp.basis[k];
-                x[d.m_off + k] = lp.x[k];
-                xb[d.m_off + k] = lp.xbar ? lp.xbar[k] : 1.0; // Simplex::new, src/simplex.rs:219-220
-            }
-            for (int64_t k = 0; k < q; ++k) {
-                nb[d.q_off + k] = (int)lp.nonbasis[k];
-                z[d.q_off + k] = lp.z[k];
-                zb[d.q_off + k] = lp.zbar ? lp.zbar[k] : 1.0;
-            }
-            DzgCtl &c0 = fs[i].ctl; // as dzg_solver_create starts a FAST solver's
-            c0.status = DZG_RUNNING;
-            c0.iter_stop = max_iter;
-            c0.enter_pos = c0.leave_pos = -1;
-            c0.del_ce = c0.del_last = -1;
-            c0.rl_listed = -1;
-            c0.tie_tol = c0.tau = o.tie_tol;
-            c0.margin = c0.min_margin = __builtin_inf();
-            c0.first_near_tie = c0.tie_skip_iter = -1;
-            c0.tie_mode = o.near_tie_action == DZG_NEAR_TIE_STOP ? 1 : 0;
-        }
-        // the first round's lists: LP indices grouped by bucket
-        int *list = (int *)hp(s_list);
-        std::vector<int> fill(kBuckets, 0);
-        for (int b = 1; b < kBuckets; ++b) fill[(size_t)b] = fill[(size_t)b - 1] + bucket_n[(size_t)b - 1];
-        for (int i = 0; i < N; ++i) list[fill[(size_t)bucket_of(lps[i].m)]++] = i;
-    }
-
-    unsigned char *dev = nullptr;
-    hipStream_t st = nullptr;
-    struct Guard {
-        unsigned char **dev;
-        hipStream_t *st;
-        ~Guard()
-        {
-            if (*dev) (void)hipFree(*dev);
-            if (*st) (void)hipStreamDestroy(*st);
-        }
-    } guard{&dev, &st};
-    FHIP(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-    FHIP(hipMalloc((void **)&dev, top));
-    FHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
+    std::vector<unsigned char> host(L.download_end, 0);
+    bh::fill_upload(host.data(), L, P, lps);
+    FState *fs = (FState *)(host.data() + s_state);
+    for (int i = 0; i < N; ++i) start_ctl(fs[i].ctl, o, max_iter);
+    bh::Device D;
+    if (const int rc = bh::upload(D, L, host.data())) return rc;
+    unsigned char *dev = D.arena;
 
     FArgs g;
-    g.lp = (const FLp *)(dev + s_desc.off);
-    g.A = (const double *)(dev + s_a.off);
-    g.var_col = (const int *)(dev + s_vc.off);
-    g.basis = (int *)(dev + s_basis.off);
-    g.nonbasis = (int *)(dev + s_nonbasis.off);
-    g.x = (double *)(dev + s_x.off);
-    g.xbar = (double *)(dev + s_xbar.off);
-    g.z = (double *)(dev + s_z.off);
-    g.zbar = (double *)(dev + s_zbar.off);
-    g.dz = (double *)(dev + s_dz.off);
-    g.state = (FState *)(dev + s_state.off);
-    g.log_kind = (int *)(dev + s_lk.off);
-    g.log_enter = (int *)(dev + s_le.off);
-    g.log_leave = (int *)(dev + s_ll.off);
-    g.log_mu = (double *)(dev + s_lmu.off);
-    g.log_margin = (double *)(dev + s_lmg.off);
-    g.eps = eps;
-    g.ppl = ppl;
-    g.refactor_every = refactor_every;
+    bh::wire(g, dev, L);
+    g.state = (FState *)(dev + s_state);
+    g.log_margin = (double *)(dev + s_lmg);
+    g.eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
+    g.ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
+                                        : DZG_BATCH_FAST_DEFAULT_PPL);
+    g.refactor_every = (int)(refactor_every_arg > 0 ? std::min<int64_t>(refactor_every_arg, 1 << 30)
+                                                    : DZG_BATCH_FAST_DEFAULT_REFACTOR);
     g.mmax = 0;
-
-    // ---- rounds: every bucket's running LPs, then one readback of the bucket counters
-    int *cur = (int *)(dev + s_list.off), *nxt = (int *)(dev + s_list2.off);
-    int *counts = (int *)(dev + s_count.off);
-    std::vector<int> seg(kBuckets, 0);
-    for (int b = 1; b < kBuckets; ++b) seg[(size_t)b] = seg[(size_t)b - 1] + bucket_n[(size_t)b - 1];
-    std::vector<int> live(bucket_n);
-    for (;;) {
-        bool any = false;
-        FHIP(hipMemsetAsync(counts, 0, sizeof(int) * kBuckets, st));
-        for (int b = 0; b < kBuckets; ++b) {
-            if (live[(size_t)b] == 0) continue;
-            any = true;
+    const int rc_rounds = bh::run_rounds(
+        (int *)(dev + L.list), (int *)(dev + L.list2), (int *)(dev + L.count), bh::segments(P.bucket_n),
+        bh::live_of(P.bucket_n), D.st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
             FArgs gb = g;
-            gb.mmax = mmax[b];
-            launch_bucket(b, gb, cur + seg[(size_t)b], live[(size_t)b], nxt + seg[(size_t)b], counts + b, st);
-            FHIP(hipGetLastError());
-        }
-        if (!any) break;
-        int h_counts[kBuckets];
-        FHIP(hipMemcpyAsync(h_counts, counts, sizeof(h_counts), hipMemcpyDeviceToHost, st));
-        FHIP(hipStreamSynchronize(st));
-        for (int b = 0; b < kBuckets; ++b) live[(size_t)b] = h_counts[b];
-        std::swap(cur, nxt);
-    }
-    FHIP(hipMemcpyAsync(host.data() + state0, dev + state0, download_end - state0, hipMemcpyDeviceToHost, st));
-    FHIP(hipStreamSynchronize(st));
+            gb.mmax = P.mmax[b];
+            launch_bucket(b, gb, list, n, next_list, next_count, D.st);
+        });
+    if (rc_rounds) return rc_rounds;
+    if (const int rc = bh::download(D, L, host.data())) return rc;
 
-    // ---- results
-    const int *bs = (const int *)hp(s_basis), *nb = (const int *)hp(s_nonbasis);
-    const double *x = (const double *)hp(s_x), *xb = (const double *)hp(s_xbar),
-                 *z = (const double *)hp(s_z), *zb = (const double *)hp(s_zbar);
-    const FState *fs = (const FState *)hp(s_state);
-    const int *lk = (const int *)hp(s_lk), *le = (const int *)hp(s_le), *ll = (const int *)hp(s_ll);
-    const double *lmu = (const double *)hp(s_lmu), *lmg = (const double *)hp(s_lmg);
+    const bh::HostView view(host.data(), L);
     for (int i = 0; i < N; ++i) {
-        const dzg_lp &lp = lps[i];
-        const FLp &d = desc[(size_t)i];
-        const DzgCtl &c = fs[i].ctl;
         dzg_result &r = res[i];
-        const int64_t m = lp.m, q = lp.n - lp.m;
-        r.status = c.status;
+        r.status = fs[i].ctl.status;
         r.numerics_used = DZG_NUMERICS_FAST;
-        r.iterations = c.iter;
-        double sum = 0.0; // objective_value, src/simplex.rs:345-352, basis-position order
-        int64_t dense = 0;
-        for (int64_t p = 0; p < m; ++p) {
-            const int var = bs[d.m_off + p];
-            const double prod = lp.c[var] * x[d.m_off + p];
-            sum = sum + prod;
-            const int64_t code = lp.var_col ? lp.var_col[var] : (var < lp.n_struct ? var : -1);
-            if (code >= 0) ++dense;
-        }
-        r.objective = lp.constant + sum;
-        for (int64_t k = 0; k < m; ++k) {
-            if (r.basis) r.basis[k] = bs[d.m_off + k];
-            if (r.x) r.x[k] = x[d.m_off + k];
-            if (r.xbar) r.xbar[k] = xb[d.m_off + k];
-        }
-        for (int64_t k = 0; k < q; ++k) {
-            if (r.nonbasis) r.nonbasis[k] = nb[d.q_off + k];
-            if (r.z) r.z[k] = z[d.q_off + k];
-            if (r.zbar) r.zbar[k] = zb[d.q_off + k];
-        }
-        const long long cnt = std::min<long long>(r.iterations, d.log_cap);
-        for (long long k = 0; k < cnt; ++k) {
-            r.log[k].kind = lk[d.log_off + k];
-            r.log[k].reserved = 0;
-            r.log[k].entering = le[d.log_off + k];
-            r.log[k].leaving = ll[d.log_off + k];
-            r.log[k].mu = lmu[d.log_off + k];
-            if (r.margins) r.margins[k] = lmg[d.log_off + k];
-        }
-        for (int k = 0; k < DZG_K_COUNT; ++k) {
-            r.kernel_ms[k] = 0.0;
-            r.kernel_launches[k] = 0;
-        }
-        r.price_bytes = 0.0;
-        r.solve_ms = 0.0;
-        r.max_pivot_error = fs[i].max_err_life;
-        r.near_ties = c.near_ties;
-        r.first_near_tie = c.first_near_tie;
-        r.min_margin = c.min_margin;
-        r.dense_columns = dense;
-        r.refactors = fs[i].refactors;
-        r.chain_fallbacks = 0;
-        r.price_pass_used = 0;
-        r.price_rows_copy = 0;
-        r.state_drift = 0.0; // not measured by the batched solver
+        r.iterations = fs[i].ctl.iter;
+        bh::unpack_common(lps[i], P.desc[(size_t)i], view, r);
+        write_fast(lps[i], P.desc[(size_t)i], fs[i], view.basis, (const double *)(host.data() + s_lmg), r);
     }
     return 0;
 }
@@ -768,26 +593,14 @@ extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_
                                     int64_t pivots_per_launch, int64_t refactor_every, dzg_result *res)
 {
     // ---- host checks first: malformed input is DZG_E_ARG on any machine
-    if (count < 0) return dzg_set_error(DZG_E_ARG, "batch: count < 0");
-    if (count > 0 && (!lps || !res)) return dzg_set_error(DZG_E_ARG, "batch: lps or res is NULL");
-    if (count >= (1ll << 31)) return dzg_set_error(DZG_E_ARG, "batch: count out of range");
-    if (pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "batch: pivots_per_launch < 0");
+    if (const int rc = bh::check_batch(lps, count, res, pivots_per_launch)) return rc;
     if (refactor_every < 0) return dzg_set_error(DZG_E_ARG, "batch: refactor_every < 0");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
     if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_FAST && o.numerics != DZG_NUMERICS_AUTO)
         return dzg_set_error(DZG_E_ARG, "batch: opts.numerics");
     if (o.numerics == DZG_NUMERICS_STRICT) return dzg_batch_solve(lps, count, &o, pivots_per_launch, res);
-    for (int64_t i = 0; i < count; ++i) {
-        const dzg_lp *lp = &lps[i];
-        std::string why;
-        const std::string at = "batch: lps[" + std::to_string(i) + "]: ";
-        if (!dzg_lp_valid(lp, why)) return dzg_set_error(DZG_E_ARG, at + why);
-        if (lp->m > DZG_BATCH_MAX_ROWS)
-            return dzg_set_error(DZG_E_ARG, at + "m > DZG_BATCH_MAX_ROWS (" + std::to_string(DZG_BATCH_MAX_ROWS) + ")");
-        if (lp->n_struct > 0 && !lp->a) return dzg_set_error(DZG_E_ARG, at + "CSC input is not batched");
-        if (lp->n - lp->m > (1ll << 30)) return dzg_set_error(DZG_E_ARG, at + "too many columns");
-    }
+    if (const int rc = bh::check_batch(lps, count)) return rc;
     if (count == 0) return 0;
     const bool is_auto = o.numerics == DZG_NUMERICS_AUTO;
     if (is_auto) o.near_tie_action = DZG_NEAR_TIE_STOP;

@@ -1,8 +1,9 @@
 // k_mip.hip -- the node LPs of a branch-and-bound round, one workgroup per node, STRICT numerics.
 //
-// The simplex loop is k_batch.hip's (batch_strict.h): the same row buckets, LDS carve-up and
-// pivots_per_launch slicing, so a node LP ends exactly where dzg_batch_solve (and hence
-// dzg_model_solve) would end it.  What is new here:
+// The simplex loop is k_batch.hip's (batch_strict.h) and the round loop, row buckets and chunked
+// launches are the batch's own (batch_host.h): the same LDS carve-up and pivots_per_launch slicing,
+// so a node LP ends exactly where dzg_batch_solve (and hence dzg_model_solve) would end it.  What is
+// new here:
 //
 //   * shared structures.  A node's standard form differs from its structure's only in the
 //     right-hand side of the bound rows of integer variables (model.cpp: a finite bound is a row
@@ -13,8 +14,8 @@
 //     integer variable.  On its first slice (iter < 0) the workgroup builds x = rhs from the row
 //     table, x̄ = z̄ = 1, the slack basis and the structure's nonbasis and z0.
 //   * device epilogue on OPTIMAL.  The objective is one sequential sum in basis-position order
-//     (k_batch.hip's host loop, unfused); the user values are x+ - x- found through a copy of the
-//     basis in LDS; the integrality test and the branching choice are mip_branch_choice
+//     (unpack_common's host loop in batch_host.h, unfused); the user values are x+ - x- found
+//     through a copy of the basis in LDS; the integrality test and the branching choice are mip_branch_choice
 //     (mip_internal.h), the host's own code.  The node's compact record is written; values stay on
 //     the device unless the node is integral.
 //   * warm starts (dzg_mip_opts.warm_start).  A node with a parent-state slot takes
@@ -29,20 +30,19 @@
 #include <string>
 #include <vector>
 
+#include "batch_host.h"
 #include "batch_strict.h"
 #include "common.h"
 #include "mip_internal.h"
-
-int dzg_set_error(int code, const std::string &msg); // engine.hip
 
 using dzg_internal::MipNodeRecord;
 using dzg_internal::MipStructure;
 
 namespace {
 
-using dzg_bs::bucket_of;
-using dzg_bs::kBuckets;
-using dzg_bs::kMaxGrid;
+namespace bh = dzg_bh;
+using bh::bucket_of;
+using bh::kBuckets;
 using dzg_bs::lds_bytes;
 
 // One structure: offsets into the double / int pools (elements).
@@ -273,28 +273,14 @@ void launch_bucket(int b, const MArgs &g, const int *list, int n, int *next_list
                    hipStream_t st)
 {
     const size_t lds = lds_bytes(g.mmax);
-    for (int c0 = 0; c0 < n; c0 += kMaxGrid[b]) {
-        const int grid = std::min(kMaxGrid[b], n - c0);
-        if (b <= 1)
-            hipLaunchKernelGGL(k_mip_node<64>, dim3(grid), dim3(64), lds, st, g, list + c0,
-                               next_list, next_count);
-        else if (b == 2)
-            hipLaunchKernelGGL(k_mip_node<128>, dim3(grid), dim3(128), lds, st, g, list + c0,
-                               next_list, next_count);
-        else
-            hipLaunchKernelGGL(k_mip_node<256>, dim3(grid), dim3(256), lds, st, g, list + c0,
-                               next_list, next_count);
-    }
+    bh::for_each_chunk(b, n, [&](int c0, int grid) {
+        bh::with_block(b, [&](auto block) {
+            constexpr int BLOCK = decltype(block)::value;
+            hipLaunchKernelGGL(k_mip_node<BLOCK>, dim3(grid), dim3(BLOCK), lds, st, g, list + c0, next_list,
+                               next_count);
+        });
+    });
 }
-
-#define MHIP(expr)                                                                              \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess)                                                                   \
-            return dzg_set_error(DZG_E_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-size_t align16(size_t b) { return (b + 15) / 16 * 16; }
 
 } // namespace
 
@@ -329,11 +315,7 @@ struct MipGpu {
 int mip_gpu_create(MipGpu **out, int device, int nvars, const std::vector<int> &int_vars)
 {
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return dzg_set_error(DZG_E_DEVICE, "no HIP device visible: dantzig_amd has no CPU path");
-    if (device < 0 || device >= ndev) return dzg_set_error(DZG_E_ARG, "opts.device out of range");
-    MHIP(hipSetDevice(device));
+    if (const int rc = bh::use_device(device)) return rc;
     MipGpu *g = new MipGpu;
     g->device = device;
     g->nvars = nvars;
@@ -401,10 +383,10 @@ static int upload_structures(MipGpu *g)
         d.pv_off = put_i(s.pos_var);
         put_i(s.neg_var); // directly after pos_var
     }
-    const size_t o_sd = 0, o_iv = align16(o_sd + sizeof(SDesc) * ns),
-                 o_ip = align16(o_iv + sizeof(int) * (g->int_vars.size() + 1)),
-                 o_dp = align16(o_ip + sizeof(int) * (ipool.size() + 1)),
-                 total = align16(o_dp + sizeof(double) * (dpool.size() + 1));
+    bh::Arena ar;
+    const size_t o_sd = ar.add(sizeof(SDesc) * ns), o_iv = ar.add(sizeof(int) * (g->int_vars.size() + 1)),
+                 o_ip = ar.add(sizeof(int) * (ipool.size() + 1)), o_dp = ar.add(sizeof(double) * (dpool.size() + 1)),
+                 total = ar.top;
     std::vector<unsigned char> host(total, 0);
     std::memcpy(host.data() + o_sd, sd.data(), sizeof(SDesc) * ns);
     if (!g->int_vars.empty())
@@ -412,13 +394,13 @@ static int upload_structures(MipGpu *g)
     if (!ipool.empty()) std::memcpy(host.data() + o_ip, ipool.data(), sizeof(int) * ipool.size());
     if (!dpool.empty()) std::memcpy(host.data() + o_dp, dpool.data(), sizeof(double) * dpool.size());
     if (g->sdev) {
-        MHIP(hipStreamSynchronize(g->st));
-        MHIP(hipFree(g->sdev));
+        DZG_HIP(hipStreamSynchronize(g->st));
+        DZG_HIP(hipFree(g->sdev));
         g->sdev = nullptr;
     }
-    MHIP(hipMalloc((void **)&g->sdev, total));
-    MHIP(hipMemcpyAsync(g->sdev, host.data(), total, hipMemcpyHostToDevice, g->st));
-    MHIP(hipStreamSynchronize(g->st));
+    DZG_HIP(hipMalloc((void **)&g->sdev, total));
+    DZG_HIP(hipMemcpyAsync(g->sdev, host.data(), total, hipMemcpyHostToDevice, g->st));
+    DZG_HIP(hipStreamSynchronize(g->st));
     g->base.sd = (const SDesc *)(g->sdev + o_sd);
     g->base.int_vars = (const int *)(g->sdev + o_iv);
     g->base.ipool = (const int *)(g->sdev + o_ip);
@@ -446,7 +428,7 @@ void mip_gpu_slot_free(MipGpu *g, int slot) { g->pool_free.push_back(slot); }
 int mip_gpu_save_states(MipGpu *g, const int *pairs, int count)
 {
     if (count <= 0) return 0;
-    MHIP(hipSetDevice(g->device));
+    DZG_HIP(hipSetDevice(g->device));
     const long long si = DZG_BATCH_MAX_ROWS + g->pool_q, sz = g->pool_q > 0 ? g->pool_q : 1;
     for (int i = 0; i < count; ++i)
         if (pairs[2 * i] < 0 || pairs[2 * i] >= g->last_count || pairs[2 * i + 1] < 0 ||
@@ -456,14 +438,14 @@ int mip_gpu_save_states(MipGpu *g, const int *pairs, int count)
         const int cap = std::max(64, g->pool_used + g->pool_used / 2);
         int *ni = nullptr;
         double *nz = nullptr;
-        MHIP(hipMalloc((void **)&ni, sizeof(int) * si * cap));
-        MHIP(hipMalloc((void **)&nz, sizeof(double) * sz * cap));
+        DZG_HIP(hipMalloc((void **)&ni, sizeof(int) * si * cap));
+        DZG_HIP(hipMalloc((void **)&nz, sizeof(double) * sz * cap));
         if (g->pool_cap > 0) {
-            MHIP(hipMemcpyAsync(ni, g->pool_i, sizeof(int) * si * g->pool_cap, hipMemcpyDeviceToDevice, g->st));
-            MHIP(hipMemcpyAsync(nz, g->pool_z, sizeof(double) * sz * g->pool_cap, hipMemcpyDeviceToDevice, g->st));
-            MHIP(hipStreamSynchronize(g->st));
-            MHIP(hipFree(g->pool_i));
-            MHIP(hipFree(g->pool_z));
+            DZG_HIP(hipMemcpyAsync(ni, g->pool_i, sizeof(int) * si * g->pool_cap, hipMemcpyDeviceToDevice, g->st));
+            DZG_HIP(hipMemcpyAsync(nz, g->pool_z, sizeof(double) * sz * g->pool_cap, hipMemcpyDeviceToDevice, g->st));
+            DZG_HIP(hipStreamSynchronize(g->st));
+            DZG_HIP(hipFree(g->pool_i));
+            DZG_HIP(hipFree(g->pool_z));
         }
         g->pool_i = ni;
         g->pool_z = nz;
@@ -471,21 +453,21 @@ int mip_gpu_save_states(MipGpu *g, const int *pairs, int count)
     }
     if (count > g->pairs_cap) {
         if (g->pairs_dev) {
-            MHIP(hipStreamSynchronize(g->st));
-            MHIP(hipFree(g->pairs_dev));
+            DZG_HIP(hipStreamSynchronize(g->st));
+            DZG_HIP(hipFree(g->pairs_dev));
             g->pairs_dev = nullptr;
         }
         const int cap = std::max(256, count + count / 2);
-        MHIP(hipMalloc((void **)&g->pairs_dev, sizeof(int) * 2 * cap));
+        DZG_HIP(hipMalloc((void **)&g->pairs_dev, sizeof(int) * 2 * cap));
         g->pairs_cap = cap;
     }
-    MHIP(hipMemcpyAsync(g->pairs_dev, pairs, sizeof(int) * 2 * count, hipMemcpyHostToDevice, g->st));
+    DZG_HIP(hipMemcpyAsync(g->pairs_dev, pairs, sizeof(int) * 2 * count, hipMemcpyHostToDevice, g->st));
     MArgs a = g->last;
     a.pool_si = si;
     a.pool_sz = sz;
     hipLaunchKernelGGL(k_mip_save, dim3(count), dim3(64), 0, g->st, a, g->pairs_dev, g->pool_i, g->pool_z);
-    MHIP(hipGetLastError());
-    MHIP(hipStreamSynchronize(g->st)); // `pairs` is the caller's; the next round reads the slots
+    DZG_HIP(hipGetLastError());
+    DZG_HIP(hipStreamSynchronize(g->st)); // `pairs` is the caller's; the next round reads the slots
     return 0;
 }
 
@@ -494,7 +476,7 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
                         double *values)
 {
     if (count <= 0) return 0;
-    MHIP(hipSetDevice(g->device));
+    DZG_HIP(hipSetDevice(g->device));
     if (g->dirty) {
         const int rc = upload_structures(g);
         if (rc < 0) return rc;
@@ -503,7 +485,7 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
     std::vector<NDesc> nd((size_t)count);
     long long nm = 0, nq = 0;
     int mmax[kBuckets] = {0, 0, 0, 0};
-    std::vector<int> bucket_n(kBuckets, 0);
+    int bucket_n[kBuckets] = {0, 0, 0, 0};
     for (int i = 0; i < count; ++i) {
         const MipStructure &s = g->structs[(size_t)sid[i]];
         nd[(size_t)i].sid = sid[i];
@@ -516,52 +498,46 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
         nq += s.n - s.m;
         const int b = bucket_of(s.m);
         mmax[b] = std::max(mmax[b], s.m);
-        bucket_n[(size_t)b]++;
+        bucket_n[b]++;
     }
     const size_t nb2 = (size_t)count * 2 * (size_t)g->nint;
-    size_t top = 0;
-    auto sec = [&](size_t bytes) {
-        const size_t off = top;
-        top = align16(top + bytes);
-        return off;
-    };
+    bh::Arena ar;
     // uploaded: descriptors, bounds, the first list; then device-only state and results
-    const size_t o_nd = sec(sizeof(NDesc) * count), o_bnd = sec(sizeof(double) * (nb2 + 1)),
-                 o_list = sec(sizeof(int) * count);
-    const size_t upload_end = top;
-    const size_t o_iter = sec(sizeof(long long) * count), o_rec = sec(sizeof(MipNodeRecord) * count),
-                 o_status = sec(sizeof(int) * count), o_list2 = sec(sizeof(int) * count),
-                 o_counts = sec(sizeof(int) * kBuckets), o_basis = sec(sizeof(int) * (nm + 1)),
-                 o_nonbasis = sec(sizeof(int) * (nq + 1)), o_x = sec(sizeof(double) * (nm + 1)),
-                 o_xbar = sec(sizeof(double) * (nm + 1)), o_z = sec(sizeof(double) * (nq + 1)),
-                 o_zbar = sec(sizeof(double) * (nq + 1)), o_dz = sec(sizeof(double) * (nq + 1)),
-                 o_vals = sec(sizeof(double) * ((size_t)count * g->nvars + 1));
-    if (top > g->rcap) { // one allocation, grown by half again so that few rounds reallocate
+    const size_t o_nd = ar.add(sizeof(NDesc) * count), o_bnd = ar.add(sizeof(double) * (nb2 + 1)),
+                 o_list = ar.add(sizeof(int) * count);
+    const size_t upload_end = ar.top;
+    const size_t o_iter = ar.add(sizeof(long long) * count), o_rec = ar.add(sizeof(MipNodeRecord) * count),
+                 o_status = ar.add(sizeof(int) * count), o_list2 = ar.add(sizeof(int) * count),
+                 o_counts = ar.add(sizeof(int) * kBuckets), o_basis = ar.add(sizeof(int) * (nm + 1)),
+                 o_nonbasis = ar.add(sizeof(int) * (nq + 1)), o_x = ar.add(sizeof(double) * (nm + 1)),
+                 o_xbar = ar.add(sizeof(double) * (nm + 1)), o_z = ar.add(sizeof(double) * (nq + 1)),
+                 o_zbar = ar.add(sizeof(double) * (nq + 1)), o_dz = ar.add(sizeof(double) * (nq + 1)),
+                 o_vals = ar.add(sizeof(double) * ((size_t)count * g->nvars + 1));
+    if (const size_t top = ar.top; top > g->rcap) { // one allocation, grown by half again so that few rounds reallocate
         if (g->rdev) {
-            MHIP(hipStreamSynchronize(g->st));
-            MHIP(hipFree(g->rdev));
+            DZG_HIP(hipStreamSynchronize(g->st));
+            DZG_HIP(hipFree(g->rdev));
             g->rdev = nullptr;
             g->rcap = 0;
         }
         const size_t cap = top + top / 2;
-        MHIP(hipMalloc((void **)&g->rdev, cap));
+        DZG_HIP(hipMalloc((void **)&g->rdev, cap));
         g->rcap = cap;
     }
     std::vector<unsigned char> host(upload_end, 0);
     std::memcpy(host.data() + o_nd, nd.data(), sizeof(NDesc) * count);
     if (nb2) std::memcpy(host.data() + o_bnd, bnd, sizeof(double) * nb2);
-    std::vector<int> seg(kBuckets, 0);
-    for (int b = 1; b < kBuckets; ++b) seg[(size_t)b] = seg[(size_t)b - 1] + bucket_n[(size_t)b - 1];
+    const bh::Segments seg = bh::segments(bucket_n);
     {
         int *list = (int *)(host.data() + o_list);
-        std::vector<int> fill(seg);
+        bh::Segments fill = seg;
         for (int i = 0; i < count; ++i) list[fill[(size_t)bucket_of(g->structs[(size_t)sid[i]].m)]++] = i;
     }
     unsigned char *dev = g->rdev;
     hipStream_t st = g->st;
-    MHIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
-    MHIP(hipMemsetAsync(dev + o_iter, 0xff, sizeof(long long) * count, st)); // -1: not initialised
-    MHIP(hipMemsetAsync(dev + o_rec, 0, sizeof(MipNodeRecord) * count, st)); // warm = 0: no restart yet
+    DZG_HIP(hipMemcpyAsync(dev, host.data(), upload_end, hipMemcpyHostToDevice, st));
+    DZG_HIP(hipMemsetAsync(dev + o_iter, 0xff, sizeof(long long) * count, st)); // -1: not initialised
+    DZG_HIP(hipMemsetAsync(dev + o_rec, 0, sizeof(MipNodeRecord) * count, st)); // warm = 0: no restart yet
 
     MArgs a = g->base;
     a.nd = (const NDesc *)(dev + o_nd);
@@ -588,37 +564,23 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
     g->last = a;
     g->last_count = count;
 
-    int *cur = (int *)(dev + o_list), *nxt = (int *)(dev + o_list2);
-    int *counts = (int *)(dev + o_counts);
-    std::vector<int> live(bucket_n);
-    for (;;) {
-        bool any = false;
-        MHIP(hipMemsetAsync(counts, 0, sizeof(int) * kBuckets, st));
-        for (int b = 0; b < kBuckets; ++b) {
-            if (live[(size_t)b] == 0) continue;
-            any = true;
-            MArgs ab = a;
-            ab.mmax = mmax[b];
-            launch_bucket(b, ab, cur + seg[(size_t)b], live[(size_t)b], nxt + seg[(size_t)b],
-                          counts + b, st);
-            MHIP(hipGetLastError());
-        }
-        if (!any) break;
-        int h_counts[kBuckets];
-        MHIP(hipMemcpyAsync(h_counts, counts, sizeof(h_counts), hipMemcpyDeviceToHost, st));
-        MHIP(hipStreamSynchronize(st));
-        for (int b = 0; b < kBuckets; ++b) live[(size_t)b] = h_counts[b];
-        std::swap(cur, nxt);
-    }
-    MHIP(hipMemcpyAsync(rec, dev + o_rec, sizeof(MipNodeRecord) * count, hipMemcpyDeviceToHost, st));
-    MHIP(hipStreamSynchronize(st));
+    const int rc = bh::run_rounds((int *)(dev + o_list), (int *)(dev + o_list2), (int *)(dev + o_counts), seg,
+                                  bh::live_of(bucket_n), st,
+                                  [&](int b, const int *list, int n, int *next_list, int *next_count) {
+                                      MArgs ab = a;
+                                      ab.mmax = mmax[b];
+                                      launch_bucket(b, ab, list, n, next_list, next_count, st);
+                                  });
+    if (rc) return rc;
+    DZG_HIP(hipMemcpyAsync(rec, dev + o_rec, sizeof(MipNodeRecord) * count, hipMemcpyDeviceToHost, st));
+    DZG_HIP(hipStreamSynchronize(st));
     if (g->nvars > 0)
         for (int i = 0; i < count; ++i)
             if (rec[i].status == DZG_OPTIMAL && rec[i].integral)
-                MHIP(hipMemcpyAsync(values + (size_t)i * g->nvars,
+                DZG_HIP(hipMemcpyAsync(values + (size_t)i * g->nvars,
                                     dev + o_vals + sizeof(double) * (size_t)i * g->nvars,
                                     sizeof(double) * g->nvars, hipMemcpyDeviceToHost, st));
-    MHIP(hipStreamSynchronize(st));
+    DZG_HIP(hipStreamSynchronize(st));
     return 0;
 }
 

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(BLOCK) void k_ranging_small(DzgRangingArgs g, const
     extern __shared__ __attribute__((aligned(16))) double s_mem[];
     __shared__ DzgRangePart s_red[4];
     const DzgRangeItem it = items[blockIdx.x];
-    const DzgDualsLp L = g.lp[it.lp];
+    const DzgBatchLp L = g.lp[it.lp];
     const int m = L.m, q = L.n - L.m, ld = m + 1;
     const double *A = g.A + L.a_off;
     const int *var_col = g.var_col + L.vc_off;
@@ -371,16 +371,12 @@ void dzg_launch_ranging_small(int bucket, const DzgRangingArgs &g, const DzgRang
                               hipStream_t st)
 {
     const size_t lds = dzg_bs::lds_bytes(g.mmax);
-    for (int c0 = 0; c0 < n; c0 += dzg_bs::kMaxGrid[bucket]) {
-        const int grid = n - c0 < dzg_bs::kMaxGrid[bucket] ? n - c0 : dzg_bs::kMaxGrid[bucket];
-        // the workgroup sizes of k_batch_strict's buckets
-        if (bucket <= 1)
-            hipLaunchKernelGGL(k_ranging_small<64>, dim3(grid), dim3(64), lds, st, g, items + c0);
-        else if (bucket == 2)
-            hipLaunchKernelGGL(k_ranging_small<128>, dim3(grid), dim3(128), lds, st, g, items + c0);
-        else
-            hipLaunchKernelGGL(k_ranging_small<256>, dim3(grid), dim3(256), lds, st, g, items + c0);
-    }
+    dzg_bh::for_each_chunk(bucket, n, [&](int c0, int grid) {
+        dzg_bh::with_block(bucket, [&](auto block) {
+            constexpr int BLOCK = decltype(block)::value;
+            hipLaunchKernelGGL(k_ranging_small<BLOCK>, dim3(grid), dim3(BLOCK), lds, st, g, items + c0);
+        });
+    });
 }
 
 void dzg_launch_range_ratio(int n, const double *src, const double *sub, const double *val, const int *idx,

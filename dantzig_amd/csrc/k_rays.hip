@@ -36,7 +36,7 @@ __global__ __launch_bounds__(BLOCK) void k_rays_small(DzgRaysArgs g, const int *
     extern __shared__ __attribute__((aligned(16))) double s_mem[];
     __shared__ double s_red[4][2];
     const int id = list[blockIdx.x];
-    const DzgDualsLp L = g.lp[id];
+    const DzgBatchLp L = g.lp[id];
     const int m = L.m, q = L.n - L.m;
     const double *A = g.A + L.a_off;
     const int *var_col = g.var_col + L.vc_off;
@@ -304,16 +304,12 @@ __global__ __launch_bounds__(256) void k_ray_finish(int kind, int m, int q, int 
 void dzg_launch_rays_small(int bucket, const DzgRaysArgs &g, const int *list, int n, hipStream_t st)
 {
     const size_t lds = dzg_bs::lds_bytes(g.mmax);
-    for (int c0 = 0; c0 < n; c0 += dzg_bs::kMaxGrid[bucket]) {
-        const int grid = n - c0 < dzg_bs::kMaxGrid[bucket] ? n - c0 : dzg_bs::kMaxGrid[bucket];
-        // the workgroup sizes of k_batch_strict's buckets
-        if (bucket <= 1)
-            hipLaunchKernelGGL(k_rays_small<64>, dim3(grid), dim3(64), lds, st, g, list + c0);
-        else if (bucket == 2)
-            hipLaunchKernelGGL(k_rays_small<128>, dim3(grid), dim3(128), lds, st, g, list + c0);
-        else
-            hipLaunchKernelGGL(k_rays_small<256>, dim3(grid), dim3(256), lds, st, g, list + c0);
-    }
+    dzg_bh::for_each_chunk(bucket, n, [&](int c0, int grid) {
+        dzg_bh::with_block(bucket, [&](auto block) {
+            constexpr int BLOCK = decltype(block)::value;
+            hipLaunchKernelGGL(k_rays_small<BLOCK>, dim3(grid), dim3(BLOCK), lds, st, g, list + c0);
+        });
+    });
 }
 
 void dzg_launch_ray_rhs(int m, const double *A, long long lda, int code, double *out, hipStream_t st)

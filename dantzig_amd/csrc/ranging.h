@@ -25,7 +25,7 @@ struct DzgRangeItem {
 };
 
 struct DzgRangingArgs {
-    const DzgDualsLp *lp;
+    const DzgBatchLp *lp;
     const double *A;
     const int *var_col;
     const int *basis, *nonbasis; // the final state of the batch

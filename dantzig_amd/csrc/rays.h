@@ -9,7 +9,7 @@
 #define DZG_RAY_SCAL 5
 
 struct DzgRaysArgs {
-    const DzgDualsLp *lp;
+    const DzgBatchLp *lp;
     const double *A;
     const int *var_col;
     const int *basis, *nonbasis; // the final state of the batch

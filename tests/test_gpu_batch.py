@@ -1,6 +1,8 @@
 """The batched STRICT solver on the GPU (dzg_batch_solve, core.solve_batch, solve_many): every LP
 of a batch follows the CPU oracle bit for bit, and neither the launch slicing nor the company an LP
 keeps in a batch changes anything about it."""
+import dataclasses
+import itertools
 import json
 import os
 import random
@@ -253,3 +255,76 @@ def test_solve_many_equals_one_solve_per_model():
     assert "optimal" in kinds and len(kinds) >= 2, kinds
     with pytest.raises((dz.exceptions.UnboundedError, dz.exceptions.InfeasibleError), match=r"\(model \d+\)"):
         dz.solve_many([p for _, p in items])
+
+
+def assert_same_extra(got, want, what=""):
+    """A CoreDuals, CoreRanging or CoreRay (or None on both sides), every field bit for bit."""
+    assert (got is None) == (want is None), what
+    if got is None:
+        return
+    for f in dataclasses.fields(got):
+        g, w = getattr(got, f.name), getattr(want, f.name)
+        if dataclasses.is_dataclass(g) or g is None or w is None:
+            assert_same_extra(g, w, f"{what} {f.name}")
+        elif isinstance(g, (float, np.ndarray)) and np.asarray(g).dtype.kind == "f":
+            assert_bit_equal(g, w, f"{what} {f.name}")
+        else:
+            assert np.array_equal(g, w), f"{what} {f.name}"
+
+
+_FOUR_WAYS = (dict(), dict(duals=True), dict(ranging=True), dict(rays=True, duals=True))
+
+
+def test_the_passes_disturb_neither_the_solve_nor_each_other():
+    rows = (1, 16, 17, 32, 33, 64, 65, 128)  # both sides of every bucket edge
+    # seeds at which every bucket holds an LP that ends optimal (m = 1, 17, 64, 65) for the duals and
+    # ranging passes, and the first three one that ends unbounded (m = 16, 33) for the rays pass
+    data = [_family(46 + k, k % 3, m, 2 * m if m <= 64 else 80) for k, m in enumerate(rows)]
+    data += _parity_set()[-2:]  # the unbounded LP and the infeasible one
+    data.append((np.zeros((0, 3)), np.zeros(0), np.array([1.0, -1.0, 0.0])))  # no rows
+    lps = [core.CoreLP.from_inequality_form(a, b, c) for a, b, c in data]
+    full = [core.solve_batch(lps, **kw) for kw in _FOUR_WAYS]
+    assert {"optimal", "unbounded", "infeasible"} <= {r.status for r in full[0]}
+    assert [full[0][rows.index(m)].status for m in (1, 17, 64, 65)] == ["optimal"] * 4
+    assert [full[0][rows.index(m)].status for m in (16, 33)] == ["unbounded"] * 2
+    for i in range(len(lps)):
+        for (p, a), (q, b) in itertools.combinations(enumerate(full), 2):
+            assert_same_run(a[i], b[i], f"LP {i}, calls {p} and {q}")
+        assert (full[1][i].duals is not None) == (full[0][i].status == "optimal"), i
+        assert (full[2][i].ranging is not None) == (full[0][i].status == "optimal"), i
+        assert (full[3][i].ray is not None) == (full[0][i].status in ("unbounded", "infeasible")), i
+        assert_same_extra(full[2][i].duals, full[1][i].duals, f"LP {i} duals, ranging call")
+        assert_same_extra(full[3][i].duals, full[1][i].duals, f"LP {i} duals, rays call")
+    # buckets 1 and 2 empty: every LP is what it was in the full batch
+    keep = [i for i, lp in enumerate(lps) if lp.m <= 16 or lp.m > 64]
+    assert len(keep) == len(lps) - 4
+    for kw, whole in zip(_FOUR_WAYS, full):
+        part = core.solve_batch([lps[i] for i in keep], **kw)
+        for g, i in zip(part, keep):
+            assert_same_run(g, whole[i], f"LP {i} {kw}")
+            for name in ("duals", "ranging", "ray"):
+                assert_same_extra(getattr(g, name), getattr(whole[i], name), f"LP {i} {kw} {name}")
+
+
+def test_the_grid_cap_is_invisible_to_the_passes():
+    count, m, ns = 257, 65, 8  # the largest bucket's smallest LPs, one more than its 256 workgroups
+    data = [_family(9300 + i, 2 * (i % 2), m, ns) for i in range(count)]
+    want = [ora.simplex_solve(ora.stdform_from_dense(a, b, c)).status for a, b, c in data]
+    ended = [i for i, s in enumerate(want) if s in ("unbounded", "infeasible")]
+    # enough OPTIMAL LPs that their 2 directions each need a second launch, LP 256 among them
+    assert want[256] == "optimal" and want.count("optimal") > 128 and ended, want
+    lps = [core.CoreLP.from_inequality_form(a, b, c) for a, b, c in data]
+    reqs = [([{i % (m + ns): 1.0}], [{i % m: 1.0}]) for i in range(count)]
+    certified = core.solve_batch(lps, duals=True, rays=True)
+    ranged = core.solve_batch(lps, ranging=reqs)
+    assert [r.status for r in certified] == want
+    for i in (256, ended[-1]):  # and the last LP of the rays pass's list
+        one = core.solve_batch([lps[i]], duals=True, rays=True)[0]
+        assert_same_run(certified[i], one, f"LP {i}")
+        assert_same_extra(certified[i].duals, one.duals, f"LP {i} duals")
+        assert_same_extra(certified[i].ray, one.ray, f"LP {i} ray")
+        one = core.solve_batch([lps[i]], ranging=[reqs[i]])[0]
+        assert_same_run(ranged[i], one, f"LP {i}, ranging call")
+        assert_same_extra(ranged[i].ranging, one.ranging, f"LP {i} ranges")
+    assert certified[256].duals is not None and ranged[256].ranging is not None
+    assert certified[ended[-1]].ray is not None
