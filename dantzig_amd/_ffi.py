@@ -46,7 +46,7 @@ EXPORTS = [
     "dzg_model_solve_batch_ranging",
     "dzg_solver_ray", "dzg_batch_solve_rays", "dzg_model_solve_rays", "dzg_model_solve_batch_rays",
     "dzg_model_map_ray",
-    "dzg_batch_solve_fast", "dzg_model_solve_batch_fast",
+    "dzg_batch_solve_fast", "dzg_model_solve_batch_fast", "dzg_debug_batch_fast_inverse",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -259,6 +259,9 @@ def lib() -> C.CDLL:
         _lib.dzg_batch_solve_fast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
                                               C.c_void_p]
         _lib.dzg_model_solve_batch_fast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_debug_batch_fast_inverse.restype = C.c_int
+        _lib.dzg_debug_batch_fast_inverse.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                                      C.c_void_p, C.c_void_p]
         _lib.dzg_solver_duals.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_batch_solve_duals.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p,
                                                C.c_void_p]

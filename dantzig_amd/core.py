@@ -585,8 +585,6 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
     is LP i's CoreResult; `.numerics` says which numerics produced it, and near_ties, first_near_tie,
     min_margin, margins, max_pivot_error and refactors mean what they mean for a single FAST solve.
     pivots_per_launch 0 = 128; refactor_every 0 = 64 pivots between two rebuilds of the inverse."""
-    import time
-
     lps = list(lps)
     allowed = {"numerics", "near_tie_action", "tie_tol", "max_iter", "epsilon", "device"}
     unknown = set(opts) - allowed
@@ -596,6 +594,19 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
         raise ValueError("solve_batch_fast: numerics is STRICT, FAST or AUTO")
     if int(pivots_per_launch) < 0 or int(refactor_every) < 0:
         raise ValueError("solve_batch_fast: pivots_per_launch and refactor_every are >= 0")
+
+    def invoke(c_lps, count, o, res):
+        return _ffi.lib().dzg_batch_solve_fast(c_lps, C.c_int64(count), C.byref(o),
+                                               C.c_int64(int(pivots_per_launch)),
+                                               C.c_int64(int(refactor_every)), res)
+    return _batch_fast(lps, log, log_cap, opts, "dzg_batch_solve_fast", invoke)
+
+
+def _batch_fast(lps, log, log_cap, opts, name, invoke) -> list:
+    """The Python-side checks, the marshalling and the results of a FAST batch entry point `name`;
+    invoke(c_lps, count, opts, res) makes the call and returns its code."""
+    import time
+
     for i, lp in enumerate(lps):
         if lp.block is not None:
             raise ValueError(f"lps[{i}]: a column-block LP cannot be batched")
@@ -627,10 +638,9 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
         r.log_cap = cap
     o = _ffi.default_opts(**opts)
     t0 = time.perf_counter()
-    rc = _ffi.lib().dzg_batch_solve_fast(c_lps, C.c_int64(count), C.byref(o), C.c_int64(int(pivots_per_launch)),
-                                         C.c_int64(int(refactor_every)), res)
+    rc = invoke(c_lps, count, o, res)
     wall_ms = (time.perf_counter() - t0) * 1e3
-    _ffi.check(rc, "dzg_batch_solve_fast")
+    _ffi.check(rc, name)
     out = []
     for i in range(count):
         r = res[i]
@@ -788,3 +798,30 @@ def merge_candidates(cands) -> int:
     for i, (r, p, y, yb, dy) in enumerate(cands):
         arr[i] = _ffi.Candidate(r, p if p >= 0 else (1 << 63) - 1, y, yb, dy)
     return int(_ffi.lib().dzg_merge_candidates(arr, C.c_int64(len(cands))))
+
+
+def debug_batch_fast_inverse(lps, pivots: int, refactor_every: int = 0, log: bool = True,
+                             log_cap: int = 4096, **opts) -> list:
+    """Test hook (dzg_debug_batch_fast_inverse): what one launch of the FAST batch kernel keeps in LDS.
+    Every LP's inverse W is built from its starting basis, at most `pivots` pivots run (refactor_every
+    as in solve_batch_fast; above `pivots`: no rebuild inside the launch), and LP i comes back as
+    (CoreResult, W): the result as solve_batch_fast reports it ("iter_limit" if the budget ended it)
+    and W as an (m, m) array, row p basis position p, column r constraint row r.  FAST numerics only;
+    keywords near_tie_action, tie_tol, epsilon, device."""
+    lps = list(lps)
+    allowed = {"numerics", "near_tie_action", "tie_tol", "epsilon", "device"}
+    unknown = set(opts) - allowed
+    if unknown:
+        raise ValueError(f"debug_batch_fast_inverse takes {sorted(allowed)}, not {sorted(unknown)}")
+    if opts.setdefault("numerics", FAST) != FAST:
+        raise ValueError("debug_batch_fast_inverse: FAST numerics only")
+    if int(pivots) < 0 or int(refactor_every) < 0:
+        raise ValueError("debug_batch_fast_inverse: pivots and refactor_every are >= 0")
+    wo = np.concatenate([[0], np.cumsum([lp.m * lp.m for lp in lps])]).astype(np.int64)
+    w = np.full(int(wo[-1]) + 1, np.nan)
+
+    def invoke(c_lps, count, o, res):
+        return _ffi.lib().dzg_debug_batch_fast_inverse(c_lps, C.c_int64(count), C.byref(o), C.c_int64(int(pivots)),
+                                                       C.c_int64(int(refactor_every)), ptr(w), res)
+    out = _batch_fast(lps, log, log_cap, opts, "dzg_debug_batch_fast_inverse", invoke)
+    return [(r, w[int(wo[i]):int(wo[i + 1])].reshape(lp.m, lp.m).copy()) for i, (r, lp) in enumerate(zip(out, lps))]

@@ -269,10 +269,14 @@ __device__ __forceinline__ void price(const double *v, int m, int q, const doubl
     }
 }
 
-template <int BLOCK, int PL>
+// DUMP (the test hook's instantiations) adds an epilogue that copies LP id's final W to
+// w_out[w_off[id] + p * m + r]; nothing else depends on it or reads the two pointers.
+template <int BLOCK, int PL, bool DUMP>
 __global__ __launch_bounds__(BLOCK) void k_batch_fast(FArgs g, const int *__restrict__ list,
                                                       int *__restrict__ next_list,
-                                                      int *__restrict__ next_count)
+                                                      int *__restrict__ next_count,
+                                                      double *__restrict__ w_out,
+                                                      const long long *__restrict__ w_off)
 {
     extern __shared__ __attribute__((aligned(16))) double s_mem[];
     const int id = list[blockIdx.x];
@@ -459,17 +463,25 @@ __global__ __launch_bounds__(BLOCK) void k_batch_fast(FArgs g, const int *__rest
         gs->refactors = refactors;
         if (status == DZG_RUNNING) next_list[atomicAdd(next_count, 1)] = id;
     }
+    if (DUMP) { // every path out of the loop has passed a barrier since W was last written
+        double *out = w_out + w_off[id];
+        for (int e = threadIdx.x; e < m * m; e += BLOCK) {
+            const int p = e / m, r = e - p * m;
+            out[e] = W[p * ld + r];
+        }
+    }
 }
 
 namespace bh = dzg_bh;
 
+template <bool DUMP>
 void launch_bucket(int b, const FArgs &g, const int *list, int n, int *next_list, int *next_count,
-                   hipStream_t st)
+                   hipStream_t st, double *w_out = nullptr, const long long *w_off = nullptr)
 {
     const size_t lds = fast_lds_bytes(g.mmax);
     if (b == 3) { // more than 64 KiB of dynamic LDS: say so once (a runtime that needs no telling ignores it)
         static const hipError_t attr =
-            hipFuncSetAttribute(reinterpret_cast<const void *>(k_batch_fast<256, 64>),
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_batch_fast<256, 64, DUMP>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds_bytes(DZG_BATCH_MAX_ROWS));
         (void)attr;
     }
@@ -477,17 +489,17 @@ void launch_bucket(int b, const FArgs &g, const int *list, int n, int *next_list
         const dim3 block(bh::kBlock[b]);
         // the pricing lanes per column follow the bucket's rows: 16, 32, then the whole wave
         if (b == 0)
-            hipLaunchKernelGGL((k_batch_fast<64, 16>), dim3(grid), block, lds, st, g, list + c0, next_list,
-                               next_count);
+            hipLaunchKernelGGL((k_batch_fast<64, 16, DUMP>), dim3(grid), block, lds, st, g, list + c0, next_list,
+                               next_count, w_out, w_off);
         else if (b == 1)
-            hipLaunchKernelGGL((k_batch_fast<64, 32>), dim3(grid), block, lds, st, g, list + c0, next_list,
-                               next_count);
+            hipLaunchKernelGGL((k_batch_fast<64, 32, DUMP>), dim3(grid), block, lds, st, g, list + c0, next_list,
+                               next_count, w_out, w_off);
         else if (b == 2)
-            hipLaunchKernelGGL((k_batch_fast<128, 64>), dim3(grid), block, lds, st, g, list + c0, next_list,
-                               next_count);
+            hipLaunchKernelGGL((k_batch_fast<128, 64, DUMP>), dim3(grid), block, lds, st, g, list + c0, next_list,
+                               next_count, w_out, w_off);
         else
-            hipLaunchKernelGGL((k_batch_fast<256, 64>), dim3(grid), block, lds, st, g, list + c0, next_list,
-                               next_count);
+            hipLaunchKernelGGL((k_batch_fast<256, 64, DUMP>), dim3(grid), block, lds, st, g, list + c0, next_list,
+                               next_count, w_out, w_off);
     });
 }
 
@@ -535,24 +547,34 @@ void write_fast(const dzg_lp &lp, const DzgBatchLp &d, const FState &fs, const i
 
 // The FAST batch itself: `o.near_tie_action` and `o.tie_tol` as given.  The driver is batch_host.h's,
 // as in k_batch.hip; the state block and the margins are FAST's own sections.
+// With w_out (dzg_debug_batch_fast_inverse) the budget is `pivots_per_launch` pivots in one launch of
+// the DUMP instantiations: iter_stop is that budget and the launch has one step more, so that
+// fast_status ends it -- after W was built, also when the budget is 0 -- and W comes down with the state.
 static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o, int64_t pivots_per_launch,
-                            int64_t refactor_every_arg, dzg_result *res)
+                            int64_t refactor_every_arg, dzg_result *res, double *w_out = nullptr)
 {
-    const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
+    const bool dump = w_out != nullptr;
+    const long long max_iter = dump ? std::min<int64_t>(pivots_per_launch, 1 << 30)
+                                    : (o.max_iter > 0 ? o.max_iter : 10000000);
     if (const int rc = bh::use_device(o.device)) return rc;
 
     const int N = (int)count;
     const bh::Packed P = bh::pack(lps, res, N, max_iter);
     bh::Layout L(P);
     const size_t s_state = L.ar.add(sizeof(FState) * N);
+    const size_t s_woff = L.ar.add(dump ? sizeof(long long) * N : 0);
     L.end_upload();
     const size_t s_lmg = L.ar.add(sizeof(double) * P.nlog);
+    std::vector<long long> w_off((size_t)N + 1, 0);
+    for (int i = 0; i < N; ++i) w_off[(size_t)i + 1] = w_off[(size_t)i] + (long long)lps[i].m * lps[i].m;
+    const size_t s_w = L.ar.add(dump ? sizeof(double) * (size_t)w_off[(size_t)N] : 0);
     L.end_download();
 
     std::vector<unsigned char> host(L.download_end, 0);
     bh::fill_upload(host.data(), L, P, lps);
     FState *fs = (FState *)(host.data() + s_state);
     for (int i = 0; i < N; ++i) start_ctl(fs[i].ctl, o, max_iter);
+    if (dump) std::memcpy(host.data() + s_woff, w_off.data(), sizeof(long long) * N);
     bh::Device D;
     if (const int rc = bh::upload(D, L, host.data())) return rc;
     unsigned char *dev = D.arena;
@@ -562,7 +584,8 @@ static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o,
     g.state = (FState *)(dev + s_state);
     g.log_margin = (double *)(dev + s_lmg);
     g.eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
-    g.ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
+    g.ppl = dump ? (int)max_iter + 1
+          : (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
                                         : DZG_BATCH_FAST_DEFAULT_PPL);
     g.refactor_every = (int)(refactor_every_arg > 0 ? std::min<int64_t>(refactor_every_arg, 1 << 30)
                                                     : DZG_BATCH_FAST_DEFAULT_REFACTOR);
@@ -572,7 +595,11 @@ static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o,
         bh::live_of(P.bucket_n), D.st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
             FArgs gb = g;
             gb.mmax = P.mmax[b];
-            launch_bucket(b, gb, list, n, next_list, next_count, D.st);
+            if (dump)
+                launch_bucket<true>(b, gb, list, n, next_list, next_count, D.st, (double *)(dev + s_w),
+                                    (const long long *)(dev + s_woff));
+            else
+                launch_bucket<false>(b, gb, list, n, next_list, next_count, D.st);
         });
     if (rc_rounds) return rc_rounds;
     if (const int rc = bh::download(D, L, host.data())) return rc;
@@ -586,6 +613,7 @@ static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o,
         bh::unpack_common(lps[i], P.desc[(size_t)i], view, r);
         write_fast(lps[i], P.desc[(size_t)i], fs[i], view.basis, (const double *)(host.data() + s_lmg), r);
     }
+    if (dump) std::memcpy(w_out, host.data() + s_w, sizeof(double) * (size_t)w_off[(size_t)N]);
     return 0;
 }
 
@@ -625,4 +653,23 @@ extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_
     if (rc2 < 0) return rc2;
     for (size_t k = 0; k < redo.size(); ++k) res[redo[k]] = res2[k];
     return 0;
+}
+
+// Test hook (tests/test_gpu_batch_fast_inverse.py): the W = B^-1 a FAST batch launch keeps in LDS.
+// Every LP's W is built from its starting basis as a launch builds it at step 0, at most `pivots`
+// pivots run in that one launch (refactor_every as in dzg_batch_solve_fast), res[i] is filled as
+// dzg_batch_solve_fast fills it, and the final W goes to w_out: LP after LP, m x m row-major, row p
+// basis position p, column r constraint row r.  opts->max_iter is not consulted: `pivots` is the budget.
+extern "C" int dzg_debug_batch_fast_inverse(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots,
+                                            int64_t refactor_every, double *w_out, dzg_result *res)
+{
+    if (const int rc = bh::check_batch(lps, count, res, pivots, w_out ? nullptr : "w_out")) return rc;
+    if (refactor_every < 0) return dzg_set_error(DZG_E_ARG, "batch: refactor_every < 0");
+    dzg_opts o;
+    if (opts) o = *opts; else dzg_opts_default(&o);
+    if (!opts || o.numerics != DZG_NUMERICS_FAST)
+        return dzg_set_error(DZG_E_ARG, "dzg_debug_batch_fast_inverse: FAST numerics only");
+    if (const int rc = bh::check_batch(lps, count)) return rc;
+    if (count == 0) return 0;
+    return batch_solve_fast(lps, count, o, pivots, refactor_every, res, w_out);
 }

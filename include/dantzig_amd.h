@@ -850,6 +850,17 @@ int64_t dzg_debug_rl_listed(dzg_solver *s);
  * solver keeps (a row-sharded rank: its slice; rows outside it are DZG_E_ARG)}.  STRICT: DZG_E_ARG.
  * No solve path calls it. */
 int dzg_debug_basis_inverse(dzg_solver *s, int64_t row0, int64_t row1, double *out, int64_t info[4]);
+/* Test hook (tests/test_gpu_batch_fast_inverse.py): the inverse W = B^-1 a dzg_batch_solve_fast launch
+ * keeps in LDS and loses when it ends.  For every LP, W is built from the LP's starting basis exactly
+ * as a launch builds it at its first step; at most `pivots` (>= 0) pivots run in that one launch, the
+ * production kernel body with an epilogue that copies W out; refactor_every as in
+ * dzg_batch_solve_fast (0 = 64; above `pivots`: no rebuild inside the launch).  res[i] is filled as
+ * dzg_batch_solve_fast fills it (DZG_ITER_LIMIT if the budget ended the LP; opts->max_iter is not
+ * consulted), and the final W goes to w_out: LP after LP, dense row-major m x m, row p basis
+ * position p, column r constraint row r (sum of m^2 doubles).  opts->numerics must be FAST; the host
+ * checks of dzg_batch_solve_fast run first.  No solve path calls it. */
+int dzg_debug_batch_fast_inverse(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots,
+                                 int64_t refactor_every, double *w_out, dzg_result *res);
 
 /* Test hook (tests/test_gpu_cand_reduce.py): runs the straight-line argmax reduction of the small-k
  * three-launch iteration (csrc/common.h, dzg_wave_best2_flat) on `ncases` independent cases and

@@ -23,9 +23,15 @@ U53 = 2.0 ** -53
 # controls hold the loosest, C_MAX: a 1e-9 relative error in one entry of a 90-row inverse reads
 # ~1.3e4 there (tests/test_inverse_check.py).
 C_INVERSE_OBSERVED = {"1 refactorisation": 20.05, "2 eta file": 10.58, "3 sparse basis": 2.887,
-                      "4 row-sharded": 2.118, "5 headline": 0.554}
+                      "4 row-sharded": 2.118, "5 headline": 0.554,
+                      "6 batch inverse": 1.623, "7 batch updates": 5.782}
 C_INVERSE = {"1 refactorisation": 200.0, "2 eta file": 100.0, "3 sparse basis": 30.0,
-             "4 row-sharded": 20.0, "5 headline": 6.0}
+             "4 row-sharded": 20.0, "5 headline": 6.0, "6 batch inverse": 16.3, "7 batch updates": 58.0}
+# Families 6 and 7 (the batched FAST solver's inverse in LDS, tests/test_gpu_batch_fast_inverse.py)
+# take their c from a reference instead: 10x the worst ratio of the float64 transcription of the
+# documented algorithm (tests/batch_fast_reference.py) on the same inputs, all rows, rounded up;
+# tests/test_batch_fast_inverse_host.py measures it again on every run and holds c to it.
+C_REFERENCE_OBSERVED = {"6 batch inverse": 1.623, "7 batch updates": 5.782}
 C_MAX = max(C_INVERSE.values())
 ROWS_SAMPLED = 16   # rows checked where m >= 4096 (and where all rows would cost too much)
 CHUNK = 512         # structural columns per long-double product

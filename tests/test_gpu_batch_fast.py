@@ -87,18 +87,29 @@ def test_unbounded_infeasible_and_empty_lps_end_as_the_oracle_says():
 
 
 def test_refactorisation_inside_and_between_launches(edges):
-    idx = [edges.at(128, 256), edges.at(65, 100)]
-    lps = [edges.lps[i] for i in idx]
-    often = core.solve_batch_fast(lps, numerics=core.FAST, refactor_every=8, pivots_per_launch=5)
-    inside = core.solve_batch_fast(lps, numerics=core.FAST, refactor_every=8, pivots_per_launch=40)
-    for i, a, b in zip(idx, often, inside):
-        w, d = edges.want[i], edges.got[i]
-        for name, g in (("every launch", a), ("inside a launch", b), ("defaults", d)):
-            print(f"{edges.key[i]} {name}: {g.iterations} pivots, {g.refactors} refactors, near_ties {g.near_ties}")
-            assert g.status == w.status == "optimal" and log3(g.pivots) == log3(w.pivots), (edges.key[i], name)
-        assert a.refactors >= a.iterations // 8
-        assert b.refactors >= b.iterations // 8
-        assert d.refactors < a.refactors
+    """One shape per bucket.  The 15-, 17- and 33-row LPs end in 21-108 pivots, fewer than the default
+    refactor_every: only refactor_every = 3 puts the one-wave elimination and the row updates at 16
+    and 32 lanes a row on their path.  One of those may be left out, by name, if it was flagged."""
+    skipped = []
+    for shapes, every, short in ((((128, 256), (65, 100)), 8, 5), (((15, 40), (17, 20), (33, 64)), 3, 2)):
+        idx = [edges.at(*sh) for sh in shapes]
+        lps = [edges.lps[i] for i in idx]
+        often = core.solve_batch_fast(lps, numerics=core.FAST, refactor_every=every, pivots_per_launch=short)
+        inside = core.solve_batch_fast(lps, numerics=core.FAST, refactor_every=every, pivots_per_launch=40)
+        for i, a, b in zip(idx, often, inside):
+            w, d = edges.want[i], edges.got[i]
+            runs = (("every launch", a), ("inside a launch", b), ("defaults", d))
+            for name, g in runs:
+                print(f"{edges.key[i]} {name}: {g.iterations} pivots, {g.refactors} refactors, near_ties {g.near_ties}")
+            if every == 3 and any(g.near_ties > 0 for _, g in runs):
+                skipped.append(edges.key[i])
+                continue
+            for name, g in runs:
+                assert g.status == w.status == "optimal" and log3(g.pivots) == log3(w.pivots), (edges.key[i], name)
+            assert a.refactors >= a.iterations // every
+            assert b.refactors >= b.iterations // every
+            assert d.refactors < a.refactors
+    assert len(skipped) <= 1, f"flagged and left out: {skipped}"
 
 
 def test_carried_state_stays_within_the_short_solve_bound(edges):
@@ -163,7 +174,7 @@ def test_an_lp_does_not_notice_its_place_in_the_batch():
 
 
 def test_limit_and_resume_from_a_structural_basis(edges):
-    for m, ns in ((128, 256), (33, 64)):
+    for m, ns in ((128, 256), (33, 64), (15, 40), (17, 20)):
         i = edges.at(m, ns)
         lp, w = edges.lps[i], edges.want[i]
         half = w.iterations // 2

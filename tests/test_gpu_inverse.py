@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import inverse_check as ic
+from tests.batch_fast_reference import scattered_lp
 
 pytestmark = pytest.mark.gpu
 
@@ -58,26 +59,6 @@ def check(s, a, ns, family, recent_count=4, every_below=400, seed=0, extra=()):
 
 
 # ------------------------------------------------------------------ 1. refactorisation, scattered bases
-def scattered_lp(core, m, k, seed):
-    """A basis of k structural columns (a random subset) at random positions; the slacks of m - k
-    random rows fill the other positions, in random order."""
-    ns = 2 * m
-    a, _, c = core.gen_dense_lp(seed=seed, m=m, n_struct=ns)
-    rng = np.random.default_rng(seed)
-    cols = rng.choice(ns, k, replace=False)
-    pos = rng.choice(m, k, replace=False)
-    slack_rows = rng.choice(m, m - k, replace=False)
-    basis = np.empty(m, dtype=np.int64)
-    basis[pos] = cols
-    basis[np.setdiff1d(np.arange(m), pos)] = ns + slack_rows
-    nonbasis = np.setdiff1d(np.arange(ns + m), basis).astype(np.int64)
-    rng.shuffle(nonbasis)
-    a = np.asarray(a)
-    lp = core.CoreLP(a=a, c=np.concatenate([c, np.zeros(m)]), basis=basis, nonbasis=nonbasis,
-                     x=np.ones(m), z=-np.ones(ns))
-    return lp, a, ns
-
-
 def _ks(m):
     return sorted({k for k in (1, 7, 63, 64, 65, 127, 128, 129, 191, 192, 193, 256, 257, 449, m - 1, m)
                    if 1 <= k <= m})
