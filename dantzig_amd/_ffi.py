@@ -47,6 +47,7 @@ EXPORTS = [
     "dzg_solver_ray", "dzg_batch_solve_rays", "dzg_model_solve_rays", "dzg_model_solve_batch_rays",
     "dzg_model_map_ray",
     "dzg_batch_solve_fast", "dzg_model_solve_batch_fast", "dzg_debug_batch_fast_inverse",
+    "dzg_solver_reoptimize",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -149,6 +150,11 @@ class Ray(C.Structure):
 class ModelRay(C.Structure):
     _fields_ = [("var", C.c_void_p), ("con", C.c_void_p), ("lb", C.c_void_p), ("ub", C.c_void_p),
                 ("core", Ray)]
+
+
+class Reopt(C.Structure):
+    _fields_ = [("rhs", C.c_void_p), ("c", C.c_void_p), ("constant", C.c_double),
+                ("set_constant", C.c_int32), ("reserved", C.c_int32)]
 
 
 class ModelRangingReq(C.Structure):
@@ -284,6 +290,7 @@ def lib() -> C.CDLL:
                                                     C.c_void_p, C.c_void_p]
         _lib.dzg_model_map_ray.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                            C.c_int64, C.c_void_p]
+        _lib.dzg_solver_reoptimize.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_mip_opts_default.restype = None
         _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -374,6 +381,15 @@ def check_ranging(rc: int, what: str) -> int:
     if rc < 0:
         msg = lib().dzg_last_error().decode()
         if "ranging is not supported" in msg:
+            raise NotImplementedError(f"{what}: {msg}")
+    return check(rc, what)
+
+
+def check_reopt(rc: int, what: str) -> int:
+    """check(), but a route without re-optimisation (the C call says so) is a NotImplementedError."""
+    if rc < 0:
+        msg = lib().dzg_last_error().decode()
+        if "reoptimize is not supported" in msg:
             raise NotImplementedError(f"{what}: {msg}")
     return check(rc, what)
 

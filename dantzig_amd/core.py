@@ -384,6 +384,28 @@ class Solver:
         _ffi.check_ray(_ffi.lib().dzg_solver_ray(self._h, C.byref(u)), "dzg_solver_ray")
         return _core_ray(u, d[:n].copy(), y[:m].copy())
 
+    def reoptimize(self, b=None, c=None, constant=None) -> None:
+        """dzg_solver_reoptimize: replaces the right-hand side `b` (m entries, by row), the objective
+        `c` (n entries, by variable, core sense) and / or the constant of the LP this solver holds,
+        and recomputes the state of its CURRENT basis for them on the GPU (x = B^-1 b, z the reduced
+        costs, xbar = zbar = 1); run() then carries on from that basis, and the pivot count and log
+        keep accumulating.  Allowed before a run and after any end but singular / panic.  A FAST
+        solver refactorises the basis for it (create it with refactor_interval != 0) and no longer
+        measures state_drift afterwards; CSC and sharded solvers: NotImplementedError.  ValueError
+        for a wrong length or when nothing is given."""
+        m, n = self._lp.m, self._lp.n
+        if b is None and c is None and constant is None:
+            raise ValueError("reoptimize: give b, c or constant")
+        b = None if b is None else f64(b)
+        c = None if c is None else f64(c)
+        if b is not None and b.shape != (m,):
+            raise ValueError(f"reoptimize: b has shape {b.shape}, the LP has {m} rows")
+        if c is not None and c.shape != (n,):
+            raise ValueError(f"reoptimize: c has shape {c.shape}, the LP has {n} variables")
+        chg = _ffi.Reopt(ptr(b), ptr(c), 0.0 if constant is None else float(constant),
+                         0 if constant is None else 1, 0)
+        _ffi.check_reopt(_ffi.lib().dzg_solver_reoptimize(self._h, C.byref(chg)), "dzg_solver_reoptimize")
+
     def debug_inverse(self, row0: int, row1: int) -> tuple[np.ndarray, dict]:
         """Test hook (dzg_debug_basis_inverse): rows [row0, row1) of the basis inverse FAST keeps --
         row i is basis position row0 + i, column r constraint row r -- and

@@ -852,6 +852,12 @@ void dzg_launch_drift(const DzgDev &d, const double *b0, const double *xb0, cons
 int dzg_drift_blocks(void);
 int dzg_drift_chunks(void);
 
+// k_restart.hip: the state of the current basis for new data, written (dzg_solver_reoptimize).  FAST,
+// right after a refactorisation: x = B^-1 rhs and xbar = 1 (ag: [m + 2] scratch); z = -dzy - c_N and
+// zbar = 1 (STRICT uses the second one too, on the dzy of its own route)
+void dzg_launch_restart_x(const DzgDev &d, const double *rhs, double *ag, int k_bound, hipStream_t st);
+void dzg_launch_restart_z(const DzgDev &d, const double *cdev, const double *dzy, hipStream_t st);
+
 // k_sparse.hip
 void dzg_launch_sp_init(const DzgDev &d, int first, hipStream_t st);
 void dzg_launch_sp_ftran(const DzgDev &d, int need_kind, int nrz, hipStream_t st);

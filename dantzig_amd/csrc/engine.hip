@@ -136,6 +136,8 @@ struct dzg_solver {
     DzgCtl *du_ctl = nullptr; // STRICT: a control block that reads DZG_RUNNING for the LU kernels
     // dzg_solver_ray (k_rays.hip): dx or dz, d by variable, the finish kernel's partial records
     double *ry_vec = nullptr, *ry_d = nullptr, *ry_part = nullptr, *ry_h = nullptr, *ry_res = nullptr;
+    // dzg_solver_reoptimize (k_restart.hip), FAST: the new right-hand side in compact numbering
+    double *ro_ag = nullptr;
     // FAST, dense, one GPU: the three-launch chain (k_chain.hip)
     unsigned long long *chain_bar = nullptr; // barrier counters (cleared only by chain_recover)
     unsigned long long *chain_dbg = nullptr; // DZG_CHAIN_DEBUG=1: phase clocks of workgroup 0
@@ -2778,6 +2780,116 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
         if (primal) std::memset(out->y, 0, sizeof(double) * m);
         else std::memcpy(out->y, vec.data(), sizeof(double) * m);
     }
+    return 0;
+}
+
+// ---- re-optimisation from the current basis after b or c change (k_restart.hip) ----
+static int reopt_finite(const char *name, const double *v, int64_t count)
+{
+    for (int64_t i = 0; v && i < count; ++i)
+        if (!std::isfinite(v[i]))
+            return fail(DZG_E_ARG, std::string("reoptimize: ") + name + "[" + std::to_string(i) + "] is not finite");
+    return 0;
+}
+
+extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
+{
+    if (!s || !chg) return fail(DZG_E_ARG, "reoptimize: NULL argument");
+    if (!chg->rhs && !chg->c && !chg->set_constant)
+        return fail(DZG_E_ARG, "reoptimize: nothing to change (rhs and c are NULL, set_constant is 0)");
+    DzgDev &d = s->d;
+    const int m = d.m, q = d.q, n = d.n;
+    TRY(reopt_finite("rhs", chg->rhs, m));
+    TRY(reopt_finite("c", chg->c, n));
+    if (chg->set_constant && !std::isfinite(chg->constant))
+        return fail(DZG_E_ARG, "reoptimize: constant is not finite");
+    if (d.csc || d.world > 1)
+        return fail(DZG_E_ARG, "reoptimize is not supported on CSC storage or sharded solvers");
+    const bool fast = s->numerics == DZG_NUMERICS_FAST;
+    if (fast && !s->rf_piv)
+        return fail(DZG_E_ARG, "reoptimize: a FAST solver needs its refactorisation workspace: create it "
+                               "with opts.refactor_interval != 0");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    DzgCtl *h = s->h_ctl;
+    const int status = h->status;
+    if (status == DZG_SINGULAR || status == DZG_PANIC || status < 0 || status > DZG_NEAR_TIE)
+        return fail(DZG_E_ARG, std::string("reoptimize: the solver's status is ") + dzg_status_str(status) +
+                                   ": its basis cannot be carried on from");
+    hipStream_t st = s->st;
+    TRY(duals_workspace(s));
+    if (fast && !s->ro_ag) TRY(dev_alloc(s, &s->ro_ag, (size_t)m + 2));
+    if (fast) {
+        // a fresh inverse of the current basis first (the eta file emptied): if it cannot be had, nothing
+        // has changed.  The drift measurement is about a solve from the slack basis with the old data:
+        // off from here on (put back if the call fails)
+        double *const drift_ref = s->dr_b0;
+        s->dr_b0 = nullptr;
+        const int rrc = refactor_now(s, true);
+        if (rrc != 0) {
+            s->dr_b0 = drift_ref;
+            return rrc;
+        }
+        TRY(read_ctl(s));
+        if (h->status != status) { // k_ref_done met a singular block: the solve's outcome stays
+            HIP_OK(hipMemcpy(&d.ctl->status, &status, sizeof(int), hipMemcpyHostToDevice));
+            h->status = status;
+            s->dr_b0 = drift_ref;
+            return fail(DZG_E_DEVICE, "reoptimize: the current basis did not refactorise (singular block)");
+        }
+    }
+    // the new data, on the host and in the device copies every post-solve call reads
+    if (chg->c) s->c_host.assign(chg->c, chg->c + n);
+    if (chg->rhs) s->x0_host.assign(chg->rhs, chg->rhs + m);
+    if (chg->set_constant) s->constant = chg->constant;
+    if (n) HIP_OK(hipMemcpyAsync(s->du_c, s->c_host.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
+    if (m) HIP_OK(hipMemcpyAsync(s->du_rhs0, s->x0_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+    if (fast) {
+        const int k = (int)h->ncompact;
+        dzg_launch_restart_x(d, s->du_rhs0, s->ro_ag, k, st);
+        // y by the two-stage scheme of the drift measurement, dzy = -N^T y by one column-wise pricing pass
+        dzg_launch_drift_y(d, s->du_c, s->du_part, s->du_y, k, st);
+        if (q) dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->du_dzy, st);
+    } else {
+        // the LU of every STRICT FTRAN / BTRAN on a copy of the device view whose control block reads
+        // DZG_RUNNING: B x = rhs in place in x, B^T y = c_B as dzg_solver_duals solves it, then
+        // neg_t_dot in the reference's order
+        std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1)), codes((size_t)(q ? q : 1));
+        std::vector<double> cb((size_t)(m ? m : 1)), ones((size_t)(m ? m : 1), 1.0);
+        if (m) HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
+        if (q) HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
+        for (int p = 0; p < m; ++p) cb[(size_t)p] = s->c_host[(size_t)basis[(size_t)p]];
+        for (int k = 0; k < q; ++k) codes[(size_t)k] = s->var_col_host[(size_t)nonbasis[(size_t)k]];
+        if (m) {
+            HIP_OK(hipMemcpyAsync(d.x, s->x0_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(d.xbar, ones.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+            HIP_OK(hipMemcpyAsync(s->du_y, cb.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
+        }
+        if (q) HIP_OK(hipMemcpyAsync(s->du_codes, codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, st));
+        HIP_OK(hipStreamSynchronize(st)); // (cb, ones and codes are locals)
+        DzgDev dd = d;
+        dd.ctl = s->du_ctl;
+        dd.dx = d.x;
+        dd.v = s->du_y;
+        if (m) {
+            dzg_launch_strict_solve(dd, 0, st);
+            dzg_launch_strict_solve(dd, 1, st);
+        }
+        if (q) dzg_launch_price_raw(DZG_PRICE_SEQ, m, d.lda, d.A, s->du_codes, q, s->du_y, s->du_dzy, st);
+    }
+    dzg_launch_restart_z(d, s->du_c, s->du_dzy, st);
+    // the control block: no pivot is in flight, the run goes on; everything that counts stays
+    h->status = DZG_RUNNING;
+    h->enter_pos = h->leave_pos = -1;
+    h->tie_skip_iter = -1;
+    h->drift_tau = 0.0;
+    h->tau = h->tie_tol;
+    HIP_OK(hipMemcpyAsync(d.ctl, h, sizeof(DzgCtl), hipMemcpyHostToDevice, st));
+    d.k_hint = d.k_lo_hint = 0;
+    s->state_drift = 0.0;
+    if (fast) dzg_launch_fast_update(d, 1, st); // first-pivot partials of the new state
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
     return 0;
 }
 

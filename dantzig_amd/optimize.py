@@ -13,8 +13,9 @@ import abc
 from dataclasses import dataclass
 from typing import Union
 
+from . import _ffi, core
 from . import rust as rs
-from .exceptions import SolveError
+from .exceptions import InfeasibleError, SolveError, UnboundedError
 from .model import AffExpr, Constraint, LinExpr, Variable
 
 _SENSES = ("minimize", "maximize")
@@ -314,6 +315,129 @@ class Optimize(abc.ABC):
             return Solution(solution=rs.solve(objective, constraints, duals=True), sense=self.sense,
                             constraints=list(self.constraints))
         return Solution(solution=rs.solve(objective, constraints), sense=self.sense)
+
+    def session(self, **core_opts) -> "Session":
+        """A Session on this model: its solve() keeps the model on the GPU, and later
+        solve(objective=..., rhs=...) calls re-optimise from the last basis instead of starting over.
+        core_opts: fields of dzg_opts (numerics, max_iter, ...) over rust.set_options()'s.  ValueError
+        for a model with an integer variable."""
+        return Session(self, **core_opts)
+
+
+class Session:
+    """A model kept on the GPU between solves (Optimize.session): the first solve() lowers the model,
+    uploads it and solves it from the slack basis; every later solve(objective=..., rhs=...) changes
+    the objective and / or right-hand sides and re-optimises from the basis the last solve ended on
+    (core.Solver.reoptimize), without a new upload.  Changes accumulate.  Only b and the objective may
+    change: variable bounds, matrix coefficients and integer variables are out of scope.
+
+    Numerics is the handle's: AUTO runs STRICT up to auto_strict_rows rows, else FAST with near
+    ties counted.  A re-optimised path is not the reference's path from the slack basis, so the
+    promise is the optimum (or the verdict), not the pivots, and at a degenerate optimum possibly
+    another vertex.  `pivots` lists the pivots of each solve."""
+
+    def __init__(self, problem: "Optimize", **core_opts) -> None:
+        self._problem = problem
+        self._constraints = list(problem.constraints)
+        self._objective = problem.objective
+        self._rhs: dict = {}   # id(constraint) -> the new b of its normal form
+        self._opts = {**rs._options, **core_opts}
+        self._opts.setdefault("refactor_interval", -1)  # (FAST: reserves what reoptimize needs)
+        self._solver = None
+        self._form = None
+        self._order = None
+        self._iterations = 0
+        self.pivots: list = []
+        self._check_lp(self._lowered()[0])
+
+    @staticmethod
+    def _check_lp(problem) -> None:
+        if rs._has_integer(*problem):
+            raise ValueError("session: re-optimisation is not defined for a model with integer variables")
+
+    def _inequalities(self) -> list:
+        """The model's rows with the right-hand sides of the session: row k of a changed constraint is
+        its linear part as lowered with b = Constraint._signs[k] * (the new b of the normal form)."""
+        rows = []
+        for constraint in self._constraints:
+            b = self._rhs.get(id(constraint))
+            for ineq, sign in zip(constraint.rust_inequalities(), constraint._signs):
+                rows.append(ineq if b is None else rs.PyInequality(linexpr=ineq._linexpr, b=sign * b))
+        return rows
+
+    def _lowered(self):
+        objective = -self._objective if self._problem.sense == "minimize" else self._objective
+        problem = (objective.to_rust_affexpr(), self._inequalities())
+        arrays, order = rs.lower(*problem)
+        return problem, arrays, order
+
+    def _change(self, objective, rhs) -> None:
+        if objective is not None:
+            self._objective = objective.to_affexpr()
+        known = {id(c) for c in self._constraints}
+        for constraint, b in (rhs or {}).items():
+            if id(constraint) not in known:
+                raise KeyError("the constraint is not part of the session's model")
+            if not isinstance(b, (int, float)):
+                raise TypeError("rhs maps a constraint to the number its normal form compares with")
+            # as a comparison forms it, b = -(constant of lhs - rhs): a written 0 arrives as -0.0
+            self._rhs[id(constraint)] = -(0.0 - float(b))
+
+    def solve(self, *, objective=None, rhs=None) -> Solution:
+        """Solve the model with `objective` (a new expression in the problem's sense) and `rhs`
+        ({constraint: new b}, b of the constraint's normal form linexpr <=, >= or == b: the number
+        Solution.rhs_range speaks about) replacing what the session holds.  Raises
+        exceptions.UnboundedError / InfeasibleError like Optimize.solve; the session stays usable.
+        ValueError if the change alters more of the standard form than b, c and the constant (an
+        objective over a variable the model had not seen)."""
+        before = (self._objective, dict(self._rhs))
+        self._change(objective, rhs)
+        try:
+            problem, arrays, order = self._lowered()
+            self._check_lp(problem)
+            form = rs.standard_form(arrays)
+            if self._solver is not None and not (form.same_shape_as(self._form)
+                                                 and [v.id for v in order] == [v.id for v in self._order]):
+                raise ValueError("session: the new objective or right-hand side changes the standard form "
+                                 "(only b and the objective's coefficients may change)")
+        except Exception:
+            self._objective, self._rhs = before
+            raise
+        if self._solver is None:
+            lp = core.CoreLP(a=form.a, c=form.c, basis=form.basis, nonbasis=form.nonbasis, x=form.x,
+                             z=form.z, var_col=form.var_col, constant=form.constant)
+            self._solver = core.Solver(lp, **self._opts)
+        else:
+            self._solver.reoptimize(b=form.x, c=form.c, constant=form.constant)
+        self._form, self._order = form, order
+        self._solver.run(0)
+        res = self._solver.result(log=False)
+        self.pivots.append(res.iterations - self._iterations)
+        self._iterations = res.iterations
+        if res.status_code == _ffi.UNBOUNDED:
+            raise UnboundedError("The objective is unbounded")
+        if res.status_code == _ffi.INFEASIBLE:
+            raise InfeasibleError("The model is infeasible")
+        if res.status_code != _ffi.OPTIMAL:
+            raise RuntimeError(f"simplex terminated with status {res.status!r} after {res.iterations} iterations")
+        by_var = dict(zip(res.basis.tolist(), res.x.tolist()))
+        values = {}
+        for i, v in enumerate(order):  # x+ - x- (src/simplex.rs:354-371)
+            values[v.id] = by_var.get(int(form.pos_var[i]), 0.0) - by_var.get(int(form.neg_var[i]), 0.0)
+        return Solution(solution=rs.PySolution(res.objective, values, self.pivots[-1], res.numerics,
+                                               (form.m, form.n)), sense=self._problem.sense)
+
+    def close(self) -> None:
+        if self._solver is not None:
+            self._solver.close()
+            self._solver = None
+            self._iterations = 0  # (a later solve() starts a new solver from the slack basis)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
 
 
 class Minimize(Optimize):

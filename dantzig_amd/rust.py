@@ -282,6 +282,44 @@ def _c_model(a: dict) -> _ffi.Model:
                       a["ncons"], p(a["con_ptr"]), p(a["con_var"]), p(a["con_coef"]), p(a["con_b"]))
 
 
+class StandardForm:
+    """dzg_build_standard_form of lower()'s arrays (Simplex::new, src/simplex.rs:123-224) as numpy
+    arrays: a is (m, n_struct); pos_var / neg_var the variable of x+ / x- per user variable (-1: unseen)."""
+    __slots__ = ("m", "n", "n_struct", "a", "var_col", "c", "constant", "basis", "nonbasis", "x", "z",
+                 "pos_var", "neg_var")
+
+    def same_shape_as(self, other: "StandardForm") -> bool:
+        """Everything but b, c and the constant agrees: what a live solver can be re-optimised over."""
+        return ((self.m, self.n, self.n_struct) == (other.m, other.n, other.n_struct)
+                and np.array_equal(self.a, other.a) and np.array_equal(self.var_col, other.var_col)
+                and np.array_equal(self.pos_var, other.pos_var) and np.array_equal(self.neg_var, other.neg_var))
+
+
+def standard_form(arrays: dict) -> StandardForm:
+    """The standard form of a lowered model, built on the host by the library (two-call protocol)."""
+    md = _c_model(arrays)
+    sf = _ffi.StdForm()
+    _ffi.check(_ffi.lib().dzg_build_standard_form(C.byref(md), C.byref(sf)), "dzg_build_standard_form")
+    m, n, nst, nv = int(sf.m), int(sf.n), int(sf.n_struct), int(arrays["nvars"])
+    a = np.zeros((max(nst, 1), max(int(sf.lda), 1)))
+    var_col, c = np.zeros(max(n, 1), np.int64), np.zeros(max(n, 1))
+    basis, nonbasis = np.zeros(max(m, 1), np.int64), np.zeros(max(n - m, 1), np.int64)
+    x, z = np.zeros(max(m, 1)), np.zeros(max(n - m, 1))
+    pos, neg = np.zeros(nv + 1, np.int64), np.zeros(nv + 1, np.int64)
+    p = _ffi.ptr
+    sf.a, sf.var_col, sf.c, sf.basis, sf.nonbasis = p(a), p(var_col), p(c), p(basis), p(nonbasis)
+    sf.x, sf.z, sf.pos_var, sf.neg_var = p(x), p(z), p(pos), p(neg)
+    _ffi.check(_ffi.lib().dzg_build_standard_form(C.byref(md), C.byref(sf)), "dzg_build_standard_form")
+    out = StandardForm()
+    out.m, out.n, out.n_struct, out.constant = m, n, nst, float(sf.constant)
+    out.a = np.ascontiguousarray(a[:nst, :m].T)
+    out.var_col, out.c = var_col[:n].copy(), c[:n].copy()
+    out.basis, out.nonbasis = basis[:m].copy(), nonbasis[:n - m].copy()
+    out.x, out.z = x[:m].copy(), z[:n - m].copy()
+    out.pos_var, out.neg_var = pos[:nv].copy(), neg[:nv].copy()
+    return out
+
+
 class _DualBuffers:
     """The caller-owned arrays of one dzg_model_duals and the struct that points at them."""
 

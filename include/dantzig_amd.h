@@ -617,6 +617,52 @@ int dzg_model_solve_batch_rays(const dzg_model *models, int64_t count, const dzg
 int dzg_model_map_ray(const dzg_model *model, int32_t kind, const double *d, const double *y, int64_t m,
                       int64_t n, dzg_model_ray *out);
 
+/* ---- Re-optimisation from the current basis after b or c change (csrc/k_restart.hip) -------- */
+
+/* New data for the LP a live handle holds.  The matrix, var_col and the sizes stay. */
+typedef struct {
+    const double *rhs;     /* m, by constraint row; NULL = keep the current one      */
+    const double *c;       /* n, by variable (core sense: maximised); NULL = keep    */
+    double constant;       /* used when set_constant != 0                            */
+    int32_t set_constant, reserved;
+} dzg_reopt;
+
+/* Changes rhs and / or c (and the constant) of the LP and recomputes the state of the CURRENT basis
+ * B (nonbasic set N) for the new data; dzg_solver_run then carries on from that basis with the
+ * parametric self-dual method, which starts from any basis once xbar = zbar = 1.
+ *   Allowed: the solver's status is DZG_RUNNING (not run yet), DZG_OPTIMAL, DZG_UNBOUNDED,
+ *   DZG_INFEASIBLE, DZG_ITER_LIMIT or DZG_NEAR_TIE -- in all of these the basis on the device is
+ *   valid; a pivot that was pending at DZG_NEAR_TIE is dropped.  DZG_SINGULAR and DZG_PANIC: DZG_E_ARG.
+ *   NULL `s` or `chg`, or both arrays NULL with set_constant == 0: DZG_E_ARG; a NaN or infinite entry:
+ *   DZG_E_ARG, dzg_last_error names the index.  These checks run on the host before any device work.
+ *   CSC storage, column- and row-sharded solvers: DZG_E_ARG, "reoptimize is not supported ...".
+ *   A FAST solver needs its refactorisation workspace (opts.refactor_interval != 0 at creation), like
+ *   dzg_solver_duals, else DZG_E_ARG.
+ * The refactorisation of B comes first.  If B does not refactorise (a singular block) the status is
+ * put back, nothing else has been touched and the call returns DZG_E_DEVICE: the call changes
+ * everything or nothing.  Then
+ *   the new data is stored on the host and the device (c, the constant, rhs0 of the dual objective
+ *   and of Farkas rays: a later dzg_solver_duals, _ranging, _ray or dzg_solver_result speaks about
+ *   the new LP);
+ *   x = B^-1 rhs;   z_k = a_{N_k} . y - c[N_k] with y = B^-T c_B -- exactly the d of dzg_duals on the
+ *   nonbasic positions;   xbar = zbar = 1.0;   status = DZG_RUNNING;
+ *   every word of the control block that describes a pivot in flight (entering and leaving
+ *   positions, the acknowledged near tie, the host's bounds on k) returns to what dzg_solver_create
+ *   writes.
+ * The pivot count, the pivot log, the margins, near_ties, first_near_tie, min_margin, refactors and
+ * solve_ms keep accumulating; opts.max_iter bounds the total.
+ * STRICT: x is the reference's LU::solve of B x = rhs, z comes from dzg_solver_duals' STRICT route
+ * (LU::solve of B^T y = c_B, then neg_t_dot in the reference's order): bit for bit what the CPU
+ * restatement gives.  FAST: both come from the fresh inverse, deterministic (no atomics): two calls
+ * with the same data on the same state leave the same bits.
+ * The drift measurement (state_drift, csrc/k_drift.hip) compares the carried state with a solve that
+ * started on the slack basis with the OLD data; after this call it is switched off, as it is for
+ * warm-started and resumed handles: state_drift reads 0, its share of the near-tie tolerance is 0 and
+ * the tolerance returns to tie_tol.
+ * The re-optimised path is not the reference's path from the slack basis: the promise is the
+ * optimum (or the verdict), not the pivots. */
+int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
