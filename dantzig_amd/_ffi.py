@@ -48,6 +48,8 @@ EXPORTS = [
     "dzg_model_map_ray",
     "dzg_batch_solve_fast", "dzg_model_solve_batch_fast", "dzg_debug_batch_fast_inverse",
     "dzg_solver_reoptimize",
+    "dzg_solver_extend", "dzg_solver_dims", "dzg_debug_matrix", "dzg_debug_matrix_rows",
+    "dzg_debug_extend_ms",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -155,6 +157,11 @@ class ModelRay(C.Structure):
 class Reopt(C.Structure):
     _fields_ = [("rhs", C.c_void_p), ("c", C.c_void_p), ("constant", C.c_double),
                 ("set_constant", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Extend(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rows", C.c_void_p), ("ld_rows", C.c_int64),
+                ("rhs", C.c_void_p), ("cols", C.c_void_p), ("ld_cols", C.c_int64), ("c_cols", C.c_void_p)]
 
 
 class ModelRangingReq(C.Structure):
@@ -291,6 +298,12 @@ def lib() -> C.CDLL:
         _lib.dzg_model_map_ray.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int64,
                                            C.c_int64, C.c_void_p]
         _lib.dzg_solver_reoptimize.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dzg_solver_extend.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dzg_solver_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_debug_matrix.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+        _lib.dzg_debug_matrix_rows.restype = C.c_int64
+        _lib.dzg_debug_matrix_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
+        _lib.dzg_debug_extend_ms.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_mip_opts_default.restype = None
         _lib.dzg_mip_opts_default.argtypes = [C.c_void_p]
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
@@ -390,6 +403,15 @@ def check_reopt(rc: int, what: str) -> int:
     if rc < 0:
         msg = lib().dzg_last_error().decode()
         if "reoptimize is not supported" in msg:
+            raise NotImplementedError(f"{what}: {msg}")
+    return check(rc, what)
+
+
+def check_extend(rc: int, what: str) -> int:
+    """check(), but a route that cannot grow its LP (the C call says so) is a NotImplementedError."""
+    if rc < 0:
+        msg = lib().dzg_last_error().decode()
+        if "extend is not supported" in msg:
             raise NotImplementedError(f"{what}: {msg}")
     return check(rc, what)
 

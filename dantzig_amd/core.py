@@ -123,6 +123,62 @@ def resumed_from(lp: CoreLP, r) -> CoreLP:
                                xbar=f64(get("xbar")).copy(), zbar=f64(get("zbar")).copy())
 
 
+def _extend_blocks(m: int, ns: int, rows, rhs, cols, c_cols):
+    """The four arrays of an extension as float64 (p, ns), (p,), (m + p, r), (r,); ValueError for a
+    wrong shape, a half-given pair or when nothing is given."""
+    if (rows is None) != (rhs is None):
+        raise ValueError("extend: rows and rhs go together")
+    if (cols is None) != (c_cols is None):
+        raise ValueError("extend: cols and c_cols go together")
+    rhs = np.zeros(0) if rhs is None else np.atleast_1d(f64(rhs))
+    c_cols = np.zeros(0) if c_cols is None else np.atleast_1d(f64(c_cols))
+    if rhs.ndim != 1 or c_cols.ndim != 1:
+        raise ValueError("extend: rhs and c_cols are vectors")
+    p, r = len(rhs), len(c_cols)
+    if p == 0 and r == 0:
+        raise ValueError("extend: give rows and rhs, or cols and c_cols")
+    rows = np.zeros((0, ns)) if rows is None else f64(rows)
+    cols = np.zeros((m + p, 0)) if cols is None else f64(cols)
+    if rows.shape != (p, ns):
+        raise ValueError(f"extend: rows has shape {rows.shape}, expected {(p, ns)}")
+    if cols.shape != (m + p, r):
+        raise ValueError(f"extend: cols has shape {cols.shape}, expected {(m + p, r)} "
+                         "(the new columns over all rows, the new ones included)")
+    return rows, rhs, cols, c_cols
+
+
+def extended_lp(lp: CoreLP, rows=None, rhs=None, cols=None, c_cols=None) -> CoreLP:
+    """Host only: the LP a handle created on `lp` holds after Solver.extend with the same arguments
+    (dzg_solver_extend).  rows (p, n_struct) / rhs (p,): new constraints on the existing structural
+    columns; cols (m + p, r) / c_cols (r,): new structural columns over all rows, the new ones
+    included.  No existing index changes: the new structural variables are n .. n+r-1 on the columns
+    n_struct .. n_struct+r-1, the slacks of the new rows n+r .. n+r+p-1 on the rows m .. m+p-1; var_col
+    is explicit.  Basis positions 0 .. m-1 and nonbasic positions 0 .. q-1 keep lp's variables, the new
+    slacks follow in the basis and the new structural variables in the nonbasis, x = [lp.x, rhs] and
+    z = [lp.z, -c_cols]: for an `lp` in its slack start, the slack start of the extended LP.  -0.0
+    entries of the new blocks are +0.0 in `a`, as on the device."""
+    import dataclasses
+
+    if lp.a is None or lp.block is not None:
+        raise NotImplementedError("extend is not supported on CSC storage or sharded solvers")
+    m, ns, n = lp.m, lp.n_struct, lp.n
+    rows, rhs, cols, c_cols = _extend_blocks(m, ns, rows, rhs, cols, c_cols)
+    p, r = len(rhs), len(c_cols)
+    a = np.zeros((m + p, ns + r))
+    a[:m, :ns] = np.asarray(lp.a, dtype=np.float64)
+    a[m:, :ns] = rows + 0.0   # (-0.0 + 0.0 = +0.0)
+    a[:, ns:] = cols + 0.0
+    var_col = (i64(lp.var_col) if lp.var_col is not None
+               else np.concatenate([np.arange(ns), -1 - np.arange(n - ns)]).astype(np.int64))
+    var_col = np.concatenate([var_col, ns + np.arange(r), -1 - (m + np.arange(p))]).astype(np.int64)
+    return dataclasses.replace(
+        lp, a=a, c=np.concatenate([f64(lp.c), c_cols, np.zeros(p)]), var_col=var_col,
+        basis=np.concatenate([i64(lp.basis), n + r + np.arange(p)]).astype(np.int64),
+        nonbasis=np.concatenate([i64(lp.nonbasis), n + np.arange(r)]).astype(np.int64),
+        x=np.concatenate([f64(lp.x), rhs]), z=np.concatenate([f64(lp.z), -c_cols]),
+        xbar=None, zbar=None)
+
+
 @dataclass
 class CoreResult:
     status: str
@@ -405,6 +461,57 @@ class Solver:
         chg = _ffi.Reopt(ptr(b), ptr(c), 0.0 if constant is None else float(constant),
                          0 if constant is None else 1, 0)
         _ffi.check_reopt(_ffi.lib().dzg_solver_reoptimize(self._h, C.byref(chg)), "dzg_solver_reoptimize")
+
+    def extend(self, rows=None, rhs=None, cols=None, c_cols=None) -> None:
+        """dzg_solver_extend: appends constraint rows (rows (p, n_struct) on the existing structural
+        columns, rhs (p,)) and / or structural columns (cols (m + p, r) over all rows, the new ones
+        included, c_cols (r,), core sense) to the LP this solver holds and recomputes the state of the
+        extended basis -- the current one with the new slacks appended, the new variables nonbasic --
+        as reoptimize() does; run() then carries on from it.  No existing index changes (see
+        extended_lp, which is the LP this solver holds afterwards); the pivot count and log keep
+        accumulating.  The resident matrix is re-laid on the GPU, only the new numbers are uploaded;
+        both matrices are resident until the call returns.  Allowed where reoptimize() is; CSC and
+        sharded solvers: NotImplementedError.  ValueError for a wrong shape or when nothing is given.
+        All or nothing: a call that raises leaves the solver as it was."""
+        lp2 = extended_lp(self._lp, rows, rhs, cols, c_cols)
+        m, ns = self._lp.m, self._lp.n_struct
+        rows, rhs, cols, c_cols = _extend_blocks(m, ns, rows, rhs, cols, c_cols)
+        p, r = len(rhs), len(c_cols)
+        rows_rm = np.ascontiguousarray(rows)            # (p, ns) row-major
+        cols_cm = np.ascontiguousarray(cols.T)          # column-major (m + p) x r
+        ext = _ffi.Extend(p, r, ptr(rows_rm) if p else None, max(ns, 1), ptr(rhs) if p else None,
+                          ptr(cols_cm) if r else None, max(m + p, 1), ptr(c_cols) if r else None)
+        _ffi.check_extend(_ffi.lib().dzg_solver_extend(self._h, C.byref(ext)), "dzg_solver_extend")
+        self._lp = lp2
+
+    def dims(self) -> tuple[int, int, int]:
+        """dzg_solver_dims: (m, n, n_struct) of the LP the solver holds now."""
+        v = [C.c_int64(0), C.c_int64(0), C.c_int64(0)]
+        _ffi.check(_ffi.lib().dzg_solver_dims(self._h, *(C.byref(x) for x in v)), "dzg_solver_dims")
+        return tuple(int(x.value) for x in v)
+
+    def debug_matrix(self) -> np.ndarray:
+        """Test hook (dzg_debug_matrix): the (m, n_struct) matrix as the device holds it."""
+        m, _, ns = self.dims()
+        out = np.zeros((max(ns, 1), max(m, 1)))         # column-major m x ns
+        _ffi.check(_ffi.lib().dzg_debug_matrix(self._h, 0, ns, ptr(out), max(m, 1)), "dzg_debug_matrix")
+        return out[:ns, :m].T.copy()
+
+    def debug_matrix_rows(self) -> np.ndarray | None:
+        """Test hook (dzg_debug_matrix_rows): the row-major copy of the matrix the row-wise pricing
+        pass reads, (m, n_struct); None where that copy is not kept."""
+        m, _, ns = self.dims()
+        out = np.zeros((max(m, 1), max(ns, 1)))
+        got = _ffi.lib().dzg_debug_matrix_rows(self._h, 0, m, ptr(out), max(ns, 1))
+        _ffi.check(int(got), "dzg_debug_matrix_rows")
+        return out[:m, :ns].copy() if got == m and m > 0 else None
+
+    def debug_extend_ms(self) -> tuple[float, float, float]:
+        """dzg_debug_extend_ms: ms the last extend() spent on (the matrix, the refactorisation, the
+        restart state)."""
+        ms = np.zeros(3)
+        _ffi.check(_ffi.lib().dzg_debug_extend_ms(self._h, ptr(ms)), "dzg_debug_extend_ms")
+        return tuple(float(x) for x in ms)
 
     def debug_inverse(self, row0: int, row1: int) -> tuple[np.ndarray, dict]:
         """Test hook (dzg_debug_basis_inverse): rows [row0, row1) of the basis inverse FAST keeps --

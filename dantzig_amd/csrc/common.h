@@ -858,6 +858,14 @@ int dzg_drift_chunks(void);
 void dzg_launch_restart_x(const DzgDev &d, const double *rhs, double *ag, int k_bound, hipStream_t st);
 void dzg_launch_restart_z(const DzgDev &d, const double *cdev, const double *dzy, hipStream_t st);
 
+// k_extend.hip: the matrix of a live solver grown on the device (dzg_solver_extend).  The resident
+// m x ncols block from leading dimension lda to ldn; a staged p x ns row-major block into rows
+// row0..row0+p-1 of the column-major matrix (-0.0 stored as +0.0)
+void dzg_launch_extend_restride(const double *src, long long lda, double *dst, long long ldn, int m, int ncols,
+                                hipStream_t st);
+void dzg_launch_extend_rows(const double *rows, long long ldr, int p, int ns, double *A, long long lda, int row0,
+                            hipStream_t st);
+
 // k_sparse.hip
 void dzg_launch_sp_init(const DzgDev &d, int first, hipStream_t st);
 void dzg_launch_sp_ftran(const DzgDev &d, int need_kind, int nrz, hipStream_t st);

@@ -138,6 +138,10 @@ struct dzg_solver {
     double *ry_vec = nullptr, *ry_d = nullptr, *ry_part = nullptr, *ry_h = nullptr, *ry_res = nullptr;
     // dzg_solver_reoptimize (k_restart.hip), FAST: the new right-hand side in compact numbering
     double *ro_ag = nullptr;
+    // dzg_solver_extend, FAST: the residual of the restart state's refinement step
+    double *ro_res = nullptr;
+    // dzg_solver_extend: ms the last call spent on the matrix, the refactorisation, the restart state
+    double extend_ms[3] = {0.0, 0.0, 0.0};
     // FAST, dense, one GPU: the three-launch chain (k_chain.hip)
     unsigned long long *chain_bar = nullptr; // barrier counters (cleared only by chain_recover)
     unsigned long long *chain_dbg = nullptr; // DZG_CHAIN_DEBUG=1: phase clocks of workgroup 0
@@ -184,13 +188,15 @@ template <typename T> static int dev_alloc(dzg_solver *s, T **p, size_t count)
         if (rc_ != 0) return rc_; \
     } while (0)
 
-static int validate(const dzg_lp *lp, std::string &why)
+// matrix_on_device: the structural block is already resident (dzg_solver_extend builds its successor
+// from it), lp->a and the CSC arrays are not looked at
+static int validate(const dzg_lp *lp, std::string &why, bool matrix_on_device = false)
 {
     if (!lp) { why = "lp is NULL"; return 0; }
     if (lp->m < 0 || lp->n < lp->m || lp->n_struct < 0 || lp->n_struct > lp->n) { why = "bad sizes"; return 0; }
     if (lp->n >= (1ll << 31) - 64 || lp->m >= (1ll << 31) - 64) { why = "index range"; return 0; }
     if (lp->n_struct > 0 && lp->a && lp->lda < lp->m) { why = "lda"; return 0; }
-    if (lp->n_struct > 0 && !lp->a) {
+    if (lp->n_struct > 0 && !lp->a && !matrix_on_device) {
         if (!lp->col_ptr || lp->col_ptr[0] != 0) { why = "neither a nor col_ptr"; return 0; }
         for (int64_t j = 0; j < lp->n_struct; ++j) {
             if (lp->col_ptr[j + 1] < lp->col_ptr[j]) { why = "col_ptr not monotone"; return 0; }
@@ -347,6 +353,7 @@ static int upload_columns(dzg_solver *s, int64_t c0, int64_t c1, const double *a
             }
         HIP_OK(hipMemcpy2DAsync(dst, sizeof(double) * d.lda, tmp.data(), sizeof(double) * d.m,
                                 sizeof(double) * d.m, (size_t)cnt, hipMemcpyHostToDevice, s->st));
+        HIP_OK(hipStreamSynchronize(s->st)); // (tmp is a local: the copy must have read it)
     }
     HIP_OK(hipStreamSynchronize(s->st)); // the caller may reuse its buffer
     s->cols_present += cnt;
@@ -372,12 +379,26 @@ extern "C" int dzg_solver_upload_columns(dzg_solver *s, int64_t col_begin, int64
     return 0;
 }
 
-extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver **out)
+// dzg_solver_extend: the successor's matrix comes from the device -- the resident block of `old`,
+// re-laid for the new leading dimension, and the rows and columns of `ext` (lp->a is NULL and is not a
+// request for CSC storage; lp->x is the right-hand side by row)
+struct ExtendSrc {
+    const dzg_solver *old;
+    const dzg_extend *ext;
+};
+static int extend_fill_matrix(dzg_solver *s, const ExtendSrc &src);
+
+static double ms_since(std::chrono::steady_clock::time_point t0)
+{
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver **out, const ExtendSrc *src)
 {
     if (!out) return fail(DZG_E_ARG, "out is NULL");
     *out = nullptr;
     std::string why;
-    if (!validate(lp, why)) return fail(DZG_E_ARG, "invalid dzg_lp: " + why);
+    if (!validate(lp, why, src != nullptr)) return fail(DZG_E_ARG, "invalid dzg_lp: " + why);
     dzg_opts o;
     if (opts_in) o = *opts_in; else dzg_opts_default(&o);
     if (o.max_iter <= 0) o.max_iter = 10000000;
@@ -444,7 +465,7 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
                            : (o.a_is_block && d.world > 1) ? lp->a
                                                            : lp->a + (size_t)d.col0 * (size_t)lp->lda;
 
-    d.csc = (ns > 0 && !lp->a) ? 1 : 0;
+    d.csc = (ns > 0 && !lp->a && !src) ? 1 : 0;
     // opts.shard_rows: the basis side sharded by rows as well (k_rowshard.hip)
     d.rs = 0;
     d.rs_r0 = 0;
@@ -541,7 +562,9 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
     A = A_alloc + (size_t)(d.col0 - mem0) * (size_t)d.lda;   // column col0: kernels index from it
     s->A_alloc = A_alloc;
     s->cols_present = d.repl ? nloc : ns;
-    if (ndense > 0 && m > 0) {
+    if (src) {
+        TRY(extend_fill_matrix(s, *src));
+    } else if (ndense > 0 && m > 0) {
         // the reference's CSC drops exact zeros (src/linalg.rs:261), so -0.0 entries act as +0.0
         bool has_negzero = false;
         for (int64_t j = 0; j < nloc && !has_negzero; ++j)
@@ -625,7 +648,7 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
         bool own_rows = true;
         for (int p = 0; p < m; ++p)
             if (var_col[basis[p]] != -1 - p) own_rows = false;
-        if (!own_rows && !(o.a_is_block && d.world > 1)) {
+        if (!own_rows && !(o.a_is_block && d.world > 1) && !src) {
             std::vector<double> rhs((size_t)m, 0.0);
             for (int p = 0; p < m; ++p) {
                 const int code = var_col[basis[p]];
@@ -692,7 +715,7 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
             s->opts.refactor_interval = o.refactor_interval;
         }
         const bool needs_initial_refactor = !slack_basis && !s->pending_refactor;
-        if (slack_basis && d.world == 1 && !d.csc && m > 0 && q > 0) {
+        if (slack_basis && d.world == 1 && !d.csc && m > 0 && q > 0 && !src) {
             // the state a refactorisation can be checked against (k_drift.hip): b = the starting x,
             // xbar0 = the starting xbar, c, and cbar: the c whose reduced costs zbar is (-zbar0 on the
             // starting nonbasics, 0 on the slacks), as c is for z
@@ -846,7 +869,13 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
         } else {
             dzg_launch_fast_update(d, 1, s->st); // first-pivot partials of the initial state
         }
-        if (needs_initial_refactor) {
+        if (needs_initial_refactor && src) { // (dzg_debug_extend_ms: the refactorisation on its own)
+            HIP_OK(hipStreamSynchronize(s->st));
+            const auto t0 = std::chrono::steady_clock::now();
+            TRY(refactor_now(s));
+            HIP_OK(hipStreamSynchronize(s->st));
+            s->extend_ms[1] = ms_since(t0);
+        } else if (needs_initial_refactor) {
             TRY(refactor_now(s));
         }
     } else {
@@ -871,6 +900,11 @@ extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_
     guard.s = nullptr;
     *out = s;
     return 0;
+}
+
+extern "C" int dzg_solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver **out)
+{
+    return solver_create(lp, opts_in, out, nullptr);
 }
 
 // ---- one iteration, enqueued ------------------------------------------------------
@@ -2784,6 +2818,9 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
 }
 
 // ---- re-optimisation from the current basis after b or c change (k_restart.hip) ----
+static int restart_state(dzg_solver *s, const double *rhs, const double *c, const double *constant,
+                         bool refine = false);
+
 static int reopt_finite(const char *name, const double *v, int64_t count)
 {
     for (int64_t i = 0; v && i < count; ++i)
@@ -2798,7 +2835,7 @@ extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
     if (!chg->rhs && !chg->c && !chg->set_constant)
         return fail(DZG_E_ARG, "reoptimize: nothing to change (rhs and c are NULL, set_constant is 0)");
     DzgDev &d = s->d;
-    const int m = d.m, q = d.q, n = d.n;
+    const int m = d.m, n = d.n;
     TRY(reopt_finite("rhs", chg->rhs, m));
     TRY(reopt_finite("c", chg->c, n));
     if (chg->set_constant && !std::isfinite(chg->constant))
@@ -2816,7 +2853,6 @@ extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
     if (status == DZG_SINGULAR || status == DZG_PANIC || status < 0 || status > DZG_NEAR_TIE)
         return fail(DZG_E_ARG, std::string("reoptimize: the solver's status is ") + dzg_status_str(status) +
                                    ": its basis cannot be carried on from");
-    hipStream_t st = s->st;
     TRY(duals_workspace(s));
     if (fast && !s->ro_ag) TRY(dev_alloc(s, &s->ro_ag, (size_t)m + 2));
     if (fast) {
@@ -2838,10 +2874,28 @@ extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
             return fail(DZG_E_DEVICE, "reoptimize: the current basis did not refactorise (singular block)");
         }
     }
+    return restart_state(s, chg->rhs, chg->c, chg->set_constant ? &chg->constant : nullptr);
+}
+
+// The state of the current basis for new data (NULL: what the handle holds), written; FAST: the inverse
+// is fresh (the caller has just refactorised), s->h_ctl is current.  The body dzg_solver_reoptimize and
+// dzg_solver_extend share.  refine (FAST): x and y take one step of iterative refinement against a
+// double-double residual, the step dzg_solver_ray takes (k_rays.hip): what the explicit inverse loses
+// to cancellation comes back.  dzg_solver_reoptimize keeps the bits it has always given.
+static int restart_state(dzg_solver *s, const double *rhs, const double *c, const double *constant, bool refine)
+{
+    DzgDev &d = s->d;
+    const int m = d.m, q = d.q, n = d.n;
+    const bool fast = s->numerics == DZG_NUMERICS_FAST;
+    DzgCtl *h = s->h_ctl;
+    hipStream_t st = s->st;
+    TRY(duals_workspace(s));
+    if (fast && !s->ro_ag) TRY(dev_alloc(s, &s->ro_ag, (size_t)m + 2));
+    if (fast && refine && !s->ro_res) TRY(dev_alloc(s, &s->ro_res, (size_t)m));
     // the new data, on the host and in the device copies every post-solve call reads
-    if (chg->c) s->c_host.assign(chg->c, chg->c + n);
-    if (chg->rhs) s->x0_host.assign(chg->rhs, chg->rhs + m);
-    if (chg->set_constant) s->constant = chg->constant;
+    if (c) s->c_host.assign(c, c + n);
+    if (rhs) s->x0_host.assign(rhs, rhs + m);
+    if (constant) s->constant = *constant;
     if (n) HIP_OK(hipMemcpyAsync(s->du_c, s->c_host.data(), sizeof(double) * n, hipMemcpyHostToDevice, st));
     if (m) HIP_OK(hipMemcpyAsync(s->du_rhs0, s->x0_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
     if (fast) {
@@ -2849,6 +2903,12 @@ extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
         dzg_launch_restart_x(d, s->du_rhs0, s->ro_ag, k, st);
         // y by the two-stage scheme of the drift measurement, dzy = -N^T y by one column-wise pricing pass
         dzg_launch_drift_y(d, s->du_c, s->du_part, s->du_y, k, st);
+        if (refine && m) {
+            dzg_launch_ray_resid_dx(d, s->du_rhs0, d.x, s->ro_res, st);      // rhs - B x, by row
+            dzg_launch_ray_dx_fast(d, k, s->ro_res, 1, d.x, st);
+            dzg_launch_ray_resid_v(d, -1, s->du_y, s->ro_res, st, s->du_c);  // c_B - B^T y, by position
+            dzg_launch_ray_vt_fast(d, k, s->ro_res, 1, s->du_y, st);
+        }
         if (q) dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->du_dzy, st);
     } else {
         // the LU of every STRICT FTRAN / BTRAN on a copy of the device view whose control block reads
@@ -2891,6 +2951,220 @@ extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
     HIP_OK(hipStreamSynchronize(st));
     HIP_OK(hipGetLastError());
     return 0;
+}
+
+// ---- rows and columns added to a live LP, re-optimised from its basis (k_extend.hip) ----
+// (a p x r block stored with leading dimension ld, p entries contiguous)
+static int extend_finite(const char *name, const double *v, int64_t len, int64_t count, int64_t ld)
+{
+    for (int64_t j = 0; v && j < count; ++j)
+        for (int64_t i = 0; i < len; ++i)
+            if (!std::isfinite(v[j * ld + i]))
+                return fail(DZG_E_ARG, std::string("extend: ") + name + "[" + std::to_string(j * ld + i) +
+                                           "] is not finite");
+    return 0;
+}
+
+// The successor's matrix (zeroed, lda' x n_struct'): the resident block re-laid, the new rows transposed
+// in from a staging block, the new columns by the path of dzg_solver_upload_columns.
+static int extend_fill_matrix(dzg_solver *s, const ExtendSrc &src)
+{
+    const dzg_solver *old = src.old;
+    const dzg_extend *e = src.ext;
+    const DzgDev &d = s->d;
+    const int m0 = old->d.m, ns0 = old->d.ns, p = (int)e->n_rows, r = (int)e->n_cols;
+    hipStream_t st = s->st;
+    dzg_launch_extend_restride(old->A_alloc, old->d.lda, s->A_alloc, d.lda, m0, ns0, st);
+    if (p > 0 && ns0 > 0) {
+        void *stage = nullptr;
+        const size_t bytes = sizeof(double) * (size_t)p * (size_t)ns0;
+        if (hipMalloc(&stage, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(DZG_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
+        }
+        struct Free { void *p; ~Free() { hipFree(p); } } free_stage{stage};
+        HIP_OK(hipMemcpy2DAsync(stage, sizeof(double) * (size_t)ns0, e->rows, sizeof(double) * (size_t)e->ld_rows,
+                                sizeof(double) * (size_t)ns0, (size_t)p, hipMemcpyHostToDevice, st));
+        dzg_launch_extend_rows(static_cast<const double *>(stage), ns0, p, ns0, s->A_alloc, d.lda, m0, st);
+        HIP_OK(hipStreamSynchronize(st)); // (the staging block goes away)
+    }
+    if (r > 0) {
+        TRY(upload_columns(s, ns0, (int64_t)ns0 + r, e->cols, e->ld_cols));
+        s->cols_present -= r; // (counted at creation already)
+    }
+    return 0;
+}
+
+extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
+{
+    if (!s || !ext) return fail(DZG_E_ARG, "extend: NULL argument");
+    const int64_t p = ext->n_rows, r = ext->n_cols;
+    if (p < 0 || r < 0) return fail(DZG_E_ARG, "extend: n_rows and n_cols must not be negative");
+    if (p == 0 && r == 0) return fail(DZG_E_ARG, "extend: nothing to add (n_rows and n_cols are 0)");
+    const int64_t m = s->d.m, n = s->d.n, ns = s->d.ns, q = s->d.q;
+    const int64_t m2 = m + p, n2 = n + p + r, ns2 = ns + r, q2 = q + r;
+    if (s->d.csc || s->d.world > 1)
+        return fail(DZG_E_ARG, "extend is not supported on CSC storage or sharded solvers");
+    if (n2 >= (1ll << 31) - 64) return fail(DZG_E_ARG, "extend: index range");
+    if (p > 0 && (!ext->rhs || (ns > 0 && !ext->rows)))
+        return fail(DZG_E_ARG, "extend: n_rows > 0 needs rows and rhs");
+    if (p > 0 && ns > 0 && ext->ld_rows < ns) return fail(DZG_E_ARG, "extend: ld_rows < n_struct");
+    if (r > 0 && (!ext->c_cols || (m2 > 0 && !ext->cols)))
+        return fail(DZG_E_ARG, "extend: n_cols > 0 needs cols and c_cols");
+    if (r > 0 && ext->ld_cols < m2) return fail(DZG_E_ARG, "extend: ld_cols < m + n_rows");
+    if (p > 0) TRY(extend_finite("rows", ext->rows, ns, p, ext->ld_rows));
+    if (p > 0) TRY(extend_finite("rhs", ext->rhs, p, 1, p));
+    if (r > 0) TRY(extend_finite("cols", ext->cols, m2, r, ext->ld_cols));
+    if (r > 0) TRY(extend_finite("c_cols", ext->c_cols, r, 1, r));
+    const bool fast = s->numerics == DZG_NUMERICS_FAST;
+    if (fast && !s->rf_piv)
+        return fail(DZG_E_ARG, "extend: a FAST solver needs its refactorisation workspace: create it "
+                               "with opts.refactor_interval != 0");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    const DzgCtl h0 = *s->h_ctl;
+    if (h0.status == DZG_SINGULAR || h0.status == DZG_PANIC || h0.status < 0 || h0.status > DZG_NEAR_TIE)
+        return fail(DZG_E_ARG, std::string("extend: the solver's status is ") + dzg_status_str(h0.status) +
+                                   ": its basis cannot be carried on from");
+    hipStream_t st = s->st;
+
+    // the extended LP on the host: everything but the matrix
+    std::vector<int> basis0((size_t)(m ? m : 1)), nonbasis0((size_t)(q ? q : 1));
+    if (m) HIP_OK(hipMemcpyAsync(basis0.data(), s->d.basis, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+    if (q) HIP_OK(hipMemcpyAsync(nonbasis0.data(), s->d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    std::vector<int64_t> basis((size_t)(m2 ? m2 : 1)), nonbasis((size_t)(q2 ? q2 : 1)), var_col((size_t)(n2 ? n2 : 1));
+    std::vector<double> c2((size_t)(n2 ? n2 : 1), 0.0), rhs2((size_t)(m2 ? m2 : 1), 0.0), z2((size_t)(q2 ? q2 : 1), 0.0);
+    for (int64_t i = 0; i < m; ++i) basis[(size_t)i] = basis0[(size_t)i];
+    for (int64_t i = 0; i < p; ++i) basis[(size_t)(m + i)] = n + r + i;
+    for (int64_t k = 0; k < q; ++k) nonbasis[(size_t)k] = nonbasis0[(size_t)k];
+    for (int64_t j = 0; j < r; ++j) nonbasis[(size_t)(q + j)] = n + j;
+    for (int64_t v = 0; v < n; ++v) {
+        var_col[(size_t)v] = s->var_col_host[(size_t)v];
+        c2[(size_t)v] = s->c_host[(size_t)v];
+    }
+    for (int64_t j = 0; j < r; ++j) {
+        var_col[(size_t)(n + j)] = ns + j;
+        c2[(size_t)(n + j)] = ext->c_cols[j];
+    }
+    for (int64_t i = 0; i < p; ++i) var_col[(size_t)(n + r + i)] = -1 - (m + i);
+    for (int64_t i = 0; i < m; ++i) rhs2[(size_t)i] = s->x0_host[(size_t)i];
+    for (int64_t i = 0; i < p; ++i) rhs2[(size_t)(m + i)] = ext->rhs[i];
+    dzg_lp lp;
+    std::memset(&lp, 0, sizeof(lp));
+    lp.m = m2; lp.n = n2; lp.n_struct = ns2;
+    lp.var_col = var_col.data();
+    lp.c = c2.data();
+    lp.constant = s->constant;
+    lp.basis = basis.data(); lp.nonbasis = nonbasis.data();
+    lp.x = rhs2.data(); lp.z = z2.data(); // (the right-hand side by row; the state is written below)
+
+    // the successor, on the same stream with the same options and the numerics the handle runs in
+    dzg_opts o = s->opts;
+    o.stream = (void *)st;
+    o.numerics = s->numerics;
+    const ExtendSrc src{s, ext};
+    dzg_solver *t = nullptr;
+    const auto t0 = std::chrono::steady_clock::now();
+    TRY(solver_create(&lp, &o, &t, &src));
+    struct Guard { dzg_solver *t; ~Guard() { if (t) dzg_solver_destroy(t); } } guard{t};
+    if (fast && t->refactors == 0) {
+        // the slack basis, which creation does not factorise: the restart kernels read the lists a
+        // refactorisation leaves, as they do in dzg_solver_reoptimize before a first run
+        const auto tr = std::chrono::steady_clock::now();
+        TRY(refactor_now(t, true));
+        HIP_OK(hipStreamSynchronize(st));
+        t->extend_ms[1] = ms_since(tr);
+    }
+    TRY(read_ctl(t));
+    if (t->h_ctl->status != DZG_RUNNING)
+        return fail(DZG_E_DEVICE, "extend: the extended basis did not refactorise (singular block)");
+    t->extend_ms[0] = ms_since(t0) - t->extend_ms[1];
+    // what carries on: the pivot count and everything counted per pivot, the log
+    DzgCtl *h = t->h_ctl;
+    h->iter = h0.iter;
+    h->price_bytes = h0.price_bytes;
+    h->price_mask = h0.price_mask;
+    h->min_margin = h0.min_margin;
+    h->near_ties = h0.near_ties;
+    h->first_near_tie = h0.first_near_tie;
+    const auto t1 = std::chrono::steady_clock::now();
+    TRY(restart_state(t, nullptr, nullptr, nullptr, true));
+    t->extend_ms[2] = ms_since(t1);
+    const long long cnt = h0.iter < s->d.log_cap ? h0.iter : s->d.log_cap;
+    if (cnt > 0 && cnt <= t->d.log_cap) {
+        HIP_OK(hipMemcpyAsync(t->d.log_kind, s->d.log_kind, sizeof(int) * cnt, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(t->d.log_enter, s->d.log_enter, sizeof(int) * cnt, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(t->d.log_leave, s->d.log_leave, sizeof(int) * cnt, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(t->d.log_mu, s->d.log_mu, sizeof(double) * cnt, hipMemcpyDeviceToDevice, st));
+        HIP_OK(hipMemcpyAsync(t->d.log_margin, s->d.log_margin, sizeof(double) * cnt, hipMemcpyDeviceToDevice, st));
+    }
+    HIP_OK(hipStreamSynchronize(st));
+    HIP_OK(hipGetLastError());
+    t->solve_ms = s->solve_ms;
+    t->refactors += s->refactors;
+    t->max_err_life = s->max_err_life;
+    t->chain_fallbacks = s->chain_fallbacks;
+    for (int c = 0; c < DZG_K_COUNT; ++c) {
+        t->kernel_ms[c] = s->kernel_ms[c];
+        t->kernel_launches[c] = s->kernel_launches[c];
+    }
+    // the successor takes the handle's place (the caller's pointer stays valid); the old state goes
+    std::swap(*s, *t);
+    s->opts = t->opts;
+    s->own_stream = t->own_stream;
+    t->own_stream = false;
+    guard.t = nullptr;
+    dzg_solver_destroy(t);
+    return 0;
+}
+
+extern "C" int dzg_solver_dims(const dzg_solver *s, int64_t *m, int64_t *n, int64_t *n_struct)
+{
+    if (!s) return fail(DZG_E_ARG, "dims: solver is NULL");
+    if (m) *m = s->d.m;
+    if (n) *n = s->d.n;
+    if (n_struct) *n_struct = s->d.ns;
+    return 0;
+}
+
+extern "C" int dzg_debug_extend_ms(const dzg_solver *s, double ms[3])
+{
+    if (!s || !ms) return fail(DZG_E_ARG, "extend_ms: NULL argument");
+    for (int i = 0; i < 3; ++i) ms[i] = s->extend_ms[i];
+    return 0;
+}
+
+extern "C" int dzg_debug_matrix(dzg_solver *s, int64_t col0, int64_t col1, double *out, int64_t ld_out)
+{
+    if (!s || (col1 > col0 && !out)) return fail(DZG_E_ARG, "matrix: NULL argument");
+    const DzgDev &d = s->d;
+    if (d.csc || d.world > 1) return fail(DZG_E_ARG, "matrix: a dense matrix on one GPU");
+    if (col0 < 0 || col1 > d.ns || col0 > col1 || ld_out < d.m)
+        return fail(DZG_E_ARG, "matrix: columns outside [0, n_struct) or ld_out < m");
+    if (col1 == col0 || d.m == 0) return 0;
+    HIP_OK(hipSetDevice(s->opts.device));
+    HIP_OK(hipStreamSynchronize(s->st));
+    HIP_OK(hipMemcpy2D(out, sizeof(double) * (size_t)ld_out, s->A_alloc + (size_t)col0 * (size_t)d.lda,
+                       sizeof(double) * (size_t)d.lda, sizeof(double) * (size_t)d.m, (size_t)(col1 - col0),
+                       hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int64_t dzg_debug_matrix_rows(dzg_solver *s, int64_t row0, int64_t row1, double *out, int64_t ld_out)
+{
+    if (!s || (row1 > row0 && !out)) return fail(DZG_E_ARG, "matrix_rows: NULL argument");
+    const DzgDev &d = s->d;
+    if (d.csc || d.world > 1) return fail(DZG_E_ARG, "matrix_rows: a dense matrix on one GPU");
+    if (row0 < 0 || row1 > d.m || row0 > row1 || ld_out < d.ns)
+        return fail(DZG_E_ARG, "matrix_rows: rows outside [0, m) or ld_out < n_struct");
+    if (!d.At || row1 == row0 || d.ns == 0) return 0;
+    HIP_OK(hipSetDevice(s->opts.device));
+    HIP_OK(hipStreamSynchronize(s->st));
+    HIP_OK(hipMemcpy2D(out, sizeof(double) * (size_t)ld_out, d.At + (size_t)row0 * (size_t)d.ldt,
+                       sizeof(double) * (size_t)d.ldt, sizeof(double) * (size_t)d.ns, (size_t)(row1 - row0),
+                       hipMemcpyDeviceToHost));
+    return row1 - row0;
 }
 
 // What a one-call solve wants beyond the result: the duals and, with `req`, the ranges of the solver

@@ -214,15 +214,16 @@ __global__ __launch_bounds__(256) void k_ray_resid_dx(const DzgDev d, const doub
     res[r] = hi + lo;
 }
 
-// res[p] = unit(pos)[p] - (B^T y)_p, one wave per basis position p (its column of B in lane order)
-__global__ __launch_bounds__(256) void k_ray_resid_v(const DzgDev d, int pos, const double *__restrict__ y,
-                                                     double *__restrict__ res)
+// res[p] = t[p] - (B^T y)_p with t = unit(pos), or t[p] = cvar[basis[p]] where cvar is given (c_B: the
+// residual of the dual vector); one wave per basis position p (its column of B in lane order)
+__global__ __launch_bounds__(256) void k_ray_resid_v(const DzgDev d, int pos, const double *__restrict__ cvar,
+                                                     const double *__restrict__ y, double *__restrict__ res)
 {
     const int lane = threadIdx.x & 63;
     const int p = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (p >= d.m) return; // (whole waves)
     const int bc = d.bcode[p];
-    double hi = (lane == 0 && p == pos) ? 1.0 : 0.0, lo = 0.0;
+    double hi = lane != 0 ? 0.0 : cvar ? cvar[d.basis[p]] : (p == pos ? 1.0 : 0.0), lo = 0.0;
     if (bc >= 0) {
         const double *col = d.A + (long long)bc * d.lda;
         for (int r = lane; r < d.m; r += 64) dd_add_prod(hi, lo, -col[r], y[r]);
@@ -336,10 +337,11 @@ void dzg_launch_ray_resid_dx(const DzgDev &d, const double *h, const double *dx,
     hipLaunchKernelGGL(k_ray_resid_dx, dim3((d.m + 255) / 256), dim3(256), 0, st, d, h, dx, res);
 }
 
-void dzg_launch_ray_resid_v(const DzgDev &d, int pos, const double *y, double *res, hipStream_t st)
+void dzg_launch_ray_resid_v(const DzgDev &d, int pos, const double *y, double *res, hipStream_t st,
+                            const double *cvar)
 {
     if (d.m <= 0) return;
-    hipLaunchKernelGGL(k_ray_resid_v, dim3((d.m + 3) / 4), dim3(256), 0, st, d, pos, y, res);
+    hipLaunchKernelGGL(k_ray_resid_v, dim3((d.m + 3) / 4), dim3(256), 0, st, d, pos, cvar, y, res);
 }
 
 void dzg_launch_ray_finish(int kind, int m, int q, int pos, const int *basis, const int *nonbasis,

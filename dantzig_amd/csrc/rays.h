@@ -37,9 +37,11 @@ void dzg_launch_ray_dx_fast(const DzgDev &d, int k, const double *h, int accumul
 // v[r] (+)= (M^T w)_r
 void dzg_launch_ray_vt_fast(const DzgDev &d, int k, const double *w, int accumulate, double *v, hipStream_t st);
 // the residuals of one refinement step, accumulated in double-double:
-// res[r] = h[r] - (B dx)_r   and   res[p] = unit(pos)[p] - (B^T y)_p
+// res[r] = h[r] - (B dx)_r   and   res[p] = unit(pos)[p] - (B^T y)_p  (with cvar, c by variable:
+// res[p] = cvar[basis[p]] - (B^T y)_p, the residual of y = B^-T c_B; pos is not looked at)
 void dzg_launch_ray_resid_dx(const DzgDev &d, const double *h, const double *dx, double *res, hipStream_t st);
-void dzg_launch_ray_resid_v(const DzgDev &d, int pos, const double *y, double *res, hipStream_t st);
+void dzg_launch_ray_resid_v(const DzgDev &d, int pos, const double *y, double *res, hipStream_t st,
+                            const double *cvar = nullptr);
 
 // Workgroups of k_ray_finish = partial records it leaves; a record is DZG_RAY_PART doubles:
 // max of max(vec, 0), 1.0 if the block met a NaN else 0.0, the block's share of the value's sum

@@ -13,6 +13,8 @@ import abc
 from dataclasses import dataclass
 from typing import Union
 
+import numpy as np
+
 from . import _ffi, core
 from . import rust as rs
 from .exceptions import InfeasibleError, SolveError, UnboundedError
@@ -328,8 +330,11 @@ class Session:
     """A model kept on the GPU between solves (Optimize.session): the first solve() lowers the model,
     uploads it and solves it from the slack basis; every later solve(objective=..., rhs=...) changes
     the objective and / or right-hand sides and re-optimises from the basis the last solve ended on
-    (core.Solver.reoptimize), without a new upload.  Changes accumulate.  Only b and the objective may
-    change: variable bounds, matrix coefficients and integer variables are out of scope.
+    (core.Solver.reoptimize), without a new upload.  Changes accumulate.  add_constraints() appends
+    constraints over the model's variables: the next solve() extends the live solver by their rows
+    (core.Solver.extend: the resident matrix grows on the GPU) and carries on from the same basis.
+    Besides that only b and the objective may change: variable bounds, the coefficients of an existing
+    row, new variables and integer variables are out of scope.
 
     Numerics is the handle's: AUTO runs STRICT up to auto_strict_rows rows, else FAST with near
     ties counted.  A re-optimised path is not the reference's path from the slack basis, so the
@@ -341,6 +346,8 @@ class Session:
         self._constraints = list(problem.constraints)
         self._objective = problem.objective
         self._rhs: dict = {}   # id(constraint) -> the new b of its normal form
+        self._added: list = []  # constraints added to a live solver, in the order of their rows
+        self._extended = 0      # ... of which the solver holds this many already
         self._opts = {**rs._options, **core_opts}
         self._opts.setdefault("refactor_interval", -1)  # (FAST: reserves what reoptimize needs)
         self._solver = None
@@ -371,10 +378,55 @@ class Session:
         arrays, order = rs.lower(*problem)
         return problem, arrays, order
 
+    def add_constraints(self, constraints) -> "Session":
+        """Add one constraint or a list of constraints over variables the model already has.  Before
+        the first solve() they simply join the model.  After it, the next solve() appends their rows
+        below the rows the solver holds (the model's, then the bound rows, then earlier additions),
+        and re-optimises from the last basis; solve(rhs={constraint: b}) works on them as on any
+        other.  ValueError for a variable the model has not seen, for an integer variable and for a
+        constraint that is already part of the session; nothing is added then."""
+        batch = [constraints] if isinstance(constraints, Constraint) else constraints
+        if not isinstance(batch, list) or not all(isinstance(c, Constraint) for c in batch):
+            raise TypeError("add_constraints takes a Constraint or a list of Constraints")
+        known = {id(c) for c in self._constraints + self._added}
+        order = self._order if self._solver is not None else self._lowered()[2]
+        seen = {v.id for v in order}
+        for k, constraint in enumerate(batch):
+            if id(constraint) in known or any(constraint is c for c in batch[:k]):
+                raise ValueError("add_constraints: the constraint is already part of the session")
+            for ineq in constraint.rust_inequalities():
+                if any(v.is_integer for v in ineq._linexpr.vars):
+                    raise ValueError("add_constraints: integer variables are not defined for a session")
+                if any(v.id not in seen for v in ineq._linexpr.vars):
+                    raise ValueError("add_constraints: the constraint uses a variable the model has not seen "
+                                     "(adding variables is a core-level feature: core.Solver.extend)")
+        if self._solver is None:
+            self._constraints += batch
+        else:
+            self._added += batch
+        return self
+
+    def _rows_of(self, constraint, form, order) -> list:
+        """The rows of `constraint` over the structural columns of `form` (the standard form of this
+        session's model, variables in `order`): [(coefficients by column, b)], one per inequality
+        sum coef_u u <= b it lowers to, +coef on the column of u's x+ and -coef on that of its x-; a
+        repeated variable keeps its last coefficient, as the builder's rows do."""
+        slot = {v.id: i for i, v in enumerate(order)}
+        new_b = self._rhs.get(id(constraint))
+        out = []
+        for ineq, sign in zip(constraint.rust_inequalities(), constraint._signs):
+            row = np.zeros(form.n_struct)
+            for coef, v in zip(ineq._linexpr.coefs, ineq._linexpr.vars):
+                u = slot[v.id]
+                row[form.var_col[form.pos_var[u]]] = coef
+                row[form.var_col[form.neg_var[u]]] = -coef
+            out.append((row, ineq._b if new_b is None else sign * new_b))
+        return out
+
     def _change(self, objective, rhs) -> None:
         if objective is not None:
             self._objective = objective.to_affexpr()
-        known = {id(c) for c in self._constraints}
+        known = {id(c) for c in self._constraints + self._added}
         for constraint, b in (rhs or {}).items():
             if id(constraint) not in known:
                 raise KeyError("the constraint is not part of the session's model")
@@ -400,6 +452,11 @@ class Session:
                                                  and [v.id for v in order] == [v.id for v in self._order]):
                 raise ValueError("session: the new objective or right-hand side changes the standard form "
                                  "(only b and the objective's coefficients may change)")
+            # the rows added to the live solver, below the form's: their b follows the form's
+            added = [r for c in self._added for r in self._rows_of(c, form, order)]
+            pending = [r for c in self._added[self._extended:] for r in self._rows_of(c, form, order)]
+            b_all = np.concatenate([form.x, [b for _, b in added]])
+            c_all = np.concatenate([form.c, np.zeros(len(added))])
         except Exception:
             self._objective, self._rhs = before
             raise
@@ -408,7 +465,10 @@ class Session:
                              z=form.z, var_col=form.var_col, constant=form.constant)
             self._solver = core.Solver(lp, **self._opts)
         else:
-            self._solver.reoptimize(b=form.x, c=form.c, constant=form.constant)
+            if pending:
+                self._solver.extend(rows=np.array([row for row, _ in pending]), rhs=[b for _, b in pending])
+                self._extended = len(self._added)
+            self._solver.reoptimize(b=b_all, c=c_all, constant=form.constant)
         self._form, self._order = form, order
         self._solver.run(0)
         res = self._solver.result(log=False)
@@ -425,13 +485,16 @@ class Session:
         for i, v in enumerate(order):  # x+ - x- (src/simplex.rs:354-371)
             values[v.id] = by_var.get(int(form.pos_var[i]), 0.0) - by_var.get(int(form.neg_var[i]), 0.0)
         return Solution(solution=rs.PySolution(res.objective, values, self.pivots[-1], res.numerics,
-                                               (form.m, form.n)), sense=self._problem.sense)
+                                               (form.m + len(added), form.n + len(added))),
+                        sense=self._problem.sense)
 
     def close(self) -> None:
         if self._solver is not None:
             self._solver.close()
             self._solver = None
             self._iterations = 0  # (a later solve() starts a new solver from the slack basis)
+            self._constraints += self._added  # (... of the whole model)
+            self._added, self._extended = [], 0
 
     def __enter__(self):
         return self

@@ -663,6 +663,60 @@ typedef struct {
  * optimum (or the verdict), not the pivots. */
 int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg);
 
+/* ---- Rows and columns added to a live LP, re-optimised from its basis (csrc/k_extend.hip) ---- */
+
+/* p new constraint rows and r new structural columns for the LP a live handle holds. */
+typedef struct {
+    int64_t n_rows;        /* p >= 0 new constraint rows, appended below row m-1                     */
+    int64_t n_cols;        /* r >= 0 new structural columns, appended after column n_struct-1        */
+    const double *rows;    /* p x n_struct, ROW-major, leading dimension ld_rows >= n_struct:
+                              the new rows' coefficients on the EXISTING structural columns          */
+    int64_t ld_rows;
+    const double *rhs;     /* p                                                                      */
+    const double *cols;    /* (m+p) x r, COLUMN-major, ld_cols >= m+p: the new columns over all rows,
+                              the new ones included                                                  */
+    int64_t ld_cols;
+    const double *c_cols;  /* r objective coefficients (core sense: maximised)                       */
+} dzg_extend;
+
+/* Appends the rows and columns of `ext` to the LP and leaves the handle in the state
+ * dzg_solver_reoptimize leaves it in, on the extended LP and the extended basis B':
+ * dzg_solver_run then carries on from B' with the parametric self-dual method.
+ *   Numbering: no existing variable, row or column index changes.  With m, n, n_struct, q = n - m
+ *   the sizes before the call, the new structural variables are n .. n+r-1 on the columns
+ *   n_struct .. n_struct+r-1; the slacks of the new rows are n+r .. n+r+p-1 on the rows m .. m+p-1.
+ *   A handle created with var_col == NULL holds an explicit var_col afterwards.  Basis positions
+ *   0 .. m-1 keep their variables and positions m .. m+p-1 hold the new slacks; nonbasic positions
+ *   0 .. q-1 keep theirs and positions q .. q+r-1 hold the new structural variables: the pivot log
+ *   stays readable across the call.
+ *   State: x = B'^-1 rhs', z_k = a_{N'_k} . y - c'[N'_k] with y = B'^-T c'_{B'}, xbar = zbar = 1,
+ *   status DZG_RUNNING, no pivot in flight, the drift measurement switched off -- all as
+ *   dzg_solver_reoptimize writes them, STRICT bit for bit the reference's LU::solve and neg_t_dot,
+ *   FAST from a fresh refactorisation of B' and one step of iterative refinement of x and y against
+ *   a double-double residual, the step dzg_solver_ray takes (deterministic, no atomics).  At the slack basis
+ *   x = rhs' and z = -c' exactly.  The pivot count, the log, the margins, near_ties, first_near_tie,
+ *   min_margin, refactors, solve_ms and max_pivot_error carry on; opts.max_iter bounds the total.
+ *   The handle keeps the numerics it was created with, even if m + p crosses auto_strict_rows.
+ *   A later dzg_solver_duals, _ranging, _ray, _reoptimize or _result speaks about the extended LP
+ *   (dzg_solver_reoptimize then takes m + p and n + p + r entries; dzg_solver_dims reports them).
+ *   Allowed in the states dzg_solver_reoptimize allows, before the first run included.
+ *   DZG_E_ARG, on the host before any device work: NULL `s` or `ext`; p == r == 0; a negative count;
+ *   ld_rows < n_struct or ld_cols < m + p; a needed array that is NULL; a NaN or infinite entry
+ *   (dzg_last_error names the array and the index); CSC storage or a column- or row-sharded solver
+ *   ("extend is not supported on CSC storage or sharded solvers"); a FAST handle without its
+ *   refactorisation workspace (opts.refactor_interval == 0); status DZG_SINGULAR or DZG_PANIC.
+ * All or nothing: the extended LP is built as a successor next to the live state and takes its place
+ * only when everything has succeeded.  If device memory runs out (DZG_E_NOMEM) or B' does not
+ * refactorise (DZG_E_DEVICE) the handle is exactly what it was.
+ * Memory: until the swap BOTH matrices are resident -- lda x n_struct and lda' x (n_struct + r)
+ * doubles, each with its row-major copy where one is kept -- next to both sets of state vectors and
+ * FAST's two inverses; the old ones are freed before the call returns.  The resident m x n_struct
+ * block is copied on the device; only p x n_struct + (m+p) x r new numbers cross to it.
+ * -0.0 entries are stored as +0.0, as dzg_solver_create stores them. */
+int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext);
+/* The sizes of the LP the handle holds now (any of the three may be NULL). */
+int dzg_solver_dims(const dzg_solver *s, int64_t *m, int64_t *n, int64_t *n_struct);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
@@ -889,6 +943,19 @@ int64_t dzg_debug_live_lists(dzg_solver *s, int64_t *entries);
  * been executed yet (a run that stopped between BTRAN and the pivot, DZG_NEAR_TIE in a dual step's
  * ratio test), -1 if none; < -1 on error.  dzg_debug_live_lists counts that row as listed. */
 int64_t dzg_debug_rl_listed(dzg_solver *s);
+/* Test hooks (tests/test_gpu_extend.py): the dense matrix as the kernels read it.
+ * dzg_debug_matrix copies structural columns [col0, col1), m rows each, column-major into `out`
+ * (ld_out >= m) and returns 0.  dzg_debug_matrix_rows copies rows [row0, row1) of the row-major copy
+ * the row-wise pricing pass reads, n_struct entries each, row-major into `out` (ld_out >= n_struct)
+ * and returns the number of rows copied: 0 where that copy is not kept.  < 0 on error (CSC storage,
+ * a sharded solver, a range outside the matrix: DZG_E_ARG). */
+int dzg_debug_matrix(dzg_solver *s, int64_t col0, int64_t col1, double *out, int64_t ld_out);
+int64_t dzg_debug_matrix_rows(dzg_solver *s, int64_t row0, int64_t row1, double *out, int64_t ld_out);
+/* Test and measurement hook (tools/extend_bench.py): how the last dzg_solver_extend on this handle
+ * spent its time, in ms of host clock -- [0] the matrix re-laid on the device (the successor's
+ * allocation, the resident block copied, the new rows and columns uploaded, the row-major copy),
+ * [1] the refactorisation of B', [2] the restart state (x, z).  Zeros before the first call. */
+int dzg_debug_extend_ms(const dzg_solver *s, double ms[3]);
 /* Test hook (tests/test_gpu_inverse.py): rows [row0, row1) of the basis inverse a FAST solver keeps,
  * B^-1 = Binv0 - U W^T (dense) or its sparse-basis form, assembled on the host from device copies of
  * the buffers the kernels read.  Row i of `out` is basis position row0 + i, column r constraint row
