@@ -50,6 +50,7 @@ EXPORTS = [
     "dzg_solver_reoptimize",
     "dzg_solver_extend", "dzg_solver_dims", "dzg_debug_matrix", "dzg_debug_matrix_rows",
     "dzg_debug_extend_ms",
+    "dzg_solver_remove",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -162,6 +163,10 @@ class Reopt(C.Structure):
 class Extend(C.Structure):
     _fields_ = [("n_rows", C.c_int64), ("n_cols", C.c_int64), ("rows", C.c_void_p), ("ld_rows", C.c_int64),
                 ("rhs", C.c_void_p), ("cols", C.c_void_p), ("ld_cols", C.c_int64), ("c_cols", C.c_void_p)]
+
+
+class Remove(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("rows", C.c_void_p), ("n_cols", C.c_int64), ("cols", C.c_void_p)]
 
 
 class ModelRangingReq(C.Structure):
@@ -299,6 +304,7 @@ def lib() -> C.CDLL:
                                            C.c_int64, C.c_void_p]
         _lib.dzg_solver_reoptimize.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_solver_extend.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dzg_solver_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_solver_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_debug_matrix.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
         _lib.dzg_debug_matrix_rows.restype = C.c_int64
@@ -408,10 +414,11 @@ def check_reopt(rc: int, what: str) -> int:
 
 
 def check_extend(rc: int, what: str) -> int:
-    """check(), but a route that cannot grow its LP (the C call says so) is a NotImplementedError."""
+    """check(), but a route that cannot grow or shrink its LP (the C call says so) is a
+    NotImplementedError."""
     if rc < 0:
         msg = lib().dzg_last_error().decode()
-        if "extend is not supported" in msg:
+        if "extend is not supported" in msg or "remove is not supported" in msg:
             raise NotImplementedError(f"{what}: {msg}")
     return check(rc, what)
 

@@ -179,6 +179,84 @@ def extended_lp(lp: CoreLP, rows=None, rhs=None, cols=None, c_cols=None) -> Core
         xbar=None, zbar=None)
 
 
+def _remove_lists(m: int, ns: int, rows, cols):
+    """The two lists of a removal as boolean masks over [0, m) and [0, n_struct); ValueError for an
+    index out of range or listed twice, when nothing is given, and when no row or no column would stay."""
+    masks = []
+    for name, idx, size in (("rows", rows, m), ("cols", cols, ns)):
+        idx = np.zeros(0, np.int64) if idx is None else np.atleast_1d(np.asarray(idx))
+        if idx.ndim != 1 or (idx.size and idx.dtype.kind not in "iu"):
+            raise ValueError(f"remove: {name} is a list of integer indices")
+        idx = idx.astype(np.int64)
+        if ((idx < 0) | (idx >= size)).any():
+            raise ValueError(f"remove: an index of {name} is out of range [0, {size})")
+        if len(np.unique(idx)) != len(idx):
+            raise ValueError(f"remove: an index of {name} is listed twice")
+        mask = np.zeros(size, bool)
+        mask[idx] = True
+        masks.append(mask)
+    if not masks[0].any() and not masks[1].any():
+        raise ValueError("remove: give rows or cols")
+    if masks[0].all() or masks[1].all():
+        raise ValueError("remove: at least one row and one structural column must stay")
+    return masks
+
+
+def _codes(lp: CoreLP) -> np.ndarray:
+    """The column code of every variable: >= 0 a structural column, -1 - r the slack of row r."""
+    if lp.var_col is not None:
+        return i64(lp.var_col)
+    return np.concatenate([np.arange(lp.n_struct), -1 - np.arange(lp.n - lp.n_struct)]).astype(np.int64)
+
+
+def reduced_lp(lp: CoreLP, rows=None, cols=None):
+    """Host only: (the LP a handle that stands at `lp`'s basis holds after Solver.remove with the same
+    arguments, var_map, row_map) (dzg_solver_remove).  rows: constraint rows to drop, with their
+    slacks; cols: structural columns to drop, with their variables.  Only what is free may go, judged
+    by lp.basis: a row whose slack is basic, a column whose variable is nonbasic; ValueError otherwise,
+    and for everything else the C call refuses.  Survivors are compressed in ascending order of their
+    old index -- variables, rows and columns alike; var_col is explicit and rewritten to match
+    (structural: the new column, slack: -1 - new row); surviving basis and nonbasic positions keep
+    their relative order, x and z their entries.  var_map (n) and row_map (m) hold the new index, or
+    -1 for what was dropped.  The inverse of extended_lp: reduced_lp(extended_lp(lp, ...), its rows,
+    its columns) is `lp` (with var_col explicit) where the new slacks are still basic and the new
+    variables nonbasic."""
+    import dataclasses
+
+    if lp.a is None or lp.block is not None:
+        raise NotImplementedError("remove is not supported on CSC storage or sharded solvers")
+    m, ns, n = lp.m, lp.n_struct, lp.n
+    drop_row, drop_col = _remove_lists(m, ns, rows, cols)
+    codes = _codes(lp)
+    basis, nonbasis = i64(lp.basis), i64(lp.nonbasis)
+    cn, cb = codes[nonbasis], codes[basis]
+    bound = nonbasis[(cn < 0) & drop_row[np.maximum(-1 - cn, 0)]]
+    if len(bound):
+        raise ValueError(f"remove: row {-1 - codes[bound[0]]} is binding (its slack, variable {bound[0]}, "
+                         "is nonbasic)")
+    held = basis[(cb >= 0) & drop_col[np.maximum(cb, 0)]]
+    if len(held):
+        raise ValueError(f"remove: column {codes[held[0]]} is basic (variable {held[0]})")
+    row_map = np.where(drop_row, -1, np.cumsum(~drop_row) - 1).astype(np.int64)
+    col_map = np.where(drop_col, -1, np.cumsum(~drop_col) - 1).astype(np.int64)
+    to = np.where(codes >= 0, col_map[np.maximum(codes, 0)], row_map[np.maximum(-1 - codes, 0)])
+    keep = to >= 0
+    var_map = np.where(keep, np.cumsum(keep) - 1, -1).astype(np.int64)
+    kb, kn = keep[basis], keep[nonbasis]
+    a = np.asarray(lp.a, dtype=np.float64)
+    if drop_row.any():          # (one axis at a time, and only where something goes: whole rows copy fast)
+        a = a[~drop_row]
+    if drop_col.any():
+        a = a[:, ~drop_col]
+    a = np.ascontiguousarray(a)
+    out = dataclasses.replace(
+        lp, a=a, c=f64(lp.c)[keep].copy(),
+        var_col=np.where(codes >= 0, to, -1 - to)[keep].astype(np.int64),
+        basis=var_map[basis[kb]], nonbasis=var_map[nonbasis[kn]],
+        x=f64(lp.x)[kb].copy(), z=f64(lp.z)[kn].copy(), xbar=None, zbar=None)
+    return out, var_map, row_map
+
+
 @dataclass
 class CoreResult:
     status: str
@@ -483,6 +561,54 @@ class Solver:
                           ptr(cols_cm) if r else None, max(m + p, 1), ptr(c_cols) if r else None)
         _ffi.check_extend(_ffi.lib().dzg_solver_extend(self._h, C.byref(ext)), "dzg_solver_extend")
         self._lp = lp2
+
+    def _at_current_basis(self) -> CoreLP:
+        """The LP this solver holds with the lists and the state of the basis it stands at."""
+        import dataclasses
+
+        res = self.result(log=False)
+        return dataclasses.replace(self._lp, basis=res.basis, nonbasis=res.nonbasis, x=res.x, z=res.z,
+                                   xbar=None, zbar=None)
+
+    def removable(self) -> tuple[np.ndarray, np.ndarray]:
+        """(row_mask (m,), col_mask (n_struct,)) at the current basis: the rows whose slack is basic
+        and the structural columns whose variable is nonbasic -- what remove() takes."""
+        if self._lp.a is None or self._lp.block is not None:
+            raise NotImplementedError("remove is not supported on CSC storage or sharded solvers")
+        m, ns = self._lp.m, self._lp.n_struct
+        res = self.result(log=False)
+        codes = _codes(self._lp)
+        in_basis, out_of_basis = codes[res.basis], codes[res.nonbasis]
+        row_mask, col_mask = np.zeros(m, bool), np.zeros(ns, bool)
+        row_mask[-1 - in_basis[in_basis < 0]] = True
+        col_mask[out_of_basis[out_of_basis >= 0]] = True
+        return row_mask, col_mask
+
+    def remove(self, rows=None, cols=None) -> tuple[np.ndarray, np.ndarray]:
+        """dzg_solver_remove: drops constraint rows (with their slacks) and / or structural columns
+        (with their variables) from the LP this solver holds and recomputes the state of the reduced
+        basis as extend() does; run() then carries on from it.  Only what is free may go (see
+        removable()): a row whose slack is basic, a column whose variable is nonbasic -- an optimal
+        solver stays optimal and the next run() takes no pivot.  Survivors are renumbered in ascending
+        order of their old index (see reduced_lp, which is the LP this solver holds afterwards);
+        returns (var_map (old n,), row_map (old m,)): the new index, or -1 for what was dropped.  The
+        pivot count and log keep accumulating; the log's older entries keep the numbering of their
+        time.  The matrix is gathered on the GPU from the resident one, only the lists of survivors
+        are uploaded.  Allowed where extend() is; CSC and sharded solvers: NotImplementedError.
+        ValueError for what the C call refuses about the lists (a binding row, a basic column, an
+        index out of range or listed twice, nothing given, no row or column left).  All or nothing: a
+        call that raises leaves the solver as it was."""
+        if self._lp.a is None or self._lp.block is not None:
+            raise NotImplementedError("remove is not supported on CSC storage or sharded solvers")
+        drop_row, drop_col = _remove_lists(self._lp.m, self._lp.n_struct, rows, cols)
+        lp2, _, _ = reduced_lp(self._at_current_basis(), rows, cols)
+        r, c = np.flatnonzero(drop_row).astype(np.int64), np.flatnonzero(drop_col).astype(np.int64)
+        var_map, row_map = np.zeros(self._lp.n, np.int64), np.zeros(self._lp.m, np.int64)
+        rem = _ffi.Remove(len(r), ptr(r) if len(r) else None, len(c), ptr(c) if len(c) else None)
+        _ffi.check_extend(_ffi.lib().dzg_solver_remove(self._h, C.byref(rem), ptr(var_map), ptr(row_map)),
+                          "dzg_solver_remove")
+        self._lp = lp2
+        return var_map, row_map
 
     def dims(self) -> tuple[int, int, int]:
         """dzg_solver_dims: (m, n, n_struct) of the LP the solver holds now."""

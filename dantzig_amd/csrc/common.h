@@ -866,6 +866,12 @@ void dzg_launch_extend_restride(const double *src, long long lda, double *dst, l
 void dzg_launch_extend_rows(const double *rows, long long ldr, int p, int ns, double *A, long long lda, int row0,
                             hipStream_t st);
 
+// k_remove.hip: the matrix of a live solver shrunk on the device (dzg_solver_remove).  dst column j',
+// row i' = src column keep_col[j'], row keep_row[i']; both device lists ascending.  keep_row == nullptr:
+// all m rows are kept (mk == m), whole columns move 16 bytes a lane
+void dzg_launch_remove_gather(const double *src, long long lda, double *dst, long long ldn, int m,
+                              const int *keep_row, int mk, const int *keep_col, int nk, hipStream_t st);
+
 // k_sparse.hip
 void dzg_launch_sp_init(const DzgDev &d, int first, hipStream_t st);
 void dzg_launch_sp_ftran(const DzgDev &d, int need_kind, int nrz, hipStream_t st);

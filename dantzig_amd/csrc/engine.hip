@@ -379,21 +379,25 @@ extern "C" int dzg_solver_upload_columns(dzg_solver *s, int64_t col_begin, int64
     return 0;
 }
 
-// dzg_solver_extend: the successor's matrix comes from the device -- the resident block of `old`,
-// re-laid for the new leading dimension, and the rows and columns of `ext` (lp->a is NULL and is not a
-// request for CSC storage; lp->x is the right-hand side by row)
-struct ExtendSrc {
+// dzg_solver_extend, dzg_solver_remove: the successor's matrix comes from the device (lp->a is NULL and
+// is not a request for CSC storage; lp->x is the right-hand side by row).  With `ext`: the resident
+// block of `old`, re-laid for the new leading dimension, and the rows and columns of `ext`.  With
+// `keep_rows` / `keep_cols` (ascending; keep_rows NULL: every row): those rows and columns of the
+// resident block, gathered.
+struct SuccessorSrc {
     const dzg_solver *old;
     const dzg_extend *ext;
+    const std::vector<int> *keep_rows;
+    const std::vector<int> *keep_cols;
 };
-static int extend_fill_matrix(dzg_solver *s, const ExtendSrc &src);
+static int successor_fill_matrix(dzg_solver *s, const SuccessorSrc &src);
 
 static double ms_since(std::chrono::steady_clock::time_point t0)
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver **out, const ExtendSrc *src)
+static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver **out, const SuccessorSrc *src)
 {
     if (!out) return fail(DZG_E_ARG, "out is NULL");
     *out = nullptr;
@@ -563,7 +567,7 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
     s->A_alloc = A_alloc;
     s->cols_present = d.repl ? nloc : ns;
     if (src) {
-        TRY(extend_fill_matrix(s, *src));
+        TRY(successor_fill_matrix(s, *src));
     } else if (ndense > 0 && m > 0) {
         // the reference's CSC drops exact zeros (src/linalg.rs:261), so -0.0 entries act as +0.0
         bool has_negzero = false;
@@ -2967,8 +2971,10 @@ static int extend_finite(const char *name, const double *v, int64_t len, int64_t
 
 // The successor's matrix (zeroed, lda' x n_struct'): the resident block re-laid, the new rows transposed
 // in from a staging block, the new columns by the path of dzg_solver_upload_columns.
-static int extend_fill_matrix(dzg_solver *s, const ExtendSrc &src)
+static int remove_fill_matrix(dzg_solver *s, const SuccessorSrc &src);
+static int successor_fill_matrix(dzg_solver *s, const SuccessorSrc &src)
 {
+    if (!src.ext) return remove_fill_matrix(s, src);
     const dzg_solver *old = src.old;
     const dzg_extend *e = src.ext;
     const DzgDev &d = s->d;
@@ -2995,6 +3001,11 @@ static int extend_fill_matrix(dzg_solver *s, const ExtendSrc &src)
     return 0;
 }
 
+static int successor_begin(dzg_solver *s, const char *what, DzgCtl *h0, std::vector<int> &basis0,
+                           std::vector<int> &nonbasis0);
+static int successor_swap(dzg_solver *s, const dzg_lp &lp, const SuccessorSrc &src, const DzgCtl &h0,
+                          const char *what);
+
 extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
 {
     if (!s || !ext) return fail(DZG_E_ARG, "extend: NULL argument");
@@ -3016,23 +3027,11 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
     if (p > 0) TRY(extend_finite("rhs", ext->rhs, p, 1, p));
     if (r > 0) TRY(extend_finite("cols", ext->cols, m2, r, ext->ld_cols));
     if (r > 0) TRY(extend_finite("c_cols", ext->c_cols, r, 1, r));
-    const bool fast = s->numerics == DZG_NUMERICS_FAST;
-    if (fast && !s->rf_piv)
-        return fail(DZG_E_ARG, "extend: a FAST solver needs its refactorisation workspace: create it "
-                               "with opts.refactor_interval != 0");
-    HIP_OK(hipSetDevice(s->opts.device));
-    TRY(read_ctl(s));
-    const DzgCtl h0 = *s->h_ctl;
-    if (h0.status == DZG_SINGULAR || h0.status == DZG_PANIC || h0.status < 0 || h0.status > DZG_NEAR_TIE)
-        return fail(DZG_E_ARG, std::string("extend: the solver's status is ") + dzg_status_str(h0.status) +
-                                   ": its basis cannot be carried on from");
-    hipStream_t st = s->st;
+    DzgCtl h0;
+    std::vector<int> basis0, nonbasis0;
+    TRY(successor_begin(s, "extend", &h0, basis0, nonbasis0));
 
     // the extended LP on the host: everything but the matrix
-    std::vector<int> basis0((size_t)(m ? m : 1)), nonbasis0((size_t)(q ? q : 1));
-    if (m) HIP_OK(hipMemcpyAsync(basis0.data(), s->d.basis, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-    if (q) HIP_OK(hipMemcpyAsync(nonbasis0.data(), s->d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
     std::vector<int64_t> basis((size_t)(m2 ? m2 : 1)), nonbasis((size_t)(q2 ? q2 : 1)), var_col((size_t)(n2 ? n2 : 1));
     std::vector<double> c2((size_t)(n2 ? n2 : 1), 0.0), rhs2((size_t)(m2 ? m2 : 1), 0.0), z2((size_t)(q2 ? q2 : 1), 0.0);
     for (int64_t i = 0; i < m; ++i) basis[(size_t)i] = basis0[(size_t)i];
@@ -3058,12 +3057,46 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
     lp.constant = s->constant;
     lp.basis = basis.data(); lp.nonbasis = nonbasis.data();
     lp.x = rhs2.data(); lp.z = z2.data(); // (the right-hand side by row; the state is written below)
+    const SuccessorSrc src{s, ext, nullptr, nullptr};
+    return successor_swap(s, lp, src, h0, "extend");
+}
 
+// What dzg_solver_extend and dzg_solver_remove share.  successor_begin: the refusals that depend on the
+// handle's state, then its control block and its two lists on the host.  successor_swap: the LP `lp`
+// (everything but the matrix, which `src` names) built as a successor next to the live state, left in
+// restart_state's state with the counters and the log carried over, and swapped into the caller's
+// handle; any failure leaves `s` as it was.
+static int successor_begin(dzg_solver *s, const char *what, DzgCtl *h0, std::vector<int> &basis0,
+                           std::vector<int> &nonbasis0)
+{
+    const int64_t m = s->d.m, q = s->d.q;
+    if (s->numerics == DZG_NUMERICS_FAST && !s->rf_piv)
+        return fail(DZG_E_ARG, std::string(what) + ": a FAST solver needs its refactorisation workspace: "
+                                                   "create it with opts.refactor_interval != 0");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    *h0 = *s->h_ctl;
+    if (h0->status == DZG_SINGULAR || h0->status == DZG_PANIC || h0->status < 0 || h0->status > DZG_NEAR_TIE)
+        return fail(DZG_E_ARG, std::string(what) + ": the solver's status is " + dzg_status_str(h0->status) +
+                                   ": its basis cannot be carried on from");
+    hipStream_t st = s->st;
+    basis0.assign((size_t)(m ? m : 1), 0);
+    nonbasis0.assign((size_t)(q ? q : 1), 0);
+    if (m) HIP_OK(hipMemcpyAsync(basis0.data(), s->d.basis, sizeof(int) * m, hipMemcpyDeviceToHost, st));
+    if (q) HIP_OK(hipMemcpyAsync(nonbasis0.data(), s->d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    return 0;
+}
+
+static int successor_swap(dzg_solver *s, const dzg_lp &lp, const SuccessorSrc &src, const DzgCtl &h0,
+                          const char *what)
+{
+    const bool fast = s->numerics == DZG_NUMERICS_FAST;
+    hipStream_t st = s->st;
     // the successor, on the same stream with the same options and the numerics the handle runs in
     dzg_opts o = s->opts;
     o.stream = (void *)st;
     o.numerics = s->numerics;
-    const ExtendSrc src{s, ext};
     dzg_solver *t = nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     TRY(solver_create(&lp, &o, &t, &src));
@@ -3078,7 +3111,7 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
     }
     TRY(read_ctl(t));
     if (t->h_ctl->status != DZG_RUNNING)
-        return fail(DZG_E_DEVICE, "extend: the extended basis did not refactorise (singular block)");
+        return fail(DZG_E_DEVICE, std::string(what) + ": the new basis did not refactorise (singular block)");
     t->extend_ms[0] = ms_since(t0) - t->extend_ms[1];
     // what carries on: the pivot count and everything counted per pivot, the log
     DzgCtl *h = t->h_ctl;
@@ -3116,6 +3149,133 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
     t->own_stream = false;
     guard.t = nullptr;
     dzg_solver_destroy(t);
+    return 0;
+}
+
+// ---- rows and columns removed from a live LP, carried on from its basis (k_remove.hip) ----
+// The successor's matrix (zeroed, lda' x n_struct'): the kept rows and columns of the resident one,
+// gathered on the device; the two lists are all that is uploaded.
+static int remove_fill_matrix(dzg_solver *s, const SuccessorSrc &src)
+{
+    const dzg_solver *old = src.old;
+    const DzgDev &d = s->d;
+    const std::vector<int> *kr = src.keep_rows;
+    const std::vector<int> &kc = *src.keep_cols;
+    const size_t nr = kr ? kr->size() : 0, nc = kc.size();
+    if (d.m <= 0 || nc == 0) return 0;
+    hipStream_t st = s->st;
+    void *lists = nullptr;
+    const size_t bytes = sizeof(int) * (nr + nc);
+    if (hipMalloc(&lists, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(DZG_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes failed");
+    }
+    struct Free { void *p; ~Free() { hipFree(p); } } free_lists{lists};
+    int *d_cols = static_cast<int *>(lists), *d_rows = d_cols + nc;
+    HIP_OK(hipMemcpyAsync(d_cols, kc.data(), sizeof(int) * nc, hipMemcpyHostToDevice, st));
+    if (nr) HIP_OK(hipMemcpyAsync(d_rows, kr->data(), sizeof(int) * nr, hipMemcpyHostToDevice, st));
+    dzg_launch_remove_gather(old->A_alloc, old->d.lda, s->A_alloc, d.lda, old->d.m, kr ? d_rows : nullptr, d.m,
+                             d_cols, (int)nc, st);
+    HIP_OK(hipStreamSynchronize(st)); // (the lists go away)
+    return 0;
+}
+
+// `idx[0..count)` marked in `drop` (sized for the range); DZG_E_ARG for one outside it or listed twice
+static int remove_mark(const char *name, const int64_t *idx, int64_t count, std::vector<char> &drop)
+{
+    for (int64_t k = 0; k < count; ++k) {
+        const int64_t i = idx[k];
+        if (i < 0 || i >= (int64_t)drop.size())
+            return fail(DZG_E_ARG, std::string("remove: ") + name + "[" + std::to_string(k) + "] = " +
+                                       std::to_string(i) + " is out of range");
+        if (drop[(size_t)i])
+            return fail(DZG_E_ARG, std::string("remove: ") + name + "[" + std::to_string(k) + "] = " +
+                                       std::to_string(i) + " is listed twice");
+        drop[(size_t)i] = 1;
+    }
+    return 0;
+}
+
+extern "C" int dzg_solver_remove(dzg_solver *s, const dzg_remove *rem, int64_t *var_map, int64_t *row_map)
+{
+    if (!s || !rem) return fail(DZG_E_ARG, "remove: NULL argument");
+    const int64_t p = rem->n_rows, r = rem->n_cols;
+    if (p < 0 || r < 0) return fail(DZG_E_ARG, "remove: n_rows and n_cols must not be negative");
+    if (p == 0 && r == 0) return fail(DZG_E_ARG, "remove: nothing to remove (n_rows and n_cols are 0)");
+    if ((p > 0 && !rem->rows) || (r > 0 && !rem->cols))
+        return fail(DZG_E_ARG, "remove: a count > 0 needs its list (NULL argument)");
+    if (s->d.csc || s->d.world > 1)
+        return fail(DZG_E_ARG, "remove is not supported on CSC storage or sharded solvers");
+    const int64_t m = s->d.m, n = s->d.n, ns = s->d.ns, q = s->d.q;
+    std::vector<char> drop_row((size_t)m, 0), drop_col((size_t)ns, 0);
+    TRY(remove_mark("rows", rem->rows, p, drop_row));
+    TRY(remove_mark("cols", rem->cols, r, drop_col));
+    const int64_t m2 = m - p, n2 = n - p - r, ns2 = ns - r, q2 = q - r;
+    if (m2 < 1 || ns2 < 1)
+        return fail(DZG_E_ARG, "remove: at least one row and one structural column must stay");
+    DzgCtl h0;
+    std::vector<int> basis0, nonbasis0;
+    TRY(successor_begin(s, "remove", &h0, basis0, nonbasis0));
+
+    // what may go: a row whose slack is basic, a structural column whose variable is nonbasic
+    const std::vector<int> &code0 = s->var_col_host;
+    for (int64_t k = 0; k < q; ++k) {
+        const int v = nonbasis0[(size_t)k], code = code0[(size_t)v];
+        if (code < 0 && drop_row[(size_t)(-1 - code)])
+            return fail(DZG_E_ARG, "remove: row " + std::to_string(-1 - code) + " is binding (its slack, variable " +
+                                       std::to_string(v) + ", is nonbasic): dropping it needs a pivot first");
+    }
+    for (int64_t i = 0; i < m; ++i) {
+        const int v = basis0[(size_t)i], code = code0[(size_t)v];
+        if (code >= 0 && drop_col[(size_t)code])
+            return fail(DZG_E_ARG, "remove: column " + std::to_string(code) + " is basic (variable " +
+                                       std::to_string(v) + " at basis position " + std::to_string(i) +
+                                       "): dropping it needs a pivot first");
+    }
+
+    // the reduced LP on the host, everything but the matrix: survivors compressed in ascending order
+    std::vector<int> keep_rows, keep_cols;
+    std::vector<int64_t> new_row((size_t)m, -1), new_col((size_t)ns, -1), new_var((size_t)n, -1);
+    for (int64_t i = 0; i < m; ++i)
+        if (!drop_row[(size_t)i]) {
+            new_row[(size_t)i] = (int64_t)keep_rows.size();
+            keep_rows.push_back((int)i);
+        }
+    for (int64_t j = 0; j < ns; ++j)
+        if (!drop_col[(size_t)j]) {
+            new_col[(size_t)j] = (int64_t)keep_cols.size();
+            keep_cols.push_back((int)j);
+        }
+    std::vector<int64_t> basis, nonbasis, var_col;
+    std::vector<double> c2, rhs2((size_t)m2, 0.0), z2((size_t)(q2 ? q2 : 1), 0.0);
+    for (int64_t v = 0; v < n; ++v) {
+        const int code = code0[(size_t)v];
+        const int64_t to = code >= 0 ? new_col[(size_t)code] : new_row[(size_t)(-1 - code)];
+        if (to < 0) continue;
+        new_var[(size_t)v] = (int64_t)var_col.size();
+        var_col.push_back(code >= 0 ? to : -1 - to);
+        c2.push_back(s->c_host[(size_t)v]);
+    }
+    for (int64_t i = 0; i < m; ++i)
+        if (new_var[(size_t)basis0[(size_t)i]] >= 0) basis.push_back(new_var[(size_t)basis0[(size_t)i]]);
+    for (int64_t k = 0; k < q; ++k)
+        if (new_var[(size_t)nonbasis0[(size_t)k]] >= 0) nonbasis.push_back(new_var[(size_t)nonbasis0[(size_t)k]]);
+    if ((int64_t)var_col.size() != n2 || (int64_t)basis.size() != m2 || (int64_t)nonbasis.size() != q2)
+        return fail(DZG_E_ARG, "remove: the handle's lists do not partition its variables");
+    for (int64_t i = 0; i < m2; ++i) rhs2[(size_t)i] = s->x0_host[(size_t)keep_rows[(size_t)i]];
+    if (nonbasis.empty()) nonbasis.push_back(0); // (q' == 0: never read)
+    dzg_lp lp;
+    std::memset(&lp, 0, sizeof(lp));
+    lp.m = m2; lp.n = n2; lp.n_struct = ns2;
+    lp.var_col = var_col.data();
+    lp.c = c2.data();
+    lp.constant = s->constant;
+    lp.basis = basis.data(); lp.nonbasis = nonbasis.data();
+    lp.x = rhs2.data(); lp.z = z2.data(); // (the right-hand side by row; the state is written by the swap)
+    const SuccessorSrc src{s, nullptr, p > 0 ? &keep_rows : nullptr, &keep_cols};
+    TRY(successor_swap(s, lp, src, h0, "remove"));
+    if (var_map) std::copy(new_var.begin(), new_var.end(), var_map);
+    if (row_map) std::copy(new_row.begin(), new_row.end(), row_map);
     return 0;
 }
 

@@ -333,6 +333,10 @@ class Session:
     (core.Solver.reoptimize), without a new upload.  Changes accumulate.  add_constraints() appends
     constraints over the model's variables: the next solve() extends the live solver by their rows
     (core.Solver.extend: the resident matrix grows on the GPU) and carries on from the same basis.
+    remove_constraints() takes constraints away again: one that add_constraints put on the live solver
+    and that is slack at the current basis leaves it on the GPU (core.Solver.remove) and the solve
+    carries on from the same basis; any other removal -- a constraint of the original model, a
+    binding one -- makes the next solve() a cold rebuild from the slack basis (counted in `rebuilds`).
     Besides that only b and the objective may change: variable bounds, the coefficients of an existing
     row, new variables and integer variables are out of scope.
 
@@ -348,6 +352,8 @@ class Session:
         self._rhs: dict = {}   # id(constraint) -> the new b of its normal form
         self._added: list = []  # constraints added to a live solver, in the order of their rows
         self._extended = 0      # ... of which the solver holds this many already
+        self._removed: list = []  # constraints to take off the live solver at the next solve
+        self.rebuilds = 0         # cold rebuilds remove_constraints has caused
         self._opts = {**rs._options, **core_opts}
         self._opts.setdefault("refactor_interval", -1)  # (FAST: reserves what reoptimize needs)
         self._solver = None
@@ -384,11 +390,13 @@ class Session:
         below the rows the solver holds (the model's, then the bound rows, then earlier additions),
         and re-optimises from the last basis; solve(rhs={constraint: b}) works on them as on any
         other.  ValueError for a variable the model has not seen, for an integer variable and for a
-        constraint that is already part of the session; nothing is added then."""
+        constraint that is already part of the session; nothing is added then.  A constraint that
+        remove_constraints has taken away since the last solve() is simply kept."""
         batch = [constraints] if isinstance(constraints, Constraint) else constraints
         if not isinstance(batch, list) or not all(isinstance(c, Constraint) for c in batch):
             raise TypeError("add_constraints takes a Constraint or a list of Constraints")
-        known = {id(c) for c in self._constraints + self._added}
+        leaving = {id(c) for c in self._removed}
+        known = {id(c) for c in self._constraints + self._added} - leaving
         order = self._order if self._solver is not None else self._lowered()[2]
         seen = {v.id for v in order}
         for k, constraint in enumerate(batch):
@@ -403,8 +411,64 @@ class Session:
         if self._solver is None:
             self._constraints += batch
         else:
-            self._added += batch
+            back = {id(c) for c in batch} & leaving    # (still on the solver: the removal is called off)
+            self._removed = [c for c in self._removed if id(c) not in back]
+            self._added += [c for c in batch if id(c) not in back]
         return self
+
+    def remove_constraints(self, constraints) -> "Session":
+        """Remove one constraint or a list of constraints the session holds.  Before the first solve()
+        they simply leave the model.  After it, the next solve() drops them from the live solver on
+        the GPU (core.Solver.remove) and re-optimises from the same basis when every one of them was
+        added by add_constraints and every one of their rows has a basic slack at the current basis
+        (the constraint is not binding there); those rows sit below the model's, so no other index
+        moves.  In every other case -- a constraint of the original model, a binding one -- the
+        session closes its solver, lowers the model without the constraints and the next solve()
+        starts from the slack basis: the result is the same, the basis is lost; `rebuilds` counts
+        these and `pivots` shows what they cost.  A removed constraint may be added again later.
+        KeyError for a constraint the session does not hold (or one listed twice); nothing is removed
+        then."""
+        batch = [constraints] if isinstance(constraints, Constraint) else constraints
+        if not isinstance(batch, list) or not all(isinstance(c, Constraint) for c in batch):
+            raise TypeError("remove_constraints takes a Constraint or a list of Constraints")
+        held = {id(c) for c in self._constraints + self._added} - {id(c) for c in self._removed}
+        for k, constraint in enumerate(batch):
+            if id(constraint) not in held or any(constraint is c for c in batch[:k]):
+                raise KeyError("the constraint is not part of the session's model")
+        gone = {id(c) for c in batch}
+        if self._solver is None:
+            self._constraints = [c for c in self._constraints if id(c) not in gone]
+            for key in gone:
+                self._rhs.pop(key, None)
+        else:
+            self._removed += batch
+        return self
+
+    def _apply_removals(self) -> None:
+        """What remove_constraints left for the next solve: off the live solver if that is free,
+        else the solver goes and the model is lowered again without them."""
+        if not self._removed:
+            return
+        gone = {id(c) for c in self._removed}
+        self._removed = []
+        rows, at = [], self._form.m
+        for constraint in self._added[:self._extended]:   # the rows the solver holds below the form's
+            k = len(constraint.rust_inequalities())
+            if id(constraint) in gone:
+                rows += range(at, at + k)
+            at += k
+        original = any(id(c) in gone for c in self._constraints)
+        if not original and (not rows or bool(self._solver.removable()[0][rows].all())):
+            if rows:
+                self._solver.remove(rows=rows)
+            self._extended -= sum(id(c) in gone for c in self._added[:self._extended])
+            self._added = [c for c in self._added if id(c) not in gone]
+        else:
+            self.close()
+            self._constraints = [c for c in self._constraints if id(c) not in gone]
+            self.rebuilds += 1
+        for key in gone:
+            self._rhs.pop(key, None)
 
     def _rows_of(self, constraint, form, order) -> list:
         """The rows of `constraint` over the structural columns of `form` (the standard form of this
@@ -442,6 +506,7 @@ class Session:
         exceptions.UnboundedError / InfeasibleError like Optimize.solve; the session stays usable.
         ValueError if the change alters more of the standard form than b, c and the constant (an
         objective over a variable the model had not seen)."""
+        self._apply_removals()
         before = (self._objective, dict(self._rhs))
         self._change(objective, rhs)
         try:
@@ -495,6 +560,11 @@ class Session:
             self._iterations = 0  # (a later solve() starts a new solver from the slack basis)
             self._constraints += self._added  # (... of the whole model)
             self._added, self._extended = [], 0
+            gone = {id(c) for c in self._removed}
+            self._constraints = [c for c in self._constraints if id(c) not in gone]
+            for key in gone:   # (removals that were waiting for the next solve)
+                self._rhs.pop(key, None)
+            self._removed = []
 
     def __enter__(self):
         return self

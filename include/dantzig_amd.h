@@ -717,6 +717,55 @@ int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext);
 /* The sizes of the LP the handle holds now (any of the three may be NULL). */
 int dzg_solver_dims(const dzg_solver *s, int64_t *m, int64_t *n, int64_t *n_struct);
 
+/* ---- Rows and columns removed from a live LP, carried on from its basis (csrc/k_remove.hip) ---- */
+
+/* Constraint rows and structural columns to drop from the LP a live handle holds. */
+typedef struct {
+    int64_t n_rows;  const int64_t *rows;   /* constraint rows to drop, each in [0, m)           */
+    int64_t n_cols;  const int64_t *cols;   /* structural columns to drop, each in [0, n_struct) */
+} dzg_remove;
+
+/* Drops the listed rows together with their slack variables and the listed structural columns
+ * together with their variables, and leaves the handle in the state dzg_solver_extend leaves it in, on
+ * the reduced LP and the reduced basis B'.  Only what is free may go: a row whose slack is BASIC (its
+ * dual value is 0; what is left of B is still a basis) and a structural column whose variable is
+ * NONBASIC.  x on the surviving positions and every surviving z are then what they were, up to the
+ * rounding of their recomputation: an optimal handle stays optimal and dzg_solver_run ends without a
+ * pivot.
+ *   Numbering: survivors are compressed in ascending order of their old index -- variables, rows and
+ *   structural columns alike.  var_col is rewritten to match: a structural variable gets its new
+ *   column, a slack -1 - (its new row).  The handle holds an explicit var_col afterwards.  Surviving
+ *   basis positions keep their relative order, and so do the nonbasic positions.
+ *   Maps (each may be NULL): var_map has the old n entries and row_map the old m entries, the new
+ *   index or -1 for what was dropped.  They are written only when the call succeeds.
+ *   The pivot log is carried over unchanged: its older entries speak in the numbering (variables and
+ *   positions) of their time; compose the maps of the calls since to read them in today's.
+ *   State: x = B'^-1 rhs', z_k = a_{N'_k} . y - c'[N'_k] with y = B'^-T c'_{B'}, xbar = zbar = 1,
+ *   status DZG_RUNNING, no pivot in flight -- as dzg_solver_extend writes them: STRICT bit for bit the
+ *   reference's LU::solve and neg_t_dot on B', FAST from the refactorisation dzg_solver_create runs on
+ *   B' plus one step of iterative refinement.  The pivot count, the log, the margins, near_ties,
+ *   first_near_tie, min_margin, refactors, solve_ms and max_pivot_error carry on.  The handle keeps
+ *   its numerics, even if m' falls to auto_strict_rows or below.  Later calls speak about the reduced
+ *   LP (dzg_solver_dims reports its sizes).
+ *   Allowed in the states dzg_solver_extend allows, before the first run included (every row and
+ *   every structural column is removable then).
+ *   DZG_E_ARG, with the handle untouched: NULL `s` or `rem`, or a NULL list with a count > 0; both
+ *   counts 0; a negative count; an index out of range or listed twice; a row whose slack is nonbasic
+ *   (dzg_last_error says the row is binding and names it); a column whose variable is basic (named);
+ *   fewer than one row or one structural column left; CSC storage or a column- or row-sharded
+ *   solver ("remove is not supported on CSC storage or sharded solvers"); a FAST handle without its
+ *   refactorisation workspace (opts.refactor_interval == 0); status DZG_SINGULAR or DZG_PANIC.
+ * All or nothing: the reduced LP is built as a successor next to the live state, as in
+ * dzg_solver_extend, and takes its place only when everything has succeeded (DZG_E_NOMEM,
+ * DZG_E_DEVICE: the handle is exactly what it was).  Until the swap both matrices are resident.
+ * The successor's matrix is lda' x n_struct', lda' by dzg_solver_create's rule for m' (it may drop);
+ * it is gathered on the device from the resident one, only the two lists of survivors are uploaded.
+ * Out of scope: dropping a binding row or a basic column (that needs a forced pivot first: pivot the
+ * slack in or the column out, then call this); CSC storage and sharded solvers; rebuilding FAST's
+ * compact inverse without a refactorisation (B'^-1 is B^-1 with rows and columns struck out, but the
+ * call refactorises B'). */
+int dzg_solver_remove(dzg_solver *s, const dzg_remove *rem, int64_t *var_map, int64_t *row_map);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
