@@ -152,10 +152,25 @@ static int price_small_k(void)
     }();
     return v;
 }
+// CUs of the current device (the one the solver's stream runs on)
+static int price_cus(void)
+{
+    static const int v = [] {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 1)
+            n = 256;
+        return n;
+    }();
+    return v;
+}
 int dzg_price_small(const DzgDev &d, int kernel)
 {
+    // (16 bytes a lane: every row of the copy 16-byte aligned.  The engine's own copy is -- ldt a
+    // multiple of 4, the base from hipMalloc; any other would be priced by k_price_rows + its finish)
+    const bool aligned = (d.ldt & 1) == 0 && (reinterpret_cast<uintptr_t>(d.At) & 15) == 0;
     return d.cpos && d.vc && d.world <= 1 && !d.rs && dzg_price_rows_certain(d, kernel) && d.k_hint < price_small_k() &&
-           (d.ldt + PRS_TILE - 1) / PRS_TILE <= 4096;
+           (d.ldt + PRS_TILE - 1) / PRS_TILE <= 4096 && aligned;
 }
 int dzg_price_small_partials(const DzgDev &d) { return (int)((d.ldt + PRS_TILE - 1) / PRS_TILE); }
 
@@ -176,15 +191,22 @@ void dzg_launch_price_fast(const DzgDev &d, int kernel, hipStream_t st, int need
                            int small, unsigned long long *dbg)
 {
     if (small) { // (the caller asked dzg_price_small)
-        // (k < 127 for the whole batch: at most eight row groups, one per wave)
-        if (d.k_hint < 8 * DZG_PR_BATCH - 1)
-            hipLaunchKernelGGL(k_price_rows_small<false>, dim3(dzg_price_small_partials(d)), dim3(512), 0, st,
-                               d.ctl, d.rows_T, d.At, d.ldt, d.col1 - d.col0, d.drow, d.vc, d.cpos, d.q,
-                               d.nbcode, d.v, d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h, dbg);
+        const int tiles = dzg_price_small_partials(d);
+#define SMALL(VEC, NG, RPT)                                                                          \
+    hipLaunchKernelGGL((k_price_rows_small<VEC, NG, RPT>), dim3(tiles), dim3(512), 0, st, d.ctl, d.rows_T, \
+                       d.At, d.ldt, d.col1 - d.col0, d.drow, d.vc, d.m, d.cpos, d.q, d.nbcode, d.v, d.dz, d.z, \
+                       d.zbar, d.rz_r, d.rz_k, d.rz_h, dbg)
+        // (k < 127 for the whole batch: at most eight row groups.  With more tiles than two workgroups
+        // per CU hold at once -- config 5 has 1 024 -- the form that fits four per CU: 21 180 it/s
+        // against 16 780 without it, profiles/price_small_one_trip.txt)
+        if (d.k_hint < 8 * DZG_PR_BATCH - 1 && tiles > 2 * price_cus())
+            SMALL(1, 1, 8);
+        // (k < 255 for the whole batch: at most sixteen row groups, one per half-wave)
+        else if (d.k_hint < 16 * DZG_PR_BATCH - 1)
+            SMALL(2, 1, 16);
         else
-            hipLaunchKernelGGL(k_price_rows_small<true>, dim3(dzg_price_small_partials(d)), dim3(512), 0, st,
-                               d.ctl, d.rows_T, d.At, d.ldt, d.col1 - d.col0, d.drow, d.vc, d.cpos, d.q,
-                               d.nbcode, d.v, d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h, dbg);
+            SMALL(2, 2, 16);
+#undef SMALL
         return;
     }
     if (d.csc) {

@@ -983,62 +983,100 @@ __global__ __launch_bounds__(256) void k_price_rows(
 // k_price_rows_small: the row-wise pass AND its finishing step in one launch, for the first few
 // hundred pivots of a solve (k + 1 <= PRS_ROWS for the whole batch: the host's bound, dzg_price_small).
 // A workgroup of 512 threads owns a tile of 64 consecutive COLUMNS of the row-major copy (512
-// contiguous bytes per row: a wave's load is one coalesced segment); wave w adds the row groups
-// g = w, w + 8, ... (group g = rows c = g, g + G, ... ascending, G as in k_price_rows) into LDS,
-// wave 0 then adds a column's G partial sums in group order -- exactly k_price_rows +
-// k_price_rows_finish's sums, bit for bit -- and, knowing where each column sits among the nonbasic
-// positions (cpos, kept by the pivot's books), writes dz and forms the z-side ratio candidates.
-// Unit columns and the candidates' per-workgroup reduction as in the finishing launch.  No partial
-// sums in memory, no second launch, nothing for k_chain_post to fold: three dependent trips
-// (control block | row list, coefficients, positions | rows, z, zbar).
+// contiguous bytes per row).  The workgroup has 8 * VEC group SLOTS of 64 / VEC lanes: a lane owns
+// VEC adjacent columns (VEC = 2: 16-byte loads, a half-wave per slot), slot s adds the row groups
+// g = s, s + 8 VEC, ... (group g = rows c = g, g + G, ... ascending, G as in k_price_rows: never more
+// than PR_BATCH = 16 rows for k + 1 <= 512) and leaves a column's partial sum in LDS; wave 0 then adds
+// a column's G partial sums in group order -- exactly k_price_rows + k_price_rows_finish's sums, bit
+// for bit -- and, knowing where each column sits among the nonbasic positions (cpos, kept by the
+// pivot's books), writes dz and forms the z-side ratio candidates.  Unit columns and the candidates'
+// per-workgroup reduction as in the finishing launch.  No partial sums in memory, no second launch,
+// nothing for k_chain_post to fold: TWO dependent trips (control block, row list, coefficients,
+// positions | rows, z, zbar).
 // grid = ceil(ldt / 64) workgroups = its count of ratio partials.
-// ---------------------------------------------------------------------------------
-// WIDE: the loads of a wave's four groups leave together (G > 8: k >= 128); otherwise one group
-// per wave and fewer registers (four workgroups per CU instead of two: config 5 has 1 024 tiles).
+//
+// The row list does not wait for the control block: thread t fetches drow[t] and vc[t] beside it
+// (k + 1 <= 512 = the workgroup's threads) and leaves the row's offset and the coefficient in LDS.
+// The rows stage then has NO operand on the issue path but registers: a lane reads the offsets of
+// its slot's entries in one batch of unconditional LDS reads, waits for them ONCE, and the row loads
+// of NG groups x RPT rows leave back to back -- an entry that does not exist re-reads row 0 and is
+// dropped by a select, so there is no branch, no LDS read and no wait between the first and the last
+// of them.  The coefficients are read behind the rows (they are not needed before the first fma) and
+// the sums are one straight run of fma in ascending c.
+// (Read from LDS entry by entry, every load and every fma sat behind an LDS round trip and an
+// exec-masked block of its own, twice over for more than 8 rows a group: profiles/price_small_one_trip.txt.)
+//   <2, 1, 16>  G <= 16 for the whole batch (k_hint < 255): one trip, every half-wave at most one group
+//   <2, 2, 16>  beyond: a half-wave's two groups (g, g + 16) leave together, still one trip
+//   <1, 1, 8>   more tiles than two workgroups per CU can cover at once and G <= 8: 8-byte loads, a
+//               wave per slot, two trips of 8 rows -- 63 registers, four workgroups per CU
+// (16-byte loads need the rows 16-byte aligned: dzg_price_small asks for that.  The 8-byte form with
+// all 16 rows in flight, <1, 2, 16>, priced the benchmark no faster than the kernel before it and is
+// not built: profiles/price_small_one_trip.txt.)
 // The control block is read as ONE snapshot (scalar loads that all leave before the first is waited
 // for; read field by field behind the early exits they sit on four cache lines and cost a trip
 // each), and the leaving variable's code comes with it (k_chain_pre publishes ctl->leave_code)
 // instead of a dependent load of bcode[leave_pos].
+// A launch the host's bound should have kept away (k beyond the rule or the cap while the solve is
+// running) stops the solve with DZG_PANIC instead of leaving k_chain_post a stale dz.
 // dbg != nullptr (DZG_CHAIN_DEBUG=1): the stage clocks of workgroup 0, slot 4 (ChainStamps):
-// control block | row list | rows | finish.
+// control block | row list (into LDS, the barrier) | rows | finish.
 #define PRS_TILE 64
 #define PRS_ROWS 512
 #define PRS_STAMP_SLOT 4
-template <bool WIDE>
-__global__ __launch_bounds__(512) void k_price_rows_small(
-    const DzgCtl *__restrict__ ctl, int rows_T, const double *__restrict__ At, long long ldt, int ncols,
-    const int *__restrict__ drow, const double *__restrict__ vc,
+// (waves per SIMD asked of the compiler: 8 = four workgroups per CU for <1, 1, 8>; else whatever a
+// workgroup needs)
+template <int VEC, int NG, int RPT>
+__global__ __launch_bounds__(512, (RPT < PR_BATCH ? 8 : 2)) void k_price_rows_small(
+    DzgCtl *__restrict__ ctl, int rows_T, const double *__restrict__ At, long long ldt, int ncols,
+    const int *__restrict__ drow, const double *__restrict__ vc, int m,
     const int *__restrict__ cpos, int q, const int *__restrict__ nbcode, const double *__restrict__ v,
     double *__restrict__ dz, const double *__restrict__ z, const double *__restrict__ zbar,
     double *__restrict__ rz_r, int *__restrict__ rz_k, double *__restrict__ rz_h,
     unsigned long long *dbg)
 {
+    constexpr int LPG = 64 / VEC; // lanes of a group slot
+    constexpr int NS = 512 / LPG; // group slots of the workgroup
+    static_assert(VEC == 1 || VEC == 2, "8- or 16-byte loads");
+    static_assert(PR_BATCH % RPT == 0 && PR_GMAX * PR_BATCH >= PRS_ROWS, "a group has at most PR_BATCH rows");
     __shared__ long long s_off[PRS_ROWS];
     __shared__ double s_coef[PRS_ROWS];
-    __shared__ double s_part[PR_GMAX][PRS_TILE];
+    __shared__ __attribute__((aligned(16))) double s_part[PR_GMAX][PRS_TILE];
     ChainStamps ts;
     ts.start(dbg);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // first trip, side by side: the control block, this thread's unit-column position, this lane's
-    // column and where it sits
+    // column and where it sits, and entry `tid` of the row list with its coefficient (fetched before k
+    // is known: entries from k on are stale and never used; the lists have m entries)
     const int spos = blockIdx.x * 512 + tid;
     int scode = 0;
     if (spos < q) scode = nbcode[spos];
     const long long j = (long long)blockIdx.x * PRS_TILE + lane;
     int pos = -1;
     if (wave == 0 && j < ncols) pos = cpos[j];
+    const int li = tid < m ? tid : m - 1;
+    const int lrow = drow[li];
+    const double lcf = vc[li];
     const int status = ctl->status, k = ctl->ncompact, lp = ctl->leave_pos;
     const int lcode_c = ctl->leave_code;
     const double mu = ctl->mu, tau = ctl->tau;
     asm volatile("" ::"s"(status), "s"(k), "s"(lp), "s"(lcode_c), "s"(mu), "s"(tau)); // (one snapshot)
-    if (status != DZG_RUNNING || k >= rows_T || k >= PRS_ROWS) return;
-    ts.mark(PRS_STAMP_SLOT); // 0: control block
-    // second trip: the row list and its coefficients; z, zbar of this thread's positions
-    const int lcode = lp >= 0 ? lcode_c : 0; // < 0: a slack leaves, row -1 - lcode carries v = 1
-    if (tid < k) {
-        s_off[tid] = (long long)drow[tid] * ldt;
-        s_coef[tid] = vc[tid];
+    if (status != DZG_RUNNING) return;
+    if (k >= rows_T || k >= PRS_ROWS) {
+        if (blockIdx.x == 0 && tid == 0) ctl->status = DZG_PANIC;
+        return;
     }
+    ts.mark(PRS_STAMP_SLOT); // 0: control block
+    // the row list as offsets into the copy, through LDS: entry c < k is row drow[c] with vc[c], entry k the
+    // leaving slack's own row with 1.0 (nothing is in flight at the barrier: it waits for no load)
+    const int lcode = lp >= 0 ? lcode_c : 0; // < 0: a slack leaves, row -1 - lcode carries v = 1
+    {
+        const bool own = tid == k && lcode < 0;
+        s_off[tid] = (long long)(own ? -1 - lcode : lrow) * ldt;
+        s_coef[tid] = own ? 1.0 : lcf;
+    }
+    __syncthreads();
+    ts.mark(PRS_STAMP_SLOT); // 1: row list
+    // second trip: the rows of this tile; z, zbar of this thread's positions beside them
     double sv = 0.0, sz = 0.0, szb = 0.0, zc = 0.0, zbc = 0.0;
     if (scode < 0) {
         sv = v[-1 - scode];
@@ -1050,63 +1088,75 @@ __global__ __launch_bounds__(512) void k_price_rows_small(
         zbc = zbar[pos];
     }
     const int nrows = k + (lcode < 0 ? 1 : 0);
-    if (tid == k && lcode < 0) {
-        s_off[k] = (long long)(-1 - lcode) * ldt;
-        s_coef[k] = 1.0;
-    }
     int G = (k + 1 + PR_BATCH - 1) / PR_BATCH; // (as k_price_rows)
     G = G > PR_GMAX ? PR_GMAX : G;
-    __syncthreads();
-    ts.mark(PRS_STAMP_SLOT); // 1: row list
-    // third trip: the rows of this tile -- eight rows of each of the wave's (up to four) groups in
-    // flight per lane, so that a pass of k + 1 <= 512 rows is two trips whatever G is; a group's
-    // rows are still added in ascending order into the group's own accumulator
-    const double *col = At + (j < ldt ? j : 0);
-    if (WIDE) {
-        double acc[4] = {0.0, 0.0, 0.0, 0.0};
-        const int rpg = (nrows + G - 1) / G; // rows of the fullest group
-        for (int r0 = 0; r0 < rpg; r0 += 8) { // block-uniform
-            double vv[4][8];
+    const int slot = tid / LPG, h = tid % LPG;
+    const long long jc = (long long)blockIdx.x * PRS_TILE + h * VEC; // (ldt is even when VEC = 2)
+    const double *col = At + (jc < ldt ? jc : 0);
+    for (int g0 = slot; g0 < G; g0 += NS * NG) {
+        double acc[NG][VEC];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int g = wave + 8 * t; // wave-uniform
+        for (int t = 0; t < NG; ++t)
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = g + (r0 + u) * G;
-                    vv[t][u] = (g < G && c < nrows) ? __builtin_nontemporal_load(col + s_off[c]) : 0.0;
+            for (int e = 0; e < VEC; ++e) acc[t][e] = 0.0;
+        for (int r0 = 0; r0 < PR_BATCH; r0 += RPT) {
+            if (RPT < PR_BATCH && g0 + r0 * G >= nrows) break; // (groups ascend with t: none has a row left)
+            // entry (t, u): c = g + (r0 + u) G of group g = g0 + NS t; it exists when g < G and
+            // c < nrows (the LDS reads are unconditional: one that does not exist reads entry 0)
+#define PRS_ENTRY(T, U)                                                                              \
+    const int c = g0 + NS * (T) + (r0 + (U)) * G;                                                    \
+    const bool ok = g0 + NS * (T) < G && c < nrows
+            long long off[NG][RPT]; // one batch of LDS reads, waited for once
+#pragma unroll
+            for (int t = 0; t < NG; ++t)
+#pragma unroll
+                for (int u = 0; u < RPT; ++u) {
+                    PRS_ENTRY(t, u);
+                    off[t][u] = s_off[ok ? c : 0];
                 }
-            }
+            // the rows, all in flight; the coefficients behind them
+            double x[NG][RPT][VEC], cf[NG][RPT];
 #pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int g = wave + 8 * t;
+            for (int t = 0; t < NG; ++t)
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = g + (r0 + u) * G;
-                    if (g < G && c < nrows) acc[t] = fma(s_coef[c], vv[t][u], acc[t]);
+                for (int u = 0; u < RPT; ++u) {
+                    PRS_ENTRY(t, u);
+                    const double *src = col + (ok ? off[t][u] : 0);
+                    if constexpr (VEC == 2) {
+                        const double2_t w = __builtin_nontemporal_load(reinterpret_cast<const double2_t *>(src));
+                        x[t][u][0] = w.x;
+                        x[t][u][1] = w.y;
+                    } else {
+                        x[t][u][0] = __builtin_nontemporal_load(src);
+                    }
                 }
-            }
+            // (the scheduler otherwise holds back two of sixteen loads until the first sums are done,
+            // a second trip, and mixes the coefficients' LDS reads among the loads)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int t = 0; t < NG; ++t)
+#pragma unroll
+                for (int u = 0; u < RPT; ++u) {
+                    PRS_ENTRY(t, u);
+                    cf[t][u] = s_coef[ok ? c : 0];
+                }
+#pragma unroll
+            for (int t = 0; t < NG; ++t)
+#pragma unroll
+                for (int u = 0; u < RPT; ++u) {
+                    PRS_ENTRY(t, u);
+#pragma unroll
+                    for (int e = 0; e < VEC; ++e)
+                        acc[t][e] = ok ? fma(cf[t][u], x[t][u][e], acc[t][e]) : acc[t][e];
+                }
+#undef PRS_ENTRY
         }
 #pragma unroll
-        for (int t = 0; t < 4; ++t)
-            if (wave + 8 * t < G) s_part[wave + 8 * t][lane] = acc[t];
-    } else {
-        for (int g = wave; g < G; g += 8) { // wave-uniform
-            double acc = 0.0;
-            for (int c0 = g; c0 < nrows; c0 += 8 * G) {
-                double vv[8];
+        for (int t = 0; t < NG; ++t)
+            if (g0 + NS * t < G) {
 #pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = c0 + u * G;
-                    vv[u] = c < nrows ? __builtin_nontemporal_load(col + s_off[c]) : 0.0;
-                }
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    const int c = c0 + u * G;
-                    if (c < nrows) acc = fma(s_coef[c], vv[u], acc);
-                }
+                for (int e = 0; e < VEC; ++e) s_part[g0 + NS * t][h * VEC + e] = acc[t][e];
             }
-            s_part[g][lane] = acc;
-        }
     }
     __syncthreads();
     ts.mark(PRS_STAMP_SLOT); // 2: rows
