@@ -40,6 +40,7 @@ EXPORTS = [
     "dzg_core_solve_full_csc", "dzg_debug_live_lists", "dzg_debug_rl_listed",
     "dzg_debug_basis_inverse", "dzg_batch_solve", "dzg_model_solve_batch", "dzg_mip_opts_default",
     "dzg_mip_solve", "dzg_mip_last_warm_stats", "dzg_debug_cand_reduce", "dzg_debug_chain_instance",
+    "dzg_debug_chain_price_counts", "dzg_debug_wk_mismatch", "dzg_debug_chain_price_rule",
     "dzg_solver_duals", "dzg_batch_solve_duals", "dzg_model_solve_duals",
     "dzg_model_solve_batch_duals", "dzg_model_map_duals",
     "dzg_solver_ranging", "dzg_batch_solve_ranging", "dzg_model_solve_ranging",
@@ -272,6 +273,11 @@ def lib() -> C.CDLL:
                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_debug_chain_instance.restype = C.c_int
         _lib.dzg_debug_chain_instance.argtypes = [C.c_int32] * 7
+        _lib.dzg_debug_chain_price_counts.argtypes = [C.c_void_p, C.c_void_p]
+        _lib.dzg_debug_wk_mismatch.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        _lib.dzg_debug_chain_price_rule.restype = C.c_int
+        _lib.dzg_debug_chain_price_rule.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64,
+                                                    C.c_int32, C.c_int32]
         _lib.dzg_batch_solve.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
         _lib.dzg_model_solve_batch.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.dzg_batch_solve_fast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,

@@ -650,6 +650,22 @@ class Solver:
                    "dzg_debug_basis_inverse")
         return out, dict(k=int(info[0]), neta=int(info[1]), rows=(int(info[2]), int(info[3])))
 
+    def debug_chain_price_counts(self) -> tuple[int, int]:
+        """Test hook (dzg_debug_chain_price_counts): chain iterations enqueued with the small-k pricing
+        pass in k_chain_pre's tail (two launches a pivot), and with the pass as a launch of its own."""
+        counts = np.zeros(2, np.int64)
+        _ffi.check(_ffi.lib().dzg_debug_chain_price_counts(self._h, ptr(counts)), "dzg_debug_chain_price_counts")
+        return int(counts[0]), int(counts[1])
+
+    def debug_wk_mismatch(self, clear_valid: bool = False) -> tuple[int, bool]:
+        """Test hook (dzg_debug_wk_mismatch): entries of the kept compact copy of the eta rows that differ
+        bitwise from a fresh gather, and whether the host held the copy valid; clear_valid: the next chain
+        batch gathers it again."""
+        info = np.zeros(2, np.int64)
+        _ffi.check(_ffi.lib().dzg_debug_wk_mismatch(self._h, int(bool(clear_valid)), ptr(info)),
+                   "dzg_debug_wk_mismatch")
+        return int(info[0]), bool(info[1])
+
     def close(self) -> None:
         if self._h:
             _ffi.lib().dzg_solver_destroy(self._h)

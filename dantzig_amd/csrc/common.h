@@ -732,13 +732,23 @@ struct DzgDev {
     // opts.shard_rows (k_rowshard.hip): this rank owns the rows [rs_r0, rs_r1) of x, xbar, dx, Binv0
     // and U; rs == 0: all of them (rs_r0 = 0, rs_r1 = m)
     int rs, rs_r0, rs_r1;
+    int fold_k;          // k_chain_post finishes the row-wise pricing pass itself while k stays below
+                         // this (default: always; DZG_CHAIN_FOLD_K is the A/B switch)
     long long rs_mcol;   // doubles of a record's column section (0: the matrix is replicated)
     int ftran_variant;   // how FTRAN loads the rows of Binv0 (fast_gemv_row_head<.., VAR>): >= 0 forced
                          // (DZG_FTRAN_VARIANT), -1: nontemporal from k = ftran_nt_k on, plain below
     int ftran_nt_k;      // 8 m k bytes of inverse beyond 1.5 x the 256-MB Infinity Cache
-    int fold_k;          // k_chain_post finishes the row-wise pricing pass itself while k stays below
-                         // this (default: always; DZG_CHAIN_FOLD_K is the A/B switch)
+    double *wk;          // [DZG_RMAX][ldw] Wc's gather KEPT CURRENT from pivot to pivot by the chain kernels:
+                         // at every kernel boundary of a chain batch wk[t][c] == W[t][drow[c]] bit for bit
+                         // (t < neta, c < k), so that every workgroup of k_chain_pre can form all of BTRAN's
+                         // compact row itself and price its tile (k_chain.hip, PRICE).  NULL: not kept -- the host
+                         // sets it per batch, only where the batch can price in the tail; the kernels then neither
+                         // store nor renumber.  No padding, nothing beyond k is defined.
 };
+// The struct is a kernel argument by value.  d.wk took the eight bytes that fold_k and the padding behind it
+// held at the struct's end (fold_k went into the hole behind rs_r1): every other member is where it was and the
+// argument segment of every kernel is as long as it was.  Eight bytes more, with nothing else changed, cost the
+// 32768 x 65536 workload 0.8 % (profiles/price_in_pre.txt, job F): measure that workload when the struct grows.
 
 #ifdef __HIPCC__
 // column of the entering variable: the local matrix (single GPU) or the winner's exchange
@@ -829,8 +839,18 @@ enum {
     DZG_CHAIN_P4_WIDE = 3,   // four passes, both lane widths
 };
 // instances != 0: the launcher may choose an instantiation (one GPU, a refreshed d.k_hint); 0: generic
+// price != 0 (the caller asked dzg_chain_price_fused): the launch prices the small-k rows in its tail
 void dzg_launch_chain_pre(const DzgDev &d, int grid, unsigned long long *bar,
-                          unsigned long long *dbg, const double *xrecv, hipStream_t st, int instances = 0);
+                          unsigned long long *dbg, const double *xrecv, hipStream_t st, int instances = 0,
+                          int price = 0);
+// The host's rule for pricing in k_chain_pre's tail (k_chain.hip): `small` = dzg_price_small holds for the
+// batch, `timed` = this slot's pricing pass is being timed on its own.  Pure host code.
+int dzg_chain_price_rule(int m, int grid, int k_hint, int tiles, long long q, int small, int timed);
+int dzg_chain_price_fused(const DzgDev &d, int grid, int small, int timed);
+int dzg_chain_keeps_wk(const DzgDev &d, int grid, int small); // the batch may run with d.wk set
+// wk := the gather of W as it stands (any neta): what a chain batch that wants the fused form
+// launches when no copy is kept (d.wk is NULL); dst != nullptr: into that buffer instead
+void dzg_launch_gather_wk(const DzgDev &d, double *dst, hipStream_t st);
 void dzg_launch_chain_post(const DzgDev &d, int grid, unsigned long long *bar,
                            unsigned long long *dbg, int only_partials, int nrz, const double *xrecv,
                            hipStream_t st, int fold = 0, int price_small = 0, int instances = 0);

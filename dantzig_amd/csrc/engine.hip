@@ -151,6 +151,14 @@ struct dzg_solver {
     bool batch_chain = false;                // the batch in flight runs the chain
     bool chain_fold = true;                  // k_chain_post finishes the row-wise pricing pass itself
     bool chain_instances = true;             // the chain launchers choose among the kernels' instantiations
+    // pricing in k_chain_pre's tail (k_chain.hip, PRICE): DZG_CHAIN_PRICE_FUSED=0, read once at creation,
+    // turns it off for A/B runs.  wk_buf: the memory of the kept compact copy of the eta rows.  d.wk is
+    // EITHER wk_buf -- the copy is the gather of W as the device holds it, and the chain kernels keep it
+    // so -- OR NULL: no copy is kept (set by run_fast's gather before a batch that can price in the tail,
+    // cleared for every other batch and wherever W, drow or neta change outside the chain)
+    bool chain_price_fused = true;
+    double *wk_buf = nullptr;
+    int64_t chain_fused = 0, chain_unfused = 0; // chain iterations enqueued in two / in three launches
                                              // (DZG_CHAIN_INSTANCES=0, the A/B switch: generic always)
                                              // (DZG_CHAIN_NO_FOLD=1 at creation: the separate launch)
     int64_t chain_fallbacks = 0;             // barrier failures recovered from (chain_recover)
@@ -866,6 +874,14 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
                 if (d.rows_T < 1) { d.At = nullptr; d.vc = nullptr; }
             }
         }
+        // the eta rows in compact coordinates, kept current by the chain kernels: only where the fused
+        // small-k pass can ever run (dzg_price_small) behind a chain
+        if (s->chain_bar && s->chain_grid > 0 && !d.spb && d.At && d.vc && d.cpos && d.world <= 1 && !d.rs &&
+            dzg_price_small_partials(d) <= s->chain_grid) {
+            TRY(dev_alloc(s, &s->wk_buf, (size_t)d.ldw * DZG_RMAX));
+            HIP_OK(hipMemsetAsync(s->wk_buf, 0, sizeof(double) * (size_t)d.ldw * DZG_RMAX, s->st));
+            if (const char *pf = std::getenv("DZG_CHAIN_PRICE_FUSED")) s->chain_price_fused = pf[0] != '0';
+        }
         dzg_launch_fast_init(d, s->st);
         if (d.spb) {
             dzg_launch_sp_init(d, 1, s->st);
@@ -1001,17 +1017,23 @@ static void enqueue_chain_iteration(dzg_solver *s, int slot)
     hipStream_t st = s->st;
     Prof pf{s, slot};
     const int pk = price_kernel_for(s);
-    pf.begin(DZG_K_FTRAN);
-    dzg_launch_chain_pre(d, s->chain_grid, s->chain_bar, s->chain_dbg, nullptr, st, // status, primal FTRAN + ratio, BTRAN row
-                         s->chain_instances);
-    pf.end(DZG_K_FTRAN);
     // k below ~480 for the whole batch: one fused kernel prices row-wise AND finishes (dz, ratio
     // candidates) per column tile -- no partial sums in memory, nothing to fold.  Otherwise, while
     // the batch prices row-wise for certain, k_chain_post finishes the pass itself (FOLD)
     const int small = dzg_price_small(d, pk);
     const int fold = !small && s->chain_fold && dzg_price_rows_certain(d, pk);
+    // ... and where every tile has a chain workgroup, that pass is the TAIL of k_chain_pre: two launches
+    // a pivot.  A slot whose pricing pass is timed keeps the three launches, so that its events
+    // bracket k_price_rows_small alone (run_fast has gathered d.wk where the batch can want it).
+    const int fused = s->chain_price_fused &&
+                      dzg_chain_price_fused(d, s->chain_grid, small, prof_on(s, DZG_K_PRICE, slot));
+    (fused ? s->chain_fused : s->chain_unfused) += 1;
+    pf.begin(DZG_K_FTRAN);
+    dzg_launch_chain_pre(d, s->chain_grid, s->chain_bar, s->chain_dbg, nullptr, st, // status, primal FTRAN + ratio, BTRAN row
+                         s->chain_instances, fused);
+    pf.end(DZG_K_FTRAN);
     pf.begin(DZG_K_PRICE);
-    dzg_launch_price_fast(d, pk, st, -1, fold, small, small ? s->chain_dbg : nullptr);
+    if (!fused) dzg_launch_price_fast(d, pk, st, -1, fold, small, small ? s->chain_dbg : nullptr);
     pf.end(DZG_K_PRICE);
     pf.begin(DZG_K_UPDATE);
     dzg_launch_chain_post(d, s->chain_grid, s->chain_bar, s->chain_dbg, 0,
@@ -1264,6 +1286,7 @@ static int measure_drift(dzg_solver *s)
 
 static int refactor_now(dzg_solver *s, bool at_end)
 {
+    s->d.wk = nullptr; // (a new Binv0, a new compact numbering, an empty eta file: gathered afresh)
     if (partitioned(s) && s->in_lockstep)
         return fail(DZG_E_ARG, "refactor: the lockstep loop refactorises its ranks together");
     int counts[2];
@@ -1430,6 +1453,7 @@ static int chain_recover(dzg_solver *s)
 {
     DzgCtl *h = s->h_ctl;
     s->chain_fallbacks += 1;
+    s->d.wk = nullptr; // (a launch that ended at a barrier may have stored a row of the copy and not pivoted)
     s->chain_retry_iter = s->chain_fallbacks >= 3 ? std::numeric_limits<long long>::max()
                                                   : h->iter + 64ll * s->opts.poll_interval;
     HIP_OK(hipMemsetAsync(s->chain_bar, 0, sizeof(unsigned long long) * DZG_CHAIN_BAR_WORDS, s->st));
@@ -1484,10 +1508,23 @@ static int run_fast(dzg_solver *s)
                              (long long)s->h_ctl->ncompact + batch <= s->chain_kcap;
             s->d.k_hint = k_bound;
             s->d.k_lo_hint = k_low;
-            if (s->batch_chain)
+            if (s->batch_chain) {
+                // a batch that can price in k_chain_pre's tail needs d.wk current: gathered here when
+                // something outside the chain has changed W, drow or neta since it last was
+                // (a batch that cannot -- k beyond the cap, more tiles than workgroups, the switch off --
+                // runs with d.wk = NULL: its kernels neither store nor renumber, and no copy is kept)
+                if (!(s->wk_buf && s->chain_price_fused && s->chain_instances &&
+                      dzg_chain_keeps_wk(s->d, s->chain_grid, dzg_price_small(s->d, price_kernel_for(s))))) {
+                    s->d.wk = nullptr;
+                } else if (!s->d.wk) {
+                    dzg_launch_gather_wk(s->d, s->wk_buf, s->st);
+                    s->d.wk = s->wk_buf;
+                }
                 for (int b = 0; b < batch; ++b) enqueue_chain_iteration(s, b);
-            else
+            } else {
+                s->d.wk = nullptr; // (the seven launches append to W and renumber without the copy)
                 for (int b = 0; b < batch; ++b) enqueue_fast_iteration(s, b);
+            }
             s->d.k_hint = s->d.k_lo_hint = 0;
         }
         s->since_refactor += batch;
@@ -1697,6 +1734,7 @@ extern "C" int dzg_shard_phase2(dzg_solver *s, const double *recv_dev, double *s
 extern "C" int dzg_shard_phase3(dzg_solver *s, const double *recv_dev)
 {
     if (!s || !recv_dev || s->numerics != DZG_NUMERICS_FAST) return fail(DZG_E_ARG, "phase3");
+    s->d.wk = nullptr; // (the phases pivot without the kept compact copy of the eta rows)
     const DzgDev &d = s->d;
     hipStream_t st = s->st;
     phase_stamp(s, DZG_K_UPDATE, 0);
@@ -3722,4 +3760,47 @@ extern "C" int dzg_kernel_second_pivot(int64_t len, double mu, const double *y, 
     if (dzg_device_count() <= 0) return fail(DZG_E_DEVICE, "no HIP device visible");
     HIP_OK(hipSetDevice(device));
     return dzg_run_second_pivot(len, mu, y, ybar, dy, pos_out);
+}
+
+// ---- test hooks of the pricing tail of k_chain_pre (include/dantzig_amd.h) ----------------------
+extern "C" int dzg_debug_chain_price_counts(dzg_solver *s, int64_t counts[2])
+{
+    if (!s || !counts) return fail(DZG_E_ARG, "NULL argument");
+    counts[0] = s->chain_fused;
+    counts[1] = s->chain_unfused;
+    return 0;
+}
+
+extern "C" int dzg_debug_chain_price_rule(int32_t m, int32_t grid, int32_t k_hint, int32_t tiles, int64_t q,
+                                          int32_t small, int32_t timed)
+{
+    return dzg_chain_price_rule(m, grid, k_hint, tiles, q, small, timed);
+}
+
+extern "C" int dzg_debug_wk_mismatch(dzg_solver *s, int32_t clear_valid, int64_t info[2])
+{
+    if (!s || !info) return fail(DZG_E_ARG, "NULL argument");
+    const DzgDev &d = s->d;
+    if (!s->wk_buf) return fail(DZG_E_ARG, "wk mismatch: this solver keeps no compact copy of the eta rows");
+    HIP_OK(hipSetDevice(s->opts.device));
+    TRY(read_ctl(s));
+    const int k = s->h_ctl->ncompact, neta = s->h_ctl->neta;
+    if (k < 0 || k > d.m || neta < 0 || neta > DZG_RMAX)
+        return fail(DZG_E_DEVICE, "wk mismatch: control block out of range");
+    info[1] = s->d.wk ? 1 : 0;
+    // a fresh gather of W into the flush's scratch (the flush gathers it again before it reads it)
+    dzg_launch_gather_wk(d, d.Wc, s->st);
+    const size_t n = (size_t)d.ldw * DZG_RMAX;
+    std::vector<double> kept(n), fresh(n);
+    HIP_OK(hipMemcpyAsync(kept.data(), s->wk_buf, sizeof(double) * n, hipMemcpyDeviceToHost, s->st));
+    HIP_OK(hipMemcpyAsync(fresh.data(), d.Wc, sizeof(double) * n, hipMemcpyDeviceToHost, s->st));
+    HIP_OK(hipStreamSynchronize(s->st));
+    HIP_OK(hipGetLastError());
+    int64_t bad = 0;
+    for (int t = 0; t < neta; ++t)
+        for (int c = 0; c < k; ++c)
+            bad += std::memcmp(&kept[(size_t)t * d.ldw + c], &fresh[(size_t)t * d.ldw + c], sizeof(double)) != 0;
+    info[0] = bad;
+    if (clear_valid) s->d.wk = nullptr;
+    return 0;
 }

@@ -1,7 +1,8 @@
 // k_chain.hip -- the FAST iteration of the dense inverse in THREE launches on one GPU:
 //
 //      k_chain_pre   status(); a primal step: beta, FTRAN, ratio test;   then BTRAN's row
-//      pricing       (k_price.hip, unchanged: the only kernel that touches the matrix)
+//      pricing       (k_price.hip: the only code that touches the matrix; while k is small it is the TAIL
+//                    of k_chain_pre -- PRICE below -- and the iteration is two launches)
 //      k_chain_post  a dual step: ratio test, beta, FTRAN;   the pivot's books;   the update
 //
 // The seven-launch form of the same iteration (k_fast.hip) pays a kernel boundary for every
@@ -45,6 +46,7 @@
 #include "common.h"
 #include "fast_decide.h"
 #include "fast_rows.h"
+#include "price_small.h"
 
 #include "chain_barrier.h"
 
@@ -411,12 +413,50 @@ __device__ __forceinline__ void chain_dot_tail(const DzgDev &d, int r0, int r1, 
 // SHARD (column sharding with the matrix replicated, one process per GPU): the z-side first pivot
 // comes from the merge of every rank's proposal (xrecv: the first exchange's records) -- all ranks
 // see the same records in the same order and apply the same rule, so they take the same decision.
-template <bool SHARD, int MAXP, bool NARROW>
+//
+// PRICE (one GPU, NARROW, one pass; 0: none, NG: the small-k row pass <2, NG, 16> of price_small.h in
+// this kernel's tail).  BTRAN's row is computed piecewise, each workgroup on its own rows, and the
+// pricing pass of every column tile needs all k + 1 compact entries of it: that is the only reason for
+// the kernel boundary in between.  But a compact entry depends on nothing this launch writes --
+// vc[c] = Binv0[p][c] - sum_t U[t][p] W[t][drow[c]], all left by earlier launches -- so every
+// workgroup forms all of vc[0..k) itself once p is known: compact column c on thread CHP_COL0 + c
+// (the rows sit on threads < CHP_COL0; k < 480 fills the workgroup exactly; no thread holds two eta
+// columns' registers), in the SAME trip as BTRAN's own loads, the eta rows from d.wk (common.h: W in
+// compact coordinates, contiguous, kept current by both chain kernels), with the owner's expression
+// and operands and therefore its bits.  Workgroup b then prices tile b as k_price_rows_small does:
+// row list and coefficients into LDS (the gathered column's buffer, free after FTRAN), one workgroup
+// barrier, the rows stage, the finish.  A unit column's v is its row's compact entry (a nonbasic
+// slack's row is a compact row by definition): s_coef[dslot[row]], no gather over v.  No barrier and
+// no launch is added; the owners still store v, vc and wk[neta] for k_chain_post and the other kernels.
+#define CHP_COL0 32
+// `d` of the running chain kernel, read again from the kernel-argument segment at the point of the
+// call, behind a barrier the compiler cannot hoist the loads across.  A stage that takes a dozen of
+// d's pointers from the by-value argument keeps them in scalar registers from the kernel's start; the
+// chain kernels sit at the scalar-register limit, and those pointers cost the stages before it 44-76
+// registers spilled through vector lanes and a microsecond (profiles/price_in_pre.txt).
+// ONLY VALID IN A KERNEL WHOSE FIRST ARGUMENT IS `const DzgDev d`, BY VALUE (offset 0 of the segment):
+// k_chain_pre below says so at its signature, and its PRICE tail checks one field of the copy against
+// the argument itself (ctl) and ends the solve with DZG_PANIC if they differ.
+typedef const __attribute__((address_space(4))) DzgDev ChainDevArg;
+__device__ __forceinline__ ChainDevArg *chain_dev_reloaded()
+{
+    ChainDevArg *kd = (ChainDevArg *)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(kd));
+    return kd;
+}
+template <bool SHARD, int MAXP, bool NARROW, int PRICE = 0>
+// (`d` MUST STAY THE FIRST ARGUMENT, BY VALUE: the PRICE tail reads it again through chain_dev_reloaded)
 __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsigned long long *bar,
                                                           unsigned long long *dbg,
                                                           const double *__restrict__ xrecv)
 {
-    __shared__ double s_ag[CH_AGCAP];
+    static_assert(PRICE == 0 || (!SHARD && NARROW && MAXP == 1 && PRICE <= 2), "the pricing tail: P1, narrow");
+    static_assert(CH_THREADS == 512 && CH_AGCAP >= 2 * PRS_ROWS + PR_GMAX * PRS_TILE, "the tail's LDS");
+    // the kept compact copy of the eta rows (d.wk) exists only in the one-pass narrow kernels: the host
+    // sets d.wk only for batches that run them (dzg_chain_keeps_wk); every other instantiation is the
+    // code it was without the copy
+    constexpr bool WK = !SHARD && NARROW && MAXP == 1;
+    __shared__ __attribute__((aligned(16))) double s_ag[CH_AGCAP];
     __shared__ double s_beta[R_], s_dx[CH_THREADS], s_up[R_];
     __shared__ ChainSlots s_c;
     ChainStamps ts;
@@ -446,6 +486,24 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
         x_i = d.x[row];
         xbar_i = d.xbar[row];
     }
+    // (PRICE) the tail's first touches: this thread's unit-column position with its z, zbar, this
+    // lane's column of the tile and where it sits, the row of this thread's compact column (fetched
+    // before k is known: entries from k on are stale and never used; the list has m entries)
+    const int tiles = PRICE ? (int)((d.ldt + PRS_TILE - 1) / PRS_TILE) : 0;
+    const int spos = (int)blockIdx.x * CH_THREADS + tid, cc = tid - CHP_COL0;
+    int scode = 0, pos = -1, lrow_c = 0;
+    double sz = 0.0, szb = 0.0;
+    const bool tile_on = PRICE != 0 && (int)blockIdx.x < tiles; // (block-uniform: this workgroup prices a tile)
+    if (tile_on) {
+        if (spos < d.q) {
+            scode = d.nbcode[spos];
+            sz = d.z[spos];
+            szb = d.zbar[spos];
+        }
+        const long long j = (long long)blockIdx.x * PRS_TILE + lane;
+        if (wave == 0 && j < d.col1 - d.col0) pos = d.cpos[j];
+        if (cc >= 0) lrow_c = d.drow[cc < m ? cc : m - 1];
+    }
     DzgCtl c = *ctl; // one snapshot; nothing the lead lane writes below is read from it
     if (c.status != DZG_RUNNING) return;
     unsigned long long gen = c.bar_gen;
@@ -472,6 +530,13 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
     ts.mark(slot); // 0: first touches + status
     // the host runs the seven launches -- and picks no NARROW kernel -- before this can happen
     if (k > CH_AGCAP || c.fp_count > 256 || (NARROW && k > 512)) {
+        if (lead) ctl->status = DZG_PANIC;
+        return;
+    }
+    // (PRICE: k_price_rows_small's guard, and what the tail's layout takes for granted: a thread per
+    // compact entry, a row per thread < CHP_COL0, every nonbasic position under a pricing workgroup)
+    if (PRICE != 0 && (k >= d.rows_T || k >= CH_THREADS - CHP_COL0 || r1 - r0 > CHP_COL0 ||
+                       tiles > nwg || (long long)tiles * CH_THREADS < d.q || !d.wk)) {
         if (lead) ctl->status = DZG_PANIC;
         return;
     }
@@ -580,17 +645,48 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
     }
     double up = 0.0, base = 0.0, w[R_];
     if (tid < R_ && tid < neta) up = d.U[(long long)tid * d.ldw + p];
-    if (has_row) {
-        if (dslot_i >= 0) base = d.binv[(long long)p * d.ldb + dslot_i];
-        fast_btran_eta_load(w, neta, d.W, d.ldw, row);
-    }
-    if (tid < R_) s_up[tid] = up;
-    __syncthreads();
-    if (has_row) {
-        if (dslot_i < 0) base = lcode == -1 - row ? 1.0 : 0.0;
-        const double vr = base - fast_btran_eta_fma(w, neta, s_up);
-        d.v[row] = vr;
-        if (dslot_i >= 0 && d.vc) d.vc[dslot_i] = vr; // (compact copy: the row-wise pricing pass's coefficients)
+    int sd = -1;
+    double zc = 0.0, zbc = 0.0, vr = 0.0;
+    if constexpr (PRICE == 0) {
+        if (has_row) {
+            if (dslot_i >= 0) base = d.binv[(long long)p * d.ldb + dslot_i];
+            fast_btran_eta_load(w, neta, d.W, d.ldw, row);
+        }
+        if (tid < R_) s_up[tid] = up;
+        __syncthreads();
+        if (has_row) {
+            if (dslot_i < 0) base = lcode == -1 - row ? 1.0 : 0.0;
+            vr = base - fast_btran_eta_fma(w, neta, s_up);
+            d.v[row] = vr;
+            if (dslot_i >= 0 && d.vc) d.vc[dslot_i] = vr; // (compact copy: the row-wise pricing pass's coefficients)
+            // (and eta row neta of the kept compact copy, which k_chain_post renumbers with the pivot)
+            if constexpr (WK)
+                if (dslot_i >= 0 && d.wk && neta < R_) d.wk[(long long)neta * d.ldw + dslot_i] = vr;
+        }
+    } else {
+        // in the same trip: this thread's compact column of row p and of the pending eta rows, the
+        // compact slot of this thread's slack position, z and zbar where this lane's column sits
+        const bool is_col = tile_on && cc >= 0 && cc < k; // (never a thread that has a row: r1 - r0 <= CHP_COL0)
+        if (scode < 0) sd = d.dslot[-1 - scode];
+        if (pos >= 0) {
+            zc = d.z[pos];
+            zbc = d.zbar[pos];
+        }
+        if (is_col) base = d.binv[(long long)p * d.ldb + cc];
+        if (has_row && dslot_i >= 0) base = d.binv[(long long)p * d.ldb + dslot_i];
+        if (has_row || is_col) // (ONE set of eta registers: the row's W, or the compact column's wk)
+            fast_btran_eta_load(w, neta, is_col ? d.wk : d.W, d.ldw, is_col ? cc : row);
+        if (tid < R_) s_up[tid] = up;
+        __syncthreads();
+        if (has_row || is_col) {
+            if (has_row && dslot_i < 0) base = lcode == -1 - row ? 1.0 : 0.0;
+            vr = base - fast_btran_eta_fma(w, neta, s_up);
+        }
+        if (has_row) {
+            d.v[row] = vr;
+            if (dslot_i >= 0 && d.vc) d.vc[dslot_i] = vr;
+            if (dslot_i >= 0 && neta < R_) d.wk[(long long)neta * d.ldw + dslot_i] = vr; // (as above)
+        }
     }
     if (lead) {
         ctl->xp = xp;
@@ -600,6 +696,37 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_pre(const DzgDev d, unsign
     }
     ts.mark(slot); // primal 7 / dual 1: BTRAN row
     ts.done(slot);
+    if constexpr (PRICE != 0) {
+        // ---- the pricing pass of tile blockIdx.x (k_price_rows_small from its row list on; its stage
+        // clocks, slot 4, under the stand-alone kernel's stage numbers: 1 list | 2 rows | 3 finish)
+        if ((int)blockIdx.x >= tiles) return; // (no tile, and no position: tiles * 512 >= q)
+        const auto *kd = chain_dev_reloaded(); // (`d` again, read here: see there)
+        if (kd->ctl != ctl) { // (the segment does not start with `d`: see chain_dev_reloaded)
+            if (lead) ctl->status = DZG_PANIC;
+            return;
+        }
+        const long long ldt = kd->ldt;
+        ts.stage = 1;
+        long long *s_off = reinterpret_cast<long long *>(s_ag);
+        double *s_coef = s_ag + PRS_ROWS;
+        double(*s_part)[PRS_TILE] = reinterpret_cast<double(*)[PRS_TILE]>(s_ag + 2 * PRS_ROWS);
+        if (cc >= 0) { // entry c < k: row drow[c] with vc[c]; entry k: the leaving slack's own row with 1.0
+            const bool own = cc == k && lcode < 0;
+            s_off[cc] = (long long)(own ? -1 - lcode : lrow_c) * ldt;
+            s_coef[cc] = own ? 1.0 : vr;
+        }
+        __syncthreads();
+        ts.mark(PRS_STAMP_SLOT); // 1: row list
+        const double sv = sd >= 0 && sd < k ? s_coef[sd] : 0.0; // v of this thread's slack's row
+        const int G = price_small_rows<2, PRICE, PR_BATCH>(kd->At, ldt, (int)blockIdx.x, k, lcode, s_off, s_coef,
+                                                           s_part);
+        __syncthreads();
+        ts.mark(PRS_STAMP_SLOT); // 2: rows
+        price_small_finish<false>(ts, G, s_part, pos, zc, zbc, scode, spos, sv, sz, szb, tiles, kd->q, kd->nbcode,
+                                  kd->v, kd->dz, kd->z, kd->zbar, mu, c.tau, kd->rz_r, kd->rz_k, kd->rz_h);
+        ts.mark(PRS_STAMP_SLOT); // 3: finish
+        ts.done(PRS_STAMP_SLOT);
+    }
 }
 
 // dz of ONE nonbasic position as the finishing launch of the row-wise pricing pass computes it
@@ -950,6 +1077,31 @@ __global__ __launch_bounds__(CH_THREADS) void k_chain_post(const DzgDev d, unsig
         }
         ts.mark(slot); // primal 1 / dual 5: step lengths
     }
+    // The kept compact copy of the eta rows (d.wk, common.h) is renumbered as the pivot renumbers the
+    // compact columns, by ONE wave, lane t for eta row t <= teta: not the books' wave of workgroup 0, not
+    // wave 0 (rows, columns, the reductions) and none that runs a beta item or row p.  An appending
+    // pivot: column k := W (v for the eta appended now) at the leaving slack's constraint row; a deleting
+    // one: the last column -- the appended one when both happen -- takes the deleted one's place.
+    // Loads and stores sit HERE, beside everybody's update: fetched with the kernel's first touches the
+    // operands stayed live through the whole kernel and cost every workgroup scalar-register spills
+    // (k_chain_post 12.85 -> 13.66 us, profiles/price_in_pre.txt).  Nothing else in the launch reads
+    // or writes wk; the books zero W at an ENTERING slack's row only, another row.
+    // Compiled into the one-pass narrow kernel only, the one a batch with d.wk set runs (dzg_chain_keeps_wk).
+    if constexpr (!SHARD && NARROW && MAXP == 1 && NOFOLD)
+    if (d.wk && !only_partials && (int)blockIdx.x == ((int)gridDim.x > 1 ? 1 : 0) && wave == 2 &&
+        lane <= teta && (app_col >= 0 || del_last >= 0)) {
+        double *wrow = d.wk + (long long)lane * d.ldw;
+        double wk_app = 0.0;
+        if (app_col >= 0) {
+            const int rl = -1 - new_code_r; // (new_code_r = the leaving variable's code: a slack's here)
+            wk_app = lane < teta ? d.W[(long long)lane * d.ldw + rl] : d.v[rl];
+        }
+        if (del_last >= 0) {
+            if (del_ce != del_last) wrow[del_ce] = app_col == del_last ? wk_app : wrow[del_last];
+        } else {
+            wrow[app_col] = wk_app;
+        }
+    }
     // ---- update of this thread's row and column; candidates on the updated values
     DzgCand2 bx = dzg_cand2_none(), bz = dzg_cand2_none();
     if (has_row) {
@@ -1069,6 +1221,8 @@ int dzg_chain_resident_per_cu(void)
         reinterpret_cast<const void *>(k_chain_pre<false, 1, true>),
         reinterpret_cast<const void *>(k_chain_pre<false, 4, true>),
         reinterpret_cast<const void *>(k_chain_pre<false, 4, false>),
+        reinterpret_cast<const void *>(k_chain_pre<false, 1, true, 1>),
+        reinterpret_cast<const void *>(k_chain_pre<false, 1, true, 2>),
         reinterpret_cast<const void *>(k_chain_post<false, CH_MAXP, false, false>),
         reinterpret_cast<const void *>(k_chain_post<true, CH_MAXP, false, false>),
         reinterpret_cast<const void *>(k_chain_post<false, 1, true, true>),
@@ -1085,10 +1239,43 @@ int dzg_chain_resident_per_cu(void)
 
 // xrecv != nullptr: a column-sharded rank (replicated matrix), records of the exchange just done.
 // instances == 0 (DZG_CHAIN_INSTANCES=0, the A/B switch): the generic kernels always.
+// The host's rule for the pricing tail of k_chain_pre (PRICE): the fused small-k pass would run
+// (small = dzg_price_small), the chain pick is the one-pass narrow kernel (rows on threads < 32, a
+// thread per compact entry), every tile and every nonbasic position has a workgroup, and this slot's
+// pricing pass is not being timed on its own (a timed slot runs the three launches, so that the
+// events bracket k_price_rows_small alone).  More tiles than workgroups stays unfused: a workgroup
+// looping over four tiles would serialise four row trips.
+int dzg_chain_price_rule(int m, int grid, int k_hint, int tiles, long long q, int small, int timed)
+{
+    if (!small || timed || tiles < 1 || tiles > grid || (long long)tiles * CH_THREADS < q) return 0;
+    if (k_hint <= 0 || k_hint >= CH_THREADS - CHP_COL0) return 0;
+    return chain_pick(m, grid, k_hint, 0, 0, 0, 0) == DZG_CHAIN_P1_NARROW;
+}
+int dzg_chain_price_fused(const DzgDev &d, int grid, int small, int timed)
+{
+    return d.wk && d.At && dzg_chain_price_rule(d.m, grid, d.k_hint, dzg_price_small_partials(d), d.q, small, timed);
+}
+// 1: a chain batch enqueued now may run with d.wk set -- some slot of it can price in the tail, and every
+// launch of it, timed slots included, picks the one-pass narrow kernels, the only ones that keep the copy
+int dzg_chain_keeps_wk(const DzgDev &d, int grid, int small)
+{
+    const int tiles = dzg_price_small_partials(d);
+    return d.At && dzg_chain_price_rule(d.m, grid, d.k_hint, tiles, d.q, small, 0) &&
+           chain_pick(d.m, grid, d.k_hint, 0, tiles, 0, 1) == DZG_CHAIN_P1_NARROW;
+}
+
 void dzg_launch_chain_pre(const DzgDev &d, int grid, unsigned long long *bar,
-                          unsigned long long *dbg, const double *xrecv, hipStream_t st, int instances)
+                          unsigned long long *dbg, const double *xrecv, hipStream_t st, int instances, int price)
 {
     const int which = instances ? chain_pick(d.m, grid, d.k_hint, 0, 0, xrecv != nullptr, 0) : DZG_CHAIN_GENERIC;
+    if (price && !xrecv) { // (the rule above held: P1_NARROW whatever `instances` says)
+        // (k < 255 for the whole batch: at most sixteen row groups, one per half-wave; else two)
+        if (d.k_hint < 16 * DZG_PR_BATCH - 1)
+            hipLaunchKernelGGL((k_chain_pre<false, 1, true, 1>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+        else
+            hipLaunchKernelGGL((k_chain_pre<false, 1, true, 2>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
+        return;
+    }
     if (xrecv)
         hipLaunchKernelGGL((k_chain_pre<true, CH_MAXP, false>), dim3(grid), dim3(CH_THREADS), 0, st, d, bar, dbg, xrecv);
     else if (which == DZG_CHAIN_P1_NARROW)

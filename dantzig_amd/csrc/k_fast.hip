@@ -412,12 +412,13 @@ __global__ __launch_bounds__(256) void k_fast_update(DzgCtl *ctl, int only_parti
 // ---------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_fast_gather_w(const DzgCtl *ctl, const double *__restrict__ W,
                                                        long long ldw, const int *__restrict__ drow,
-                                                       double *__restrict__ Wc)
+                                                       double *__restrict__ Wc, int full_only)
 {
     // a flush folds a FULL eta file: one enqueued behind an iteration that did not pivot (the run
     // stopped, a barrier failed) is a no-op, so the flush falls after the same pivots whatever
     // happens in between -- results stay reproducible bit for bit
-    if (ctl->neta < R_) return;
+    // (full_only == 0: the chain's kept copy, gathered afresh whatever neta is -- dzg_launch_gather_wk)
+    if (full_only && ctl->neta < R_) return;
     const int k = ctl->ncompact, neta = ctl->neta;
     const int t = blockIdx.y;
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
@@ -794,7 +795,7 @@ void dzg_launch_fast_flush(const DzgDev &d, hipStream_t st)
     // ncompact <= k_hint <= m (the host's bound for the batch in flight); the kernels mask by ctl
     const int kmax = d.k_hint > 0 && d.k_hint < d.m ? d.k_hint : d.m;
     hipLaunchKernelGGL(k_fast_gather_w, dim3((kmax + 15 + 255) / 256, R_), dim3(256), 0, st, d.ctl,
-                       d.W, d.ldw, d.drow, d.Wc);
+                       d.W, d.ldw, d.drow, d.Wc, 1);
     // row-sharded basis side: this rank's rows only (a multiple of 16 rows from the top, so the
     // MFMA tiles are the single-GPU solve's tiles: the same bits)
     const int r0 = d.rs ? d.rs_r0 : 0, rows = (d.rs ? d.rs_r1 : d.m) - r0;
@@ -813,6 +814,15 @@ void dzg_launch_fast_flush(const DzgDev &d, hipStream_t st)
         hipLaunchKernelGGL(k_fast_flush_mfma<true>, dim3((kmax + 63) / 64, (rows + 63) / 64), dim3(256), 0, st,
                            d.ctl, rows, binv, d.ldb, U, d.ldw, d.Wc, d.ldw);
     hipLaunchKernelGGL(k_fast_flush_done, dim3(1), dim3(1), 0, st, d.ctl, ((kmax + 63) / 64) * 64);
+}
+
+// The chain's kept copy of the eta rows in compact coordinates (d.wk, common.h), or `dst`, from W and
+// drow as they stand: the flush's gather, for any neta.
+void dzg_launch_gather_wk(const DzgDev &d, double *dst, hipStream_t st)
+{
+    const int kmax = d.k_hint > 0 && d.k_hint < d.m ? d.k_hint : d.m;
+    hipLaunchKernelGGL(k_fast_gather_w, dim3((kmax + 15 + 255) / 256, R_), dim3(256), 0, st, d.ctl,
+                       d.W, d.ldw, d.drow, dst ? dst : d.wk, 0);
 }
 
 void dzg_launch_shard_propose(const DzgDev &d, int mode, int nrz, double *xsend, hipStream_t st)

@@ -26,46 +26,15 @@
 // Column codes: >= 0 structural column index, < 0 unit (slack) column of row -1-code.
 #pragma once
 #include "common.h"
+#include "price_small.h" // the fused small-k pass's stages and helpers (k_chain.hip runs them too, and cannot
+                         // include this file: it defines kernels that are no templates)
 
-typedef double double2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ int price_code(const int *__restrict__ nonbasis,
                                           const int *__restrict__ var_col, int pos)
 {
     const int v = nonbasis[pos];
     return var_col ? var_col[v] : v;
-}
-
-// ratio-test candidate of one position (src/simplex.rs:449-455): dz / (z + mu*zbar) if > 0
-// (FAST numerics only: the candidate carries its competition for the near-tie arbitration, and
-// a denominator that is zero up to rounding marks the whole test untrustworthy -- the reference
-// may have +inf, which wins, NaN or a negative ratio there)
-__device__ __forceinline__ void price_candidate(DzgCand2 &best, double dzk, int pos, double mu,
-                                                double tau, const double *__restrict__ z,
-                                                const double *__restrict__ zbar)
-{
-    const double zk = z[pos], scaled = mu * zbar[pos];
-    const double den = zk + scaled;
-    DzgCand2 c;
-    c.r = dzg_div(dzk, den);
-    c.k = pos;
-    c.h = -__builtin_inf();
-    if (c.r > 0.0) best = dzg_better2(best, c);
-    if (dzg_noise_zero(den, zk, scaled, tau)) best.h = __builtin_inf();
-}
-
-// the same with z[pos], zbar[pos] already in registers
-__device__ __forceinline__ void price_candidate_v(DzgCand2 &best, double dzk, int pos, double mu,
-                                                  double tau, double zk, double zbk)
-{
-    const double scaled = mu * zbk;
-    const double den = zk + scaled;
-    DzgCand2 c;
-    c.r = dzg_div(dzk, den);
-    c.k = pos;
-    c.h = -__builtin_inf();
-    if (c.r > 0.0) best = dzg_better2(best, c);
-    if (dzg_noise_zero(den, zk, scaled, tau)) best.h = __builtin_inf();
 }
 
 // unit columns: every thread of the grid takes positions pos = tid, tid + nthreads, ...
@@ -93,23 +62,6 @@ __device__ __forceinline__ void price_publish(DzgCand2 best, double *__restrict_
                                               int *__restrict__ rz_k, double *__restrict__ rz_h)
 {
     best = dzg_block_best2(best);
-    if (rz_r && threadIdx.x == 0) {
-        rz_r[blockIdx.x] = best.r;
-        rz_k[blockIdx.x] = best.k;
-        rz_h[blockIdx.x] = best.h;
-    }
-}
-
-// k_price_rows_small's publish step (512 threads): the straight-line wave reduction of common.h,
-// then the eight wave results in the three steps of one half row -- one workgroup barrier instead of
-// two, no 64-lane butterfly for eight values.  The same candidate, bit for bit (common.h).
-// Only for a launch of exactly 512 threads, all of which arrive here (k_price_rows_small:
-// __launch_bounds__(512), launched with 512; its early exits are taken by the whole workgroup): the
-// half-row stage holds eight wave results, no more.
-__device__ __forceinline__ void price_publish_small(DzgCand2 best, double *__restrict__ rz_r,
-                                                    int *__restrict__ rz_k, double *__restrict__ rz_h)
-{
-    best = dzg_block_best2_flat<8>(best, false);
     if (rz_r && threadIdx.x == 0) {
         rz_r[blockIdx.x] = best.r;
         rz_k[blockIdx.x] = best.k;
@@ -873,8 +825,6 @@ __global__ __launch_bounds__(256) void k_price_csc_rl(
 // = the tree kernel's count of ratio partials.  The order of a column's sum depends on k and the
 // compact numbering only (not on the grid, the tile width or a column sharding).
 // ---------------------------------------------------------------------------------
-#define PR_GMAX DZG_PR_GMAX
-#define PR_BATCH DZG_PR_BATCH // rows per group at least (G = ceil(rows / PR_BATCH), capped at PR_GMAX)
 #define PR_PIPE 8   // rows per register set of the streaming loop
 template <int VEC, int PIPE = PR_PIPE>
 __global__ __launch_bounds__(256) void k_price_rows(
@@ -994,6 +944,8 @@ __global__ __launch_bounds__(256) void k_price_rows(
 // nothing for k_chain_post to fold: TWO dependent trips (control block, row list, coefficients,
 // positions | rows, z, zbar).
 // grid = ceil(ldt / 64) workgroups = its count of ratio partials.
+// The rows stage and the finish are device functions (price_small.h: price_small_rows, price_small_finish):
+// the kernel below is the first trip and the row list in front of them.
 //
 // The row list does not wait for the control block: thread t fetches drow[t] and vc[t] beside it
 // (k + 1 <= 512 = the workgroup's threads) and leaves the row's offset and the coefficient in LDS.
@@ -1020,9 +972,6 @@ __global__ __launch_bounds__(256) void k_price_rows(
 // running) stops the solve with DZG_PANIC instead of leaving k_chain_post a stale dz.
 // dbg != nullptr (DZG_CHAIN_DEBUG=1): the stage clocks of workgroup 0, slot 4 (ChainStamps):
 // control block | row list (into LDS, the barrier) | rows | finish.
-#define PRS_TILE 64
-#define PRS_ROWS 512
-#define PRS_STAMP_SLOT 4
 // (waves per SIMD asked of the compiler: 8 = four workgroups per CU for <1, 1, 8>; else whatever a
 // workgroup needs)
 template <int VEC, int NG, int RPT>
@@ -1034,10 +983,6 @@ __global__ __launch_bounds__(512, (RPT < PR_BATCH ? 8 : 2)) void k_price_rows_sm
     double *__restrict__ rz_r, int *__restrict__ rz_k, double *__restrict__ rz_h,
     unsigned long long *dbg)
 {
-    constexpr int LPG = 64 / VEC; // lanes of a group slot
-    constexpr int NS = 512 / LPG; // group slots of the workgroup
-    static_assert(VEC == 1 || VEC == 2, "8- or 16-byte loads");
-    static_assert(PR_BATCH % RPT == 0 && PR_GMAX * PR_BATCH >= PRS_ROWS, "a group has at most PR_BATCH rows");
     __shared__ long long s_off[PRS_ROWS];
     __shared__ double s_coef[PRS_ROWS];
     __shared__ __attribute__((aligned(16))) double s_part[PR_GMAX][PRS_TILE];
@@ -1087,106 +1032,11 @@ __global__ __launch_bounds__(512, (RPT < PR_BATCH ? 8 : 2)) void k_price_rows_sm
         zc = z[pos];
         zbc = zbar[pos];
     }
-    const int nrows = k + (lcode < 0 ? 1 : 0);
-    int G = (k + 1 + PR_BATCH - 1) / PR_BATCH; // (as k_price_rows)
-    G = G > PR_GMAX ? PR_GMAX : G;
-    const int slot = tid / LPG, h = tid % LPG;
-    const long long jc = (long long)blockIdx.x * PRS_TILE + h * VEC; // (ldt is even when VEC = 2)
-    const double *col = At + (jc < ldt ? jc : 0);
-    for (int g0 = slot; g0 < G; g0 += NS * NG) {
-        double acc[NG][VEC];
-#pragma unroll
-        for (int t = 0; t < NG; ++t)
-#pragma unroll
-            for (int e = 0; e < VEC; ++e) acc[t][e] = 0.0;
-        for (int r0 = 0; r0 < PR_BATCH; r0 += RPT) {
-            if (RPT < PR_BATCH && g0 + r0 * G >= nrows) break; // (groups ascend with t: none has a row left)
-            // entry (t, u): c = g + (r0 + u) G of group g = g0 + NS t; it exists when g < G and
-            // c < nrows (the LDS reads are unconditional: one that does not exist reads entry 0)
-#define PRS_ENTRY(T, U)                                                                              \
-    const int c = g0 + NS * (T) + (r0 + (U)) * G;                                                    \
-    const bool ok = g0 + NS * (T) < G && c < nrows
-            long long off[NG][RPT]; // one batch of LDS reads, waited for once
-#pragma unroll
-            for (int t = 0; t < NG; ++t)
-#pragma unroll
-                for (int u = 0; u < RPT; ++u) {
-                    PRS_ENTRY(t, u);
-                    off[t][u] = s_off[ok ? c : 0];
-                }
-            // the rows, all in flight; the coefficients behind them
-            double x[NG][RPT][VEC], cf[NG][RPT];
-#pragma unroll
-            for (int t = 0; t < NG; ++t)
-#pragma unroll
-                for (int u = 0; u < RPT; ++u) {
-                    PRS_ENTRY(t, u);
-                    const double *src = col + (ok ? off[t][u] : 0);
-                    if constexpr (VEC == 2) {
-                        const double2_t w = __builtin_nontemporal_load(reinterpret_cast<const double2_t *>(src));
-                        x[t][u][0] = w.x;
-                        x[t][u][1] = w.y;
-                    } else {
-                        x[t][u][0] = __builtin_nontemporal_load(src);
-                    }
-                }
-            // (the scheduler otherwise holds back two of sixteen loads until the first sums are done,
-            // a second trip, and mixes the coefficients' LDS reads among the loads)
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < NG; ++t)
-#pragma unroll
-                for (int u = 0; u < RPT; ++u) {
-                    PRS_ENTRY(t, u);
-                    cf[t][u] = s_coef[ok ? c : 0];
-                }
-#pragma unroll
-            for (int t = 0; t < NG; ++t)
-#pragma unroll
-                for (int u = 0; u < RPT; ++u) {
-                    PRS_ENTRY(t, u);
-#pragma unroll
-                    for (int e = 0; e < VEC; ++e)
-                        acc[t][e] = ok ? fma(cf[t][u], x[t][u][e], acc[t][e]) : acc[t][e];
-                }
-#undef PRS_ENTRY
-        }
-#pragma unroll
-        for (int t = 0; t < NG; ++t)
-            if (g0 + NS * t < G) {
-#pragma unroll
-                for (int e = 0; e < VEC; ++e) s_part[g0 + NS * t][h * VEC + e] = acc[t][e];
-            }
-    }
+    const int G = price_small_rows<VEC, NG, RPT>(At, ldt, (int)blockIdx.x, k, lcode, s_off, s_coef, s_part);
     __syncthreads();
     ts.mark(PRS_STAMP_SLOT); // 2: rows
-    DzgCand2 best = dzg_cand2_none();
-    if (pos >= 0) { // (wave 0) the finishing launch's sum: the groups in order
-        double sum = 0.0;
-        for (int g = 0; g < G; ++g) sum = sum + s_part[g][lane];
-        dz[pos] = -sum;
-        price_candidate_v(best, -sum, pos, mu, tau, zc, zbc);
-    }
-    // ---- unit columns (the arithmetic of price_slack_positions)
-    if (scode < 0) {
-        const double p = 1.0 * -sv;
-        const double d = 0.0 + p;
-        dz[spos] = d;
-        price_candidate_v(best, d, spos, mu, tau, sz, szb);
-    }
-    for (int ps = spos + (int)gridDim.x * 512; ps < q; ps += (int)gridDim.x * 512) { // (never: 8 threads per column)
-        const int code = nbcode[ps];
-        if (code < 0) {
-            const double p = 1.0 * -v[-1 - code];
-            const double d = 0.0 + p;
-            dz[ps] = d;
-            price_candidate(best, d, ps, mu, tau, z, zbar);
-        }
-    }
-    ts.pin(best);
-    const unsigned long long t_publish = ts.now();
-    price_publish_small(best, rz_r, rz_k, rz_h);
-    ts.site(DZG_SITE_PUBLISH, t_publish);
+    price_small_finish<true>(ts, G, s_part, pos, zc, zbc, scode, spos, sv, sz, szb, (int)gridDim.x, q, nbcode, v, dz, z,
+                             zbar, mu, tau, rz_r, rz_k, rz_h);
     ts.mark(PRS_STAMP_SLOT); // 3: finish
     ts.done(PRS_STAMP_SLOT);
 }

@@ -1047,6 +1047,25 @@ int dzg_debug_cand_reduce(int32_t device, int32_t form, int64_t ncases, const do
 int dzg_debug_chain_instance(int32_t m, int32_t grid, int32_t k_bound, int32_t fold, int32_t nrz,
                              int32_t shard, int32_t post);
 
+/* Test hooks of the small-k pricing pass run in k_chain_pre's tail (csrc/k_chain.hip, PRICE;
+ * tests/test_gpu_price_in_pre.py).
+ * dzg_debug_chain_price_counts: counts[0] = chain iterations this solver has enqueued with the pass
+ * in k_chain_pre's tail (two launches), counts[1] = with the pass as a launch of its own (three).
+ * dzg_debug_wk_mismatch: info[0] = the number of entries in which the kept compact copy of the eta
+ * rows differs BITWISE from a fresh gather of W (t < neta, c < k; gathered into scratch on the
+ * solver's stream), info[1] = whether the host held the copy valid (kept it) as it stood; clear_valid != 0 then drops the
+ * flag, so that the next chain batch gathers the copy again.  DZG_E_ARG when the solver keeps no copy.
+ * Call it between run() calls only, never while a batch is in flight: the scratch is the eta flush's
+ * (which gathers again before it reads it), and the gather is sized for the full width.
+ * dzg_debug_chain_price_rule: the host's rule (1: the pass runs in the tail) for m rows on `grid`
+ * chain workgroups, the host's bound k_hint on the compact width, `tiles` column tiles, q nonbasic
+ * positions, `small` = the fused small-k pass would run, `timed` = this slot's pricing pass is being
+ * timed on its own.  Pure host code: no device is touched. */
+int dzg_debug_chain_price_counts(dzg_solver *s, int64_t counts[2]);
+int dzg_debug_wk_mismatch(dzg_solver *s, int32_t clear_valid, int64_t info[2]);
+int dzg_debug_chain_price_rule(int32_t m, int32_t grid, int32_t k_hint, int32_t tiles, int64_t q,
+                               int32_t small, int32_t timed);
+
 /* Deterministic max-loc merge: largest ratio wins, lowest global position on ties --
  * the sequential first-wins rule of src/simplex.rs:432-435,456-459.  Returns the index
  * of the winning record, or -1 when every record is empty. */
