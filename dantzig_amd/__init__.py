@@ -10,12 +10,12 @@ Public names match the reference package (python-source/dantzig/__init__.py:2-10
 """
 from . import exceptions
 from .model import Variable
-from .optimize import Maximize, Minimize, solve_many
+from .optimize import Maximize, Minimize, SessionBatch, sessions, solve_many
 
 Var = Variable
 Min = Minimize
 Max = Maximize
 
-# solve_many (batched .solve(), an addition of this package) stays out of __all__, which names
-# exactly the reference's public surface
+# solve_many (batched .solve()) and sessions (batched Optimize.session()), additions of this package,
+# stay out of __all__, which names exactly the reference's public surface
 __all__ = ["Variable", "Var", "Minimize", "Min", "Maximize", "Max", "exceptions"]

@@ -52,6 +52,7 @@ EXPORTS = [
     "dzg_solver_extend", "dzg_solver_dims", "dzg_debug_matrix", "dzg_debug_matrix_rows",
     "dzg_debug_extend_ms",
     "dzg_solver_remove",
+    "dzg_batch_solve_from", "dzg_debug_batch_restart_ms",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -159,6 +160,10 @@ class ModelRay(C.Structure):
 class Reopt(C.Structure):
     _fields_ = [("rhs", C.c_void_p), ("c", C.c_void_p), ("constant", C.c_double),
                 ("set_constant", C.c_int32), ("reserved", C.c_int32)]
+
+
+class BatchStart(C.Structure):
+    _fields_ = [("basis", C.c_void_p), ("nonbasis", C.c_void_p)]
 
 
 class Extend(C.Structure):
@@ -312,6 +317,10 @@ def lib() -> C.CDLL:
         _lib.dzg_solver_extend.argtypes = [C.c_void_p, C.c_void_p]
         _lib.dzg_solver_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_solver_dims.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_solve_from.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                              C.c_void_p, C.c_void_p]
+        _lib.dzg_debug_batch_restart_ms.restype = C.c_double
+        _lib.dzg_debug_batch_restart_ms.argtypes = []
         _lib.dzg_debug_matrix.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
         _lib.dzg_debug_matrix_rows.restype = C.c_int64
         _lib.dzg_debug_matrix_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]

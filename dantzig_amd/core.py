@@ -724,9 +724,40 @@ _PIVOT_DTYPE = np.dtype([("kind", "<i4"), ("reserved", "<i4"), ("entering", "<i8
                          ("leaving", "<i8"), ("mu", "<f8")])
 
 
+def _batch_starts(lps, start) -> list:
+    """solve_batch's `start`, checked: per LP None or the (basis, nonbasis) pair as int64 arrays."""
+    start = list(start)
+    if len(start) != len(lps):
+        raise ValueError(f"start: {len(start)} entries for {len(lps)} LPs (one per LP, None = cold)")
+    out = []
+    for i, (lp, s) in enumerate(zip(lps, start)):
+        if isinstance(s, CoreResult):
+            s = None if s.status in ("singular", "panic") else (s.basis, s.nonbasis)
+        if s is None:
+            out.append(None)
+            continue
+        try:
+            basis, nonbasis = s
+        except (TypeError, ValueError):
+            raise ValueError(f"start[{i}]: None, a CoreResult or a (basis, nonbasis) pair") from None
+        basis, nonbasis = i64(basis), i64(nonbasis)
+        m, n = lp.m, lp.n
+        if basis.shape != (m,) or nonbasis.shape != (n - m,):
+            raise ValueError(f"start[{i}]: basis / nonbasis of {basis.size} / {nonbasis.size} entries, "
+                             f"lps[{i}] has m = {m}, n - m = {n - m}")
+        codes = _codes(lp)[i64(lp.basis)] if len(lp.basis) == m and m > 0 else np.zeros(0, np.int64)
+        if (codes >= 0).any() or len(set(codes.tolist())) != m:
+            raise ValueError(f"lps[{i}]: a warm LP is given in slack-basis form (its own basis all slack)")
+        both = np.concatenate([basis, nonbasis])
+        if both.size and (both.min() < 0 or both.max() >= n or len(set(both.tolist())) != n):
+            raise ValueError(f"start[{i}]: basis / nonbasis is not a partition of 0 .. {n - 1}")
+        out.append((basis, nonbasis))
+    return out
+
+
 def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
                 duals: bool = False, ranging=False, pivot_tol: float = 0.0, rays: bool = False,
-                **opts) -> list:
+                start=None, **opts) -> list:
     """dzg_batch_solve: every LP of `lps` in STRICT numerics, one workgroup per LP, in one call.
 
     The whole batch is checked on the host first (ValueError: more than 128 rows, CSC input, FAST
@@ -738,7 +769,15 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
     as (cost_dirs, rhs_dirs) with the meaning of Solver.ranging (dzg_batch_solve_ranging): every
     result gains `.ranging`, a CoreRanging, and `.duals` as well; None for an LP that did not end
     optimal.  rays=True (dzg_batch_solve_rays; composes with duals, not with ranging): every result
-    gains `.ray`, a CoreRay for an LP that ended unbounded or infeasible and None otherwise."""
+    gains `.ray`, a CoreRay for an LP that ended unbounded or infeasible and None otherwise.
+
+    start (dzg_batch_solve_from; composes with duals, not with ranging or rays): one entry per LP,
+    each None (solve this LP cold, exactly as without `start`), a CoreResult of an earlier solve of
+    the same matrix, or a (basis, nonbasis) pair.  A CoreResult that ended singular or panicked
+    counts as None.  `lps[i]` is the LP to solve now in slack-basis form (its x is the right-hand
+    side, its c the costs); a warm LP gets the state its start basis defines for that data (x =
+    B^-1 rhs, fresh reduced costs, xbar = zbar = 1) and is pivoted on from there.  iterations and
+    pivots count from 0.  A singular start basis ends "singular" with 0 iterations."""
     import time
 
     lps = list(lps)
@@ -747,6 +786,9 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         raise ValueError("solve_batch runs STRICT numerics only (numerics=STRICT or AUTO)")
     if rays and ranging is not False and ranging is not None:
         raise ValueError("rays=True and ranging: the ranging call carries no ray; ask in two calls")
+    if start is not None and (rays or (ranging is not False and ranging is not None)):
+        raise ValueError("start composes with duals only: ask for ranging or rays in a call without it")
+    starts = None if start is None else _batch_starts(lps, start)
     for i, lp in enumerate(lps):
         if lp.block is not None:
             raise ValueError(f"lps[{i}]: a column-block LP cannot be batched")
@@ -804,8 +846,16 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         for i in range(count):
             ry[i].d = rd_all.ctypes.data + 8 * int(ro[i])
             ry[i].y = ry_all.ctypes.data + 8 * int(mo[i])
+    if starts is not None:
+        c_start = (_ffi.BatchStart * max(count, 1))()
+        for i, s in enumerate(starts):
+            if s is not None:
+                c_start[i].basis, c_start[i].nonbasis = ptr(s[0]), ptr(s[1])
     t0 = time.perf_counter()
-    if rays:
+    if starts is not None:
+        rc = _ffi.lib().dzg_batch_solve_from(c_lps, c_start, C.c_int64(count), C.byref(o),
+                                             C.c_int64(int(pivots_per_launch)), res, du if duals else None)
+    elif rays:
         rc = _ffi.lib().dzg_batch_solve_rays(c_lps, C.c_int64(count), C.byref(o),
                                              C.c_int64(int(pivots_per_launch)), res, du if duals else None, ry)
     elif want_ranging:
@@ -818,7 +868,7 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
         rc = _ffi.lib().dzg_batch_solve(c_lps, C.c_int64(count), C.byref(o),
                                         C.c_int64(int(pivots_per_launch)), res)
     wall_ms = (time.perf_counter() - t0) * 1e3
-    _ffi.check_ranging(rc, "dzg_batch_solve_rays" if rays else "dzg_batch_solve_ranging" if want_ranging else
+    _ffi.check_ranging(rc, "dzg_batch_solve_from" if starts is not None else "dzg_batch_solve_rays" if rays else "dzg_batch_solve_ranging" if want_ranging else
                        ("dzg_batch_solve_duals" if duals else "dzg_batch_solve"))
     out = []
     for i in range(count):

@@ -249,9 +249,18 @@ struct Layout {
     }
 };
 
+// The constraint row of a slack variable as var_col codes it (-1 - row), the column of a structural
+inline int64_t var_code(const dzg_lp &lp, int64_t v)
+{
+    return lp.var_col ? lp.var_col[v] : (v < lp.n_struct ? v : -1 - (v - lp.n_struct));
+}
+
 // The descriptors, A, var_col, the starting state and the first round's lists (LP indices grouped by
-// bucket) into the upload buffer.
-inline void fill_upload(unsigned char *host, const Layout &L, const Packed &P, const dzg_lp *lps)
+// bucket) into the upload buffer.  An LP with a start basis (start[i].basis != NULL, dzg_batch_solve_from)
+// goes up as k_batch_restart reads it: the start's basis and nonbasis, the right-hand side by
+// constraint row in x (lp.x[p] belongs to the row whose slack sits at position p), xbar = zbar = 1.
+inline void fill_upload(unsigned char *host, const Layout &L, const Packed &P, const dzg_lp *lps,
+                        const dzg_batch_start *start = nullptr)
 {
     std::memcpy(host + L.desc, P.desc.data(), sizeof(DzgBatchLp) * P.desc.size());
     double *a = (double *)(host + L.a);
@@ -269,6 +278,20 @@ inline void fill_upload(unsigned char *host, const Layout &L, const Packed &P, c
         for (int64_t v = 0; v < lp.n; ++v)
             vc[d.vc_off + v] = lp.var_col ? (int)lp.var_col[v]
                                           : (v < lp.n_struct ? (int)v : (int)(-1 - (v - lp.n_struct)));
+        list[fill[(size_t)bucket_of(lp.m)]++] = i;
+        if (start && start[i].basis) {
+            for (int64_t k = 0; k < m; ++k) {
+                bs[d.m_off + k] = (int)start[i].basis[k];
+                x[d.m_off + (-1 - var_code(lp, lp.basis[k]))] = lp.x[k];
+                xb[d.m_off + k] = 1.0;
+            }
+            for (int64_t k = 0; k < q; ++k) {
+                nb[d.q_off + k] = (int)start[i].nonbasis[k];
+                z[d.q_off + k] = 0.0; // the kernel's to write
+                zb[d.q_off + k] = 1.0;
+            }
+            continue;
+        }
         for (int64_t k = 0; k < m; ++k) {
             bs[d.m_off + k] = (int)lp.basis[k];
             x[d.m_off + k] = lp.x[k];
@@ -279,7 +302,6 @@ inline void fill_upload(unsigned char *host, const Layout &L, const Packed &P, c
             z[d.q_off + k] = lp.z[k];
             zb[d.q_off + k] = lp.zbar ? lp.zbar[k] : 1.0;
         }
-        list[fill[(size_t)bucket_of(lp.m)]++] = i;
     }
 }
 

@@ -32,6 +32,7 @@
 #include <vector>
 
 #include "batch_host.h"
+#include "batch_restart.h"
 #include "batch_strict.h"
 #include "common.h"
 #include "duals.h"
@@ -121,6 +122,8 @@ struct BatchExtras {
 // brought down in the buffers named after it.
 struct Ctx {
     const dzg_lp *lps;
+    const dzg_batch_start *start; // dzg_batch_solve_from: the LPs with a start basis are warm
+    bool warm = false;            // any of them
     int N;
     dzg_result *res;
     BatchExtras ex;
@@ -129,6 +132,7 @@ struct Ctx {
     size_t status = 0, iter = 0; // the STRICT state sections
     // sections behind the solve's: duals (c and the starting x go up; y, d and the scalars come
     // down), then rays (d, y and the scalars come down)
+    // (c alone goes up as well whenever an LP is warm: the restart prices with it)
     size_t c = 0, x0 = 0, dlist = 0, y = 0, d = 0, scal = 0, duals_end = 0;
     size_t rlist = 0, rd = 0, ry = 0, rscal = 0;
     std::vector<unsigned char> host;
@@ -141,10 +145,13 @@ struct Ctx {
     std::vector<long long> rg_out;     // LP i's ranges: rg_out[i] .., cost directions first
     size_t r_lo = 0, r_hi = 0, r_lov = 0, r_hiv = 0;
 
-    Ctx(const dzg_lp *lps_, int n, dzg_result *res_, const BatchExtras &ex_, long long max_iter)
-        : lps(lps_), N(n), res(res_), ex(ex_), P(bh::pack(lps_, res_, n, max_iter)), L(P)
+    Ctx(const dzg_lp *lps_, const dzg_batch_start *start_, int n, dzg_result *res_, const BatchExtras &ex_,
+        long long max_iter)
+        : lps(lps_), start(start_), N(n), res(res_), ex(ex_), P(bh::pack(lps_, res_, n, max_iter)), L(P)
     {
+        for (int i = 0; start && i < n; ++i) warm = warm || start[i].basis;
     }
+    bool is_warm(int i) const { return start && start[i].basis; }
     const int *stat() const { return (const int *)(host.data() + status); } // after the download
 };
 
@@ -157,8 +164,9 @@ int pack_and_upload(Ctx &C)
     C.iter = L.ar.add(sizeof(long long) * N);
     L.end_upload();
     L.end_download();
-    if (C.ex.duals || C.ex.rays) {
-        C.c = L.ar.add(sizeof(double) * C.P.nvc);
+    const bool post = C.ex.duals || C.ex.rays;
+    if (post || C.warm) C.c = L.ar.add(sizeof(double) * C.P.nvc);
+    if (post) {
         C.x0 = L.ar.add(sizeof(double) * C.P.nm);
         C.dlist = L.ar.add(sizeof(int) * N);
         C.y = L.ar.add(sizeof(double) * C.P.nm);
@@ -173,25 +181,94 @@ int pack_and_upload(Ctx &C)
         C.rscal = L.ar.add(sizeof(double) * DZG_RAY_SCAL * N);
     }
     C.host.assign(L.download_end, 0);
-    bh::fill_upload(C.host.data(), L, C.P, C.lps);
+    bh::fill_upload(C.host.data(), L, C.P, C.lps, C.start);
     int *st = (int *)(C.host.data() + C.status);
     for (int i = 0; i < N; ++i) st[i] = DZG_RUNNING;
     if (const int rc = bh::upload(C.D, L, C.host.data())) return rc;
     unsigned char *dev = C.D.arena;
-    if (C.ex.duals || C.ex.rays) { // c and the starting x, for the passes behind the solve
-        C.cx0.assign(C.dlist - C.c, 0);
-        double *cc = (double *)C.cx0.data(), *x0 = (double *)(C.cx0.data() + (C.x0 - C.c));
+    if (post || C.warm) { // c and the starting x, for the restart and the passes behind the solve
+        C.cx0.assign(post ? C.dlist - C.c : sizeof(double) * (size_t)C.P.nvc, 0);
+        double *cc = (double *)C.cx0.data(), *x0 = post ? (double *)(C.cx0.data() + (C.x0 - C.c)) : nullptr;
         for (int i = 0; i < N; ++i) {
             const dzg_lp &lp = C.lps[i];
             const DzgBatchLp &d = C.P.desc[(size_t)i];
             for (int64_t v = 0; v < lp.n; ++v) cc[d.vc_off + v] = lp.c[v];
-            for (int64_t k = 0; k < lp.m; ++k) x0[d.m_off + k] = lp.x[k];
+            for (int64_t k = 0; post && k < lp.m; ++k) x0[d.m_off + k] = lp.x[k];
         }
         DZG_HIP(hipMemcpyAsync(dev + C.c, C.cx0.data(), C.cx0.size(), hipMemcpyHostToDevice, C.D.st));
     }
     bh::wire(C.g, dev, L);
     C.g.status = (int *)(dev + C.status);
     C.g.iter = (long long *)(dev + C.iter);
+    return 0;
+}
+
+thread_local double t_restart_ms = 0.0; // dzg_debug_batch_restart_ms
+
+// ---- the restart state of the warm LPs: one workgroup each, bucket by bucket, before the first
+// round.  A singular start leaves the first round's lists; `live` follows.
+int restart_pass(Ctx &C, std::array<int, kBuckets> &live)
+{
+    unsigned char *dev = C.D.arena;
+    hipStream_t st = C.D.st;
+    std::vector<int> warm;
+    bh::Segments wseg{};
+    for (int b = 0; b < kBuckets; ++b) {
+        for (int i = 0; i < C.N; ++i)
+            if (C.is_warm(i) && bh::bucket_of(C.lps[i].m) == b) warm.push_back(i);
+        wseg[(size_t)b + 1] = (int)warm.size();
+    }
+    // the next round's list is free until the first round appends to it
+    int *wlist = (int *)(dev + C.L.list2);
+    DZG_HIP(hipMemcpyAsync(wlist, warm.data(), sizeof(int) * warm.size(), hipMemcpyHostToDevice, st));
+    DzgBatchRestartArgs a;
+    a.lp = C.g.lp;
+    a.A = C.g.A;
+    a.var_col = C.g.var_col;
+    a.basis = C.g.basis;
+    a.nonbasis = C.g.nonbasis;
+    a.x = C.g.x;
+    a.xbar = C.g.xbar;
+    a.z = C.g.z;
+    a.zbar = C.g.zbar;
+    a.c = (const double *)(dev + C.c);
+    a.status = C.g.status;
+    struct Events {
+        hipEvent_t e0 = nullptr, e1 = nullptr;
+        ~Events()
+        {
+            if (e0) (void)hipEventDestroy(e0);
+            if (e1) (void)hipEventDestroy(e1);
+        }
+    } ev;
+    DZG_HIP(hipEventCreate(&ev.e0));
+    DZG_HIP(hipEventCreate(&ev.e1));
+    DZG_HIP(hipEventRecord(ev.e0, st));
+    for (int b = 0; b < kBuckets; ++b) {
+        const int cnt = wseg[(size_t)b + 1] - wseg[(size_t)b];
+        if (cnt == 0) continue;
+        a.mmax = C.P.mmax[b];
+        dzg_launch_batch_restart(b, a, wlist + wseg[(size_t)b], cnt, st);
+        DZG_HIP(hipGetLastError());
+    }
+    DZG_HIP(hipEventRecord(ev.e1, st));
+    std::vector<int> status((size_t)C.N);
+    DZG_HIP(hipMemcpyAsync(status.data(), dev + C.status, sizeof(int) * C.N, hipMemcpyDeviceToHost, st));
+    DZG_HIP(hipStreamSynchronize(st));
+    float ms = 0.0f;
+    DZG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    t_restart_ms = ms;
+    if (std::all_of(status.begin(), status.end(), [](int s) { return s == DZG_RUNNING; })) return 0;
+    // the first round's lists without the singular starts, in the order fill_upload gave them
+    int *list = (int *)(C.host.data() + C.L.list);
+    const bh::Segments seg = bh::segments(C.P.bucket_n);
+    for (int b = 0; b < kBuckets; ++b) {
+        int n = 0;
+        for (int k = seg[(size_t)b]; k < seg[(size_t)b + 1]; ++k)
+            if (status[(size_t)list[k]] == DZG_RUNNING) list[seg[(size_t)b] + n++] = list[k];
+        live[(size_t)b] = n;
+    }
+    DZG_HIP(hipMemcpyAsync(dev + C.L.list, list, sizeof(int) * C.N, hipMemcpyHostToDevice, st));
     return 0;
 }
 
@@ -458,9 +535,40 @@ void write_results(const Ctx &C)
 // move), what `ex` asks for: the duals of the LPs that end OPTIMAL (k_duals.hip), their ranges
 // (k_ranging.hip, which reads the duals' fresh d), the rays of the LPs that end UNBOUNDED or
 // INFEASIBLE (k_rays.hip).
-static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots_per_launch,
-                       dzg_result *res, BatchExtras ex)
+// A warm LP's own basis is all slack, one per row; its start is a partition of 0 .. n-1.
+static bool start_valid(const dzg_lp &lp, const dzg_batch_start &s, std::string &why)
 {
+    if (!s.basis) return true;
+    const int64_t m = lp.m, n = lp.n;
+    if (n > m && !s.nonbasis) {
+        why = "start: nonbasis is NULL beside a basis";
+        return false;
+    }
+    std::vector<char> seen((size_t)m, 0);
+    for (int64_t p = 0; p < m; ++p) {
+        const int64_t code = bh::var_code(lp, lp.basis[p]);
+        if (code >= 0 || seen[(size_t)(-1 - code)]) {
+            why = "start: the LP's own basis is not all slack (basis[" + std::to_string(p) + "])";
+            return false;
+        }
+        seen[(size_t)(-1 - code)] = 1;
+    }
+    seen.assign((size_t)n, 0);
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t v = k < m ? s.basis[k] : s.nonbasis[k - m];
+        if (v < 0 || v >= n || seen[(size_t)v]) {
+            why = "start: basis/nonbasis is not a partition of 0..n-1";
+            return false;
+        }
+        seen[(size_t)v] = 1;
+    }
+    return true;
+}
+
+static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots_per_launch,
+                       dzg_result *res, BatchExtras ex, const dzg_batch_start *start = nullptr)
+{
+    t_restart_ms = 0.0;
     std::vector<dzg_duals> du_own; // ranging needs the fresh d on the device; the caller may not want it
     if (ex.ranging && !ex.du && count > 0 && count < (1ll << 31)) {
         dzg_duals none;
@@ -479,22 +587,26 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
         return dzg_set_error(DZG_E_ARG, "batch: STRICT numerics only (FAST is not batched)");
     const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
     const int rc_lps = bh::check_batch(lps, count, [&](int64_t i, std::string &why) {
+        if (start && !start_valid(lps[i], start[i], why)) return false;
         return !ex.ranging || dzg_ranging_req_valid(&ex.req[i], lps[i].m, lps[i].n, why);
     });
     if (rc_lps) return rc_lps;
     if (count == 0) return 0;
     if (const int rc = bh::use_device(o.device)) return rc;
 
-    Ctx C(lps, (int)count, res, ex, max_iter);
+    Ctx C(lps, start, (int)count, res, ex, max_iter);
     C.g.max_iter = max_iter;
     C.g.eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
     C.g.ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30) : DZG_BATCH_DEFAULT_PPL);
     if (const int rc = pack_and_upload(C)) return rc;
     unsigned char *dev = C.D.arena;
     hipStream_t st = C.D.st;
+    std::array<int, kBuckets> live = bh::live_of(C.P.bucket_n);
+    if (C.warm)
+        if (const int rc = restart_pass(C, live)) return rc;
     const int rc_rounds = bh::run_rounds(
         (int *)(dev + C.L.list), (int *)(dev + C.L.list2), (int *)(dev + C.L.count), bh::segments(C.P.bucket_n),
-        bh::live_of(C.P.bucket_n), st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
+        live, st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
             BArgs gb = C.g;
             gb.mmax = C.P.mmax[b];
             launch_bucket(b, gb, list, n, next_list, next_count, st);
@@ -549,3 +661,15 @@ extern "C" int dzg_batch_solve_rays(const dzg_lp *lps, int64_t count, const dzg_
     ex.ry = ry;
     return batch_solve(lps, count, opts, pivots_per_launch, res, ex);
 }
+
+extern "C" int dzg_batch_solve_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                                    const dzg_opts *opts, int64_t pivots_per_launch, dzg_result *res,
+                                    dzg_duals *du)
+{
+    BatchExtras ex;
+    ex.duals = du != nullptr;
+    ex.du = du;
+    return batch_solve(lps, count, opts, pivots_per_launch, res, ex, start);
+}
+
+extern "C" double dzg_debug_batch_restart_ms(void) { return t_restart_ms; }

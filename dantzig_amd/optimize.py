@@ -326,6 +326,39 @@ class Optimize(abc.ABC):
         return Session(self, **core_opts)
 
 
+def _model_rows(constraints, rhs: dict) -> list:
+    """The rows of `constraints` with the right-hand sides of `rhs` ({id(constraint): the new b of its
+    normal form}): row k of a changed constraint is its linear part as lowered with
+    b = Constraint._signs[k] * (the new b)."""
+    rows = []
+    for constraint in constraints:
+        b = rhs.get(id(constraint))
+        for ineq, sign in zip(constraint.rust_inequalities(), constraint._signs):
+            rows.append(ineq if b is None else rs.PyInequality(linexpr=ineq._linexpr, b=sign * b))
+    return rows
+
+
+def _lower_model(sense: str, objective, rows: list):
+    """(the core problem, lower()'s arrays, the variables in lowering order) of a model in `sense`:
+    the lowering Session and SessionBatch share."""
+    objective = -objective if sense == "minimize" else objective
+    problem = (objective.to_rust_affexpr(), rows)
+    arrays, order = rs.lower(*problem)
+    return problem, arrays, order
+
+
+def _normal_b(b) -> float:
+    """As a comparison forms it, b = -(constant of lhs - rhs): a written 0 arrives as -0.0."""
+    return -(0.0 - float(b))
+
+
+def _user_values(res, form, order) -> dict:
+    """{variable id: x+ - x-} of a core result on the standard form `form` (src/simplex.rs:354-371)."""
+    by_var = dict(zip(res.basis.tolist(), res.x.tolist()))
+    return {v.id: by_var.get(int(form.pos_var[i]), 0.0) - by_var.get(int(form.neg_var[i]), 0.0)
+            for i, v in enumerate(order)}
+
+
 class Session:
     """A model kept on the GPU between solves (Optimize.session): the first solve() lowers the model,
     uploads it and solves it from the slack basis; every later solve(objective=..., rhs=...) changes
@@ -371,18 +404,10 @@ class Session:
     def _inequalities(self) -> list:
         """The model's rows with the right-hand sides of the session: row k of a changed constraint is
         its linear part as lowered with b = Constraint._signs[k] * (the new b of the normal form)."""
-        rows = []
-        for constraint in self._constraints:
-            b = self._rhs.get(id(constraint))
-            for ineq, sign in zip(constraint.rust_inequalities(), constraint._signs):
-                rows.append(ineq if b is None else rs.PyInequality(linexpr=ineq._linexpr, b=sign * b))
-        return rows
+        return _model_rows(self._constraints, self._rhs)
 
     def _lowered(self):
-        objective = -self._objective if self._problem.sense == "minimize" else self._objective
-        problem = (objective.to_rust_affexpr(), self._inequalities())
-        arrays, order = rs.lower(*problem)
-        return problem, arrays, order
+        return _lower_model(self._problem.sense, self._objective, self._inequalities())
 
     def add_constraints(self, constraints) -> "Session":
         """Add one constraint or a list of constraints over variables the model already has.  Before
@@ -496,8 +521,7 @@ class Session:
                 raise KeyError("the constraint is not part of the session's model")
             if not isinstance(b, (int, float)):
                 raise TypeError("rhs maps a constraint to the number its normal form compares with")
-            # as a comparison forms it, b = -(constant of lhs - rhs): a written 0 arrives as -0.0
-            self._rhs[id(constraint)] = -(0.0 - float(b))
+            self._rhs[id(constraint)] = _normal_b(b)
 
     def solve(self, *, objective=None, rhs=None) -> Solution:
         """Solve the model with `objective` (a new expression in the problem's sense) and `rhs`
@@ -545,10 +569,7 @@ class Session:
             raise InfeasibleError("The model is infeasible")
         if res.status_code != _ffi.OPTIMAL:
             raise RuntimeError(f"simplex terminated with status {res.status!r} after {res.iterations} iterations")
-        by_var = dict(zip(res.basis.tolist(), res.x.tolist()))
-        values = {}
-        for i, v in enumerate(order):  # x+ - x- (src/simplex.rs:354-371)
-            values[v.id] = by_var.get(int(form.pos_var[i]), 0.0) - by_var.get(int(form.neg_var[i]), 0.0)
+        values = _user_values(res, form, order)
         return Solution(solution=rs.PySolution(res.objective, values, self.pivots[-1], res.numerics,
                                                (form.m + len(added), form.n + len(added))),
                         sense=self._problem.sense)
@@ -622,3 +643,124 @@ def solve_many(problems, *, duals: bool = False, ranging: bool = False, rays: bo
             else Solution(solution=r, sense=p.sense, constraints=list(p.constraints) if duals else None,
                           objective=p.objective if ranging else None)
             for p, r in zip(problems, raw)]
+
+
+class _BatchModel:
+    """One model of a SessionBatch: what it holds now and where its last solve ended."""
+    __slots__ = ("problem", "objective", "rhs", "form", "order", "last")
+
+
+def sessions(problems, **core_opts) -> "SessionBatch":
+    """A SessionBatch over `problems` (Minimize / Maximize models): the batched sibling of
+    Optimize.session()."""
+    return SessionBatch(problems, **core_opts)
+
+
+class SessionBatch:
+    """Many small models re-optimised together (dantzig_amd.sessions): the first solve() runs every
+    model from its slack basis in one STRICT batch, one workgroup per model; every later
+    solve(objectives=..., rhs=...) hands each model's last basis to the batch as its start
+    (core.solve_batch(start=...)), so that a model whose data moved a little takes the few pivots
+    from its last basis instead of all of them.  Changes accumulate, as in a Session.
+
+    A model is started cold again when its last solve ended singular or panicked, or when its change
+    alters more of the standard form than b, c and the constant.  The batch is stateless on the
+    device: nothing stays there between calls, the matrices are uploaded again on every call; what
+    is kept, on the host, is each model's last basis.  A re-optimised path is not the reference's
+    path from the slack basis: the promise is the optimum (or the verdict), not the pivots, and at a
+    degenerate optimum possibly another vertex.
+
+    `pivots` holds one list per call with one count per model, `cold` the number of models each call
+    started cold.  core_opts: fields of dzg_opts over rust.set_options()'s; numerics is STRICT (AUTO
+    means STRICT here).  ValueError for a model that does not go through the STRICT batch: more than
+    128 rows in standard form, or an integer variable."""
+
+    def __init__(self, problems, **core_opts) -> None:
+        problems = list(problems)
+        for i, p in enumerate(problems):
+            if not isinstance(p, Optimize):
+                raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
+        self._opts = {**rs._options, **core_opts}
+        if self._opts.get("numerics", core.AUTO) not in (core.STRICT, core.AUTO):
+            raise ValueError("sessions: the batch runs STRICT numerics only (numerics=STRICT or AUTO)")
+        self._models = []
+        for i, p in enumerate(problems):
+            st = _BatchModel()
+            st.problem, st.objective, st.rhs, st.last = p, p.objective, {}, None
+            st.form, st.order = self._lower(i, p, st.objective, st.rhs)
+            self._models.append(st)
+        self.pivots: list = []
+        self.cold: list = []
+
+    @staticmethod
+    def _lower(i: int, p: "Optimize", objective, rhs: dict):
+        problem, arrays, order = _lower_model(p.sense, objective, _model_rows(p.constraints, rhs))
+        if rs._has_integer(*problem):
+            raise ValueError(f"problems[{i}]: re-optimisation is not defined for a model with integer variables")
+        form = rs.standard_form(arrays)
+        if form.m > _ffi.BATCH_MAX_ROWS:
+            raise ValueError(f"problems[{i}]: {form.m} rows in standard form; the batch takes at most "
+                             f"{_ffi.BATCH_MAX_ROWS}")
+        return form, order
+
+    def __len__(self) -> int:
+        return len(self._models)
+
+    def _per_model(self, what, name: str) -> list:
+        if what is None:
+            return [None] * len(self._models)
+        what = list(what)
+        if len(what) != len(self._models):
+            raise ValueError(f"{name}: {len(what)} entries for {len(self._models)} models (None = unchanged)")
+        return what
+
+    def solve(self, objectives=None, rhs=None, return_exceptions: bool = False) -> list:
+        """Solve every model with objectives[i] (a new expression in model i's sense) and rhs[i]
+        ({constraint: new b}, as Session.solve takes it) replacing what the batch holds for it; None,
+        for one model or for the whole argument, means unchanged.  Returns one Solution per model,
+        values mapped as Session.solve maps them.  A model that ends unbounded or infeasible raises
+        UnboundedError / InfeasibleError with its index in the message once the whole batch is done;
+        with return_exceptions=True the exception stands in that model's place.  Either way the batch
+        stays usable.  KeyError / TypeError / ValueError for a bad change: nothing is changed then."""
+        objectives, rhs = self._per_model(objectives, "objectives"), self._per_model(rhs, "rhs")
+        staged = []
+        for i, st in enumerate(self._models):
+            objective = st.objective if objectives[i] is None else objectives[i].to_affexpr()
+            new_rhs = dict(st.rhs)
+            known = {id(c) for c in st.problem.constraints}
+            for constraint, b in (rhs[i] or {}).items():
+                if id(constraint) not in known:
+                    raise KeyError(f"rhs[{i}]: the constraint is not part of the model")
+                if not isinstance(b, (int, float)):
+                    raise TypeError("rhs maps a constraint to the number its normal form compares with")
+                new_rhs[id(constraint)] = _normal_b(b)
+            form, order = self._lower(i, st.problem, objective, new_rhs)
+            warm = (st.last is not None and st.last.status not in ("singular", "panic")
+                    and form.same_shape_as(st.form) and [v.id for v in order] == [v.id for v in st.order])
+            staged.append((objective, new_rhs, form, order, warm))
+        lps = [core.CoreLP(a=f.a, c=f.c, basis=f.basis, nonbasis=f.nonbasis, x=f.x, z=f.z, var_col=f.var_col,
+                           constant=f.constant) for _, _, f, _, _ in staged]
+        start = [st.last if warm else None for st, (_, _, _, _, warm) in zip(self._models, staged)]
+        results = core.solve_batch(lps, log=False, start=start if any(s is not None for s in start) else None,
+                                   **self._opts)
+        out = []
+        for i, (st, (objective, new_rhs, form, order, _), res) in enumerate(zip(self._models, staged, results)):
+            st.objective, st.rhs, st.form, st.order, st.last = objective, new_rhs, form, order, res
+            if res.status_code == _ffi.UNBOUNDED:
+                out.append(UnboundedError(f"The objective is unbounded (model {i})"))
+            elif res.status_code == _ffi.INFEASIBLE:
+                out.append(InfeasibleError(f"The model is infeasible (model {i})"))
+            elif res.status_code != _ffi.OPTIMAL:
+                out.append(RuntimeError(f"simplex terminated with status {res.status!r} after "
+                                        f"{res.iterations} iterations (model {i})"))
+            else:
+                out.append(Solution(solution=rs.PySolution(res.objective, _user_values(res, form, order),
+                                                           res.iterations, res.numerics, (form.m, form.n)),
+                                    sense=st.problem.sense))
+        self.pivots.append([r.iterations for r in results])
+        self.cold.append(sum(s is None for s in start))
+        if not return_exceptions:
+            for o in out:
+                if isinstance(o, Exception):
+                    raise o
+        return out

@@ -766,6 +766,45 @@ typedef struct {
  * call refactorises B'). */
 int dzg_solver_remove(dzg_solver *s, const dzg_remove *rem, int64_t *var_map, int64_t *row_map);
 
+/* ---- Batches re-optimised from their last bases (csrc/k_batch_restart.hip) ---------------- */
+
+/* The basis an LP of a batch starts from: typically res[i].basis / res[i].nonbasis of an earlier
+ * call on the same matrix. */
+typedef struct {
+    const int64_t *basis;     /* m,   NULL = start this LP cold */
+    const int64_t *nonbasis;  /* n-m                            */
+} dzg_batch_start;
+
+/* dzg_batch_solve (du == NULL) or dzg_batch_solve_duals (du != NULL) with a start basis per LP.
+ *   lps[i] is the LP to solve now, in the slack-basis form dzg_batch_solve takes: its basis is all
+ *   slack, so lps[i].x[p] is the right-hand side of the row whose slack sits at position p; c and
+ *   constant are the costs.  start[i] names the basis B (nonbasic set N) to start from.
+ *   An entry with start[i].basis == NULL, and every entry when start == NULL, is solved exactly as
+ *   dzg_batch_solve / dzg_batch_solve_duals solve it, bit for bit.  Cold and warm LPs mix freely;
+ *   an LP's result does not depend on its place in the batch.
+ * A warm LP gets dzg_solver_reoptimize's STRICT restart state before the first pivot, from one
+ * launch of k_batch_restart per bucket:
+ *   x = LU::solve(B, rhs);   z_k = a_{N_k} . y - c[N_k] with y = LU::solve(B^T, c_B), the d of
+ *   dzg_duals on the nonbasic positions, in the reference's operation order;   xbar = zbar = 1.0;
+ *   the pivot count and the log start at 0 for this call.
+ * The pivots that follow are the reference's from that state, bit for bit.  They are not the
+ * reference's pivots from the slack basis: the promise is the optimum (or the verdict), not the
+ * path.
+ * A start whose B or B^T meets a zero pivot anywhere in its factorisation (the last diagonal entry
+ * included), or whose restart x or z holds a non-finite entry, ends DZG_SINGULAR without a pivot:
+ * iterations = 0, basis / nonbasis as handed in.  The other LPs of the batch are not affected.
+ * Numerics: STRICT, or AUTO (= STRICT here); FAST is DZG_E_ARG.  Every check of dzg_batch_solve
+ * applies; beside them, on the host and before any device work, DZG_E_ARG with the LP's index in
+ * dzg_last_error: a warm LP whose own basis is not all slack, nonbasis == NULL beside a basis, a
+ * start that is not a partition of 0 .. n-1 into m and n-m distinct entries.
+ * Nothing stays on the device between calls: the matrices go up again every time. */
+int dzg_batch_solve_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                         const dzg_opts *opts, int64_t pivots_per_launch, dzg_result *res,
+                         dzg_duals *du);
+/* Device time (ms, between two events on the call's stream) of the k_batch_restart launches of the
+ * calling thread's last dzg_batch_solve_from; 0 when it had no warm LP. */
+double dzg_debug_batch_restart_ms(void);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
