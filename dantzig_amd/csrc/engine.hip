@@ -2304,6 +2304,120 @@ extern "C" int dzg_solver_result(dzg_solver *s, dzg_result *res)
     return 0;
 }
 
+// ---- what the calls on a finished solver share ---------------------------
+// s->du_c, s->du_rhs0, s->du_ctl and the zero pads of s->du_y mirror the handle's own data: filled once
+// by duals_workspace, the first two refreshed by restart_state, read by every call.  Anything else in
+// the scratch buffers a call uploads or computes itself before it reads it, but s->du_d, which
+// dzg_solver_ranging takes from the dzg_solver_duals call it makes.
+// The two refusals that depend on how the solver was created, placed by each caller where its order of
+// checks has them.  `unsupported`: the whole sentence where it is not "<what> is not supported ...".
+static int dense_one_gpu_only(const dzg_solver *s, const char *what, const char *unsupported = nullptr)
+{
+    if (s->d.csc || s->d.world > 1)
+        return fail(DZG_E_ARG, unsupported ? std::string(unsupported)
+                                           : std::string(what) + " is not supported on CSC storage or sharded solvers");
+    return 0;
+}
+
+static int fast_needs_workspace(const dzg_solver *s, const char *what)
+{
+    if (s->numerics == DZG_NUMERICS_FAST && !s->rf_piv)
+        return fail(DZG_E_ARG, std::string(what) + ": a FAST solver needs its refactorisation workspace: "
+                                                   "create it with opts.refactor_interval != 0");
+    return 0;
+}
+
+// a basis can be carried on from before a run and after any end but singular / panic
+static int carry_on_status_ok(const char *what, int status)
+{
+    if (status == DZG_SINGULAR || status == DZG_PANIC || status < 0 || status > DZG_NEAR_TIE)
+        return fail(DZG_E_ARG, std::string(what) + ": the solver's status is " + dzg_status_str(status) +
+                                   ": its basis cannot be carried on from");
+    return 0;
+}
+
+static int singular_block(const char *what, const char *which)
+{
+    return fail(DZG_E_DEVICE, std::string(what) + ": the " + which + " basis did not refactorise (singular block)");
+}
+
+// FAST: a fresh inverse of the current basis, the eta file emptied (s->h_ctl is current).  Where
+// k_ref_done met a singular block the status is put back on both sides: the solve's outcome stays.
+static int fresh_inverse(dzg_solver *s, const char *what, const char *which_basis)
+{
+    const int status = s->h_ctl->status;
+    TRY(refactor_now(s, true));
+    TRY(read_ctl(s));
+    if (s->h_ctl->status != status) {
+        HIP_OK(hipMemcpy(&s->d.ctl->status, &status, sizeof(int), hipMemcpyHostToDevice));
+        s->h_ctl->status = status;
+        return singular_block(what, which_basis);
+    }
+    return 0;
+}
+
+// the lists of the current basis on the host (one entry at least: data() is never NULL); codes: upload_codes
+struct BasisLists {
+    std::vector<int> basis, nonbasis, codes;
+};
+
+static int fetch_lists(dzg_solver *s, BasisLists &lists)
+{
+    const int m = s->d.m, q = s->d.q;
+    lists.basis.assign((size_t)(m ? m : 1), 0);
+    lists.nonbasis.assign((size_t)(q ? q : 1), 0);
+    if (m) HIP_OK(hipMemcpyAsync(lists.basis.data(), s->d.basis, sizeof(int) * m, hipMemcpyDeviceToHost, s->st));
+    if (q) HIP_OK(hipMemcpyAsync(lists.nonbasis.data(), s->d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost, s->st));
+    HIP_OK(hipStreamSynchronize(s->st));
+    return 0;
+}
+
+// STRICT: the column codes of the nonbasic variables, queued for s->du_codes (the sequential pricing pass
+// reads them) from lists.codes: the caller synchronises the stream before `lists` or that pass goes on
+static int upload_codes(dzg_solver *s, BasisLists &lists)
+{
+    const int q = s->d.q;
+    lists.codes.assign((size_t)(q ? q : 1), 0);
+    for (int k = 0; k < q; ++k) lists.codes[(size_t)k] = s->var_col_host[(size_t)lists.nonbasis[(size_t)k]];
+    if (q) HIP_OK(hipMemcpyAsync(s->du_codes, lists.codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, s->st));
+    return 0;
+}
+
+// STRICT: the copy of the device view that the LU kernels of every STRICT FTRAN / BTRAN run on here: its
+// control block is the scratch one, which reads DZG_RUNNING (the solver's own is left alone), v is s->du_y
+static DzgDev strict_view(const dzg_solver *s, double *dx)
+{
+    DzgDev dd = s->d;
+    dd.ctl = s->du_ctl;
+    dd.v = s->du_y;
+    dd.dx = dx;
+    return dd;
+}
+
+// init + sum (or - sum) of a[idx ? idx[i] : i] * b[i] in the reference's order: ascending, one rounded
+// product and one rounded sum or difference per element
+static double dot_reference_order(const std::vector<double> &a, const int *idx, const std::vector<double> &b,
+                                  int count, double init = 0.0, bool subtract = false)
+{
+    double acc = init;
+    for (int i = 0; i < count; ++i) {
+        const double prod = a[(size_t)(idx ? idx[i] : i)] * b[(size_t)i];
+        acc = subtract ? acc - prod : acc + prod;
+    }
+    return acc;
+}
+
+// (`count` runs of `len` entries, `ld` apart)
+static int finite_block(const char *prefix, const char *name, const double *v, int64_t len, int64_t count, int64_t ld)
+{
+    for (int64_t j = 0; v && j < count; ++j)
+        for (int64_t i = 0; i < len; ++i)
+            if (!std::isfinite(v[j * ld + i]))
+                return fail(DZG_E_ARG, std::string(prefix) + name + "[" + std::to_string(j * ld + i) +
+                                           "] is not finite");
+    return 0;
+}
+
 // ---- dual values and reduced costs at the optimum (k_duals.hip) -------------
 static int duals_workspace(dzg_solver *s)
 {
@@ -2341,25 +2455,27 @@ extern "C" int dzg_solver_duals(dzg_solver *s, dzg_duals *out)
     const DzgDev &d = s->d;
     const int m = d.m, q = d.q, n = d.n;
     hipStream_t st = s->st;
-    std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1));
+    BasisLists lists;
+    TRY(fetch_lists(s, lists));
+    const std::vector<int> &basis = lists.basis, &nonbasis = lists.nonbasis;
     std::vector<double> x((size_t)(m ? m : 1)), z((size_t)(q ? q : 1));
-    if (m) {
-        HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(x.data(), d.x, sizeof(double) * m, hipMemcpyDeviceToHost));
-    }
-    if (q) {
-        HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
-        HIP_OK(hipMemcpy(z.data(), d.z, sizeof(double) * q, hipMemcpyDeviceToHost));
-    }
-    double sum = 0.0; // objective_value as dzg_solver_result forms it
-    for (int p = 0; p < m; ++p) {
-        const double prod = s->c_host[(size_t)basis[p]] * x[p];
-        sum = sum + prod;
-    }
+    if (m) HIP_OK(hipMemcpy(x.data(), d.x, sizeof(double) * m, hipMemcpyDeviceToHost));
+    if (q) HIP_OK(hipMemcpy(z.data(), d.z, sizeof(double) * q, hipMemcpyDeviceToHost));
     out->reserved = 0;
-    out->primal_obj = s->constant + sum;
+    // objective_value as dzg_solver_result forms it
+    out->primal_obj = s->constant + dot_reference_order(s->c_host, basis.data(), x, m);
     std::vector<double> y((size_t)(m ? m : 1), 0.0), dv((size_t)(n ? n : 1), 0.0);
     double dmin = std::numeric_limits<double>::infinity(), dabs = 0.0, zdiff = 0.0, xmin = dmin, dot = 0.0;
+    const auto give = [&](int source) {
+        out->source = source;
+        out->dual_obj = s->constant + dot;
+        out->primal_infeas = std::max(0.0, -xmin);
+        out->dual_infeas = std::max(0.0, -dmin);
+        out->z_diff = zdiff / std::max(1.0, dabs); // (carried: 0)
+        if (out->y && m) std::memcpy(out->y, y.data(), sizeof(double) * m);
+        if (out->d && n) std::memcpy(out->d, dv.data(), sizeof(double) * n);
+        return 0;
+    };
 
     if (d.csc || d.world > 1) {
         // carried: the slack entries of z are the dual vector, z the reduced costs
@@ -2370,51 +2486,27 @@ extern "C" int dzg_solver_duals(dzg_solver *s, dzg_duals *out)
             dmin = std::min(dmin, z[k]);
         }
         for (int p = 0; p < m; ++p) xmin = std::min(xmin, x[p]);
-        for (int i = 0; i < m; ++i) {
-            const double prod = s->x0_host[(size_t)i] * y[(size_t)i];
-            dot = dot + prod;
-        }
-        out->source = DZG_DUALS_CARRIED;
-        out->dual_obj = s->constant + dot;
-        out->primal_infeas = std::max(0.0, -xmin);
-        out->dual_infeas = std::max(0.0, -dmin);
-        out->z_diff = 0.0;
-        if (out->y && m) std::memcpy(out->y, y.data(), sizeof(double) * m);
-        if (out->d && n) std::memcpy(out->d, dv.data(), sizeof(double) * n);
-        return 0;
+        dot = dot_reference_order(s->x0_host, nullptr, y, m);
+        return give(DZG_DUALS_CARRIED);
     }
 
     const bool fast = s->numerics == DZG_NUMERICS_FAST;
-    if (fast && !s->rf_piv)
-        return fail(DZG_E_ARG, "duals: a FAST solver needs its refactorisation workspace: create it "
-                               "with opts.refactor_interval != 0");
+    TRY(fast_needs_workspace(s, "duals"));
     TRY(duals_workspace(s));
     if (fast) {
-        // a fresh inverse of the final basis (the eta file emptied), then y by the two-stage scheme of
-        // the drift measurement on buffers of our own, then one column-wise pricing pass with y as v
-        TRY(refactor_now(s, true));
-        TRY(read_ctl(s));
-        if (s->h_ctl->status != DZG_OPTIMAL) { // k_ref_done met a singular block: the solve's outcome stays
-            const int keep = DZG_OPTIMAL;
-            HIP_OK(hipMemcpy(&d.ctl->status, &keep, sizeof(int), hipMemcpyHostToDevice));
-            s->h_ctl->status = keep;
-            return fail(DZG_E_DEVICE, "duals: the optimal basis did not refactorise (singular block)");
-        }
+        // on the fresh inverse y by the two-stage scheme of the drift measurement on buffers of our
+        // own, then one column-wise pricing pass with y as v
+        TRY(fresh_inverse(s, "duals", "optimal"));
         dzg_launch_drift_y(d, s->du_c, s->du_part, s->du_y, (int)s->h_ctl->ncompact, st);
         dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->du_dzy, st);
     } else {
-        // B^T y = c_B by the LU of every STRICT BTRAN, on a copy of the device view whose control block
-        // reads DZG_RUNNING and whose v is our own buffer; then neg_t_dot in the reference's order
+        // B^T y = c_B by the LU of every STRICT BTRAN, then neg_t_dot in the reference's order
         std::vector<double> cb((size_t)(m ? m : 1));
-        std::vector<int> codes((size_t)(q ? q : 1));
         for (int p = 0; p < m; ++p) cb[(size_t)p] = s->c_host[(size_t)basis[p]];
-        for (int k = 0; k < q; ++k) codes[(size_t)k] = s->var_col_host[(size_t)nonbasis[k]];
         if (m) HIP_OK(hipMemcpyAsync(s->du_y, cb.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
-        if (q) HIP_OK(hipMemcpyAsync(s->du_codes, codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, st));
-        HIP_OK(hipStreamSynchronize(st)); // (cb and codes are locals)
-        DzgDev dd = d;
-        dd.ctl = s->du_ctl;
-        dd.v = s->du_y;
+        TRY(upload_codes(s, lists));
+        HIP_OK(hipStreamSynchronize(st)); // (cb is a local)
+        const DzgDev dd = strict_view(s, d.dx);
         dzg_launch_strict_solve(dd, 1, st);
         dzg_launch_price_raw(DZG_PRICE_SEQ, m, d.lda, d.A, s->du_codes, q, s->du_y, s->du_dzy, st);
     }
@@ -2434,21 +2526,8 @@ extern "C" int dzg_solver_duals(dzg_solver *s, dzg_duals *out)
         xmin = std::min(xmin, r[3]);
         dot = dot + r[4];
     }
-    if (!fast) { // the reference's order: rows ascending, one rounded product and sum each
-        dot = 0.0;
-        for (int i = 0; i < m; ++i) {
-            const double prod = s->x0_host[(size_t)i] * y[(size_t)i];
-            dot = dot + prod;
-        }
-    }
-    out->source = DZG_DUALS_FRESH;
-    out->dual_obj = s->constant + dot;
-    out->primal_infeas = std::max(0.0, -xmin);
-    out->dual_infeas = std::max(0.0, -dmin);
-    out->z_diff = zdiff / std::max(1.0, dabs);
-    if (out->y && m) std::memcpy(out->y, y.data(), sizeof(double) * m);
-    if (out->d && n) std::memcpy(out->d, dv.data(), sizeof(double) * n);
-    return 0;
+    if (!fast) dot = dot_reference_order(s->x0_host, nullptr, y, m); // not the workgroups' sum: rows ascending
+    return give(DZG_DUALS_FRESH);
 }
 
 // "no duals": an LP that did not end OPTIMAL, or whose duals could not be computed (k_batch.hip and
@@ -2557,19 +2636,20 @@ extern "C" int dzg_solver_ranging(dzg_solver *s, const dzg_ranging_req *req, dzg
     TRY(read_ctl(s));
     if (s->h_ctl->status != DZG_OPTIMAL)
         return fail(DZG_E_ARG, "ranging: the solver's status is not DZG_OPTIMAL");
-    if (d.csc || d.world > 1)
-        return fail(DZG_E_ARG, "ranging is not supported on CSC storage or sharded solvers: a range cannot "
-                               "be read off the carried z");
+    TRY(dense_one_gpu_only(s, "ranging",
+                           "ranging is not supported on CSC storage or sharded solvers: a range cannot "
+                           "be read off the carried z"));
     dzg_duals tmp;
     std::memset(&tmp, 0, sizeof(tmp));
-    TRY(dzg_solver_duals(s, duals ? duals : &tmp)); // leaves the fresh d by variable in s->du_d
+    // (leaves the fresh d by variable in s->du_d and, FAST, the fresh inverse: all that is read of its scratch)
+    TRY(dzg_solver_duals(s, duals ? duals : &tmp));
     const double tol = req->pivot_tol == 0.0 ? 1e-9 : req->pivot_tol;
     const int nc = (int)req->ncost, nr = (int)req->nrhs;
     hipStream_t st = s->st;
 
-    std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1));
-    if (m) HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (q) HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
+    BasisLists lists;
+    TRY(fetch_lists(s, lists));
+    const std::vector<int> &basis = lists.basis, &nonbasis = lists.nonbasis;
     std::vector<int> where((size_t)(n ? n : 1), 0); // variable -> basis position p, or -1 - nonbasic position
     for (int p = 0; p < m; ++p) where[(size_t)basis[p]] = p;
     for (int k = 0; k < q; ++k) where[(size_t)nonbasis[k]] = -1 - k;
@@ -2638,15 +2718,14 @@ extern "C" int dzg_solver_ranging(dzg_solver *s, const dzg_ranging_req *req, dzg
         HIP_OK(hipGetLastError());
         HIP_OK(hipStreamSynchronize(st)); // (the CSR vectors are locals)
     } else {
-        // one LU solve of every STRICT FTRAN / BTRAN per direction, on the scratch control block of
-        // dzg_solver_duals; a cost direction also takes the sequential pricing pass
+        // one LU solve of every STRICT FTRAN / BTRAN per direction; a cost direction also takes the
+        // sequential pricing pass
         double *dxv = nullptr, *gn = nullptr;
         TRY(mem.get(&dxv, (size_t)m + 2)); TRY(mem.get(&gn, (size_t)q));
         TRY(mem.get(&part, (size_t)DZG_RANGE_BLOCKS));
-        DzgDev dd = d;
-        dd.ctl = s->du_ctl;
-        dd.v = s->du_y;
-        dd.dx = dxv;
+        TRY(upload_codes(s, lists));
+        HIP_OK(hipStreamSynchronize(st));
+        const DzgDev dd = strict_view(s, dxv);
         std::vector<double> hv((size_t)(m ? m : 1)), gv((size_t)(q ? q : 1));
         for (int i = 0; i < nc; ++i) {
             std::fill(hv.begin(), hv.end(), 0.0);
@@ -2736,18 +2815,15 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
     if (status != DZG_UNBOUNDED && status != DZG_INFEASIBLE)
         return fail(DZG_E_ARG, "ray: the solver's status is neither DZG_UNBOUNDED nor DZG_INFEASIBLE");
     const DzgDev &d = s->d;
-    if (d.csc || d.world > 1)
-        return fail(DZG_E_ARG, "rays are not supported on CSC storage or sharded solvers");
+    TRY(dense_one_gpu_only(s, "ray", "rays are not supported on CSC storage or sharded solvers"));
+    TRY(fast_needs_workspace(s, "ray"));
     const bool fast = s->numerics == DZG_NUMERICS_FAST;
-    if (fast && !s->rf_piv)
-        return fail(DZG_E_ARG, "ray: a FAST solver needs its refactorisation workspace: create it "
-                               "with opts.refactor_interval != 0");
     const int m = d.m, q = d.q, n = d.n;
     const bool primal = status == DZG_UNBOUNDED;
     hipStream_t st = s->st;
-    std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1));
-    if (m) HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
-    if (q) HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
+    BasisLists lists;
+    TRY(fetch_lists(s, lists));
+    const std::vector<int> &basis = lists.basis, &nonbasis = lists.nonbasis;
     const int len = primal ? q : m;
     std::vector<double> side((size_t)(len ? len : 1)), sidebar((size_t)(len ? len : 1));
     if (len) {
@@ -2766,17 +2842,11 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
         TRY(dev_alloc(s, &s->ry_part, (size_t)DZG_RAY_BLOCKS * DZG_RAY_PART)); // set last: "reserved"
     }
     if (fast) {
-        // a fresh inverse of the final basis (the eta file emptied): dx is a_j through its columns,
-        // y its row `pos` in row space, each refined once against a double-double residual (the
-        // explicit inverse alone loses |M| |a| eps where the entering column nearly cancels a basic
-        // one); dz one column-wise pricing pass with y as v
-        TRY(refactor_now(s, true));
-        TRY(read_ctl(s));
-        if (s->h_ctl->status != status) { // k_ref_done met a singular block: the solve's outcome stays
-            HIP_OK(hipMemcpy(&d.ctl->status, &status, sizeof(int), hipMemcpyHostToDevice));
-            s->h_ctl->status = status;
-            return fail(DZG_E_DEVICE, "ray: the final basis did not refactorise (singular block)");
-        }
+        // on the fresh inverse: dx is a_j through its columns, y its row `pos` in row space, each
+        // refined once against a double-double residual (the explicit inverse alone loses |M| |a| eps
+        // where the entering column nearly cancels a basic one); dz one column-wise pricing pass with
+        // y as v
+        TRY(fresh_inverse(s, "ray", "final"));
         const int k = (int)s->h_ctl->ncompact;
         if (primal) {
             dzg_launch_ray_rhs(m, d.A, d.lda, s->var_col_host[(size_t)var], s->ry_h, st);
@@ -2791,21 +2861,15 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
             dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->ry_vec, st);
         }
     } else {
-        // the LU of every STRICT FTRAN / BTRAN on a copy of the device view whose control block reads
-        // DZG_RUNNING (the solver's own reads UNBOUNDED / INFEASIBLE and is left alone), then
-        // neg_t_dot in the reference's order
-        DzgDev dd = d;
-        dd.ctl = s->du_ctl;
-        dd.v = s->du_y;
-        dd.dx = s->ry_vec;
+        // the LU of every STRICT FTRAN / BTRAN, then (Farkas) neg_t_dot in the reference's order: only
+        // that pass reads the column codes
+        const DzgDev dd = strict_view(s, s->ry_vec);
         if (primal) {
             dzg_launch_ray_rhs(m, d.A, d.lda, s->var_col_host[(size_t)var], s->ry_vec, st);
             dzg_launch_strict_solve(dd, 0, st);
         } else {
-            std::vector<int> codes((size_t)(q ? q : 1));
-            for (int k = 0; k < q; ++k) codes[(size_t)k] = s->var_col_host[(size_t)nonbasis[(size_t)k]];
-            if (q) HIP_OK(hipMemcpyAsync(s->du_codes, codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, st));
-            HIP_OK(hipStreamSynchronize(st)); // (codes is a local)
+            TRY(upload_codes(s, lists));
+            HIP_OK(hipStreamSynchronize(st));
             dzg_launch_ray_rhs(m, nullptr, 0, pos, s->du_y, st);
             dzg_launch_strict_solve(dd, 1, st);
             dzg_launch_price_raw(DZG_PRICE_SEQ, m, d.lda, d.A, s->du_codes, q, s->du_y, s->ry_vec, st);
@@ -2831,18 +2895,10 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
     double value;
     if (fast) {
         value = primal ? s->c_host[(size_t)var] - sum : sum;
-    } else if (primal) { // the reference's order: one rounded product and one rounded difference each
-        value = s->c_host[(size_t)var];
-        for (int p = 0; p < m; ++p) {
-            const double prod = s->c_host[(size_t)basis[(size_t)p]] * vec[(size_t)p];
-            value = value - prod;
-        }
+    } else if (primal) { // the reference's order: c_j less the products c_B[p] dx[p], one by one
+        value = dot_reference_order(s->c_host, basis.data(), vec, m, s->c_host[(size_t)var], true);
     } else {
-        value = 0.0;
-        for (int i = 0; i < m; ++i) {
-            const double prod = s->x0_host[(size_t)i] * vec[(size_t)i];
-            value = value + prod;
-        }
+        value = dot_reference_order(s->x0_host, nullptr, vec, m);
     }
     out->kind = primal ? DZG_RAY_PRIMAL : DZG_RAY_FARKAS;
     out->var = var;
@@ -2863,60 +2919,33 @@ extern "C" int dzg_solver_ray(dzg_solver *s, dzg_ray *out)
 static int restart_state(dzg_solver *s, const double *rhs, const double *c, const double *constant,
                          bool refine = false);
 
-static int reopt_finite(const char *name, const double *v, int64_t count)
-{
-    for (int64_t i = 0; v && i < count; ++i)
-        if (!std::isfinite(v[i]))
-            return fail(DZG_E_ARG, std::string("reoptimize: ") + name + "[" + std::to_string(i) + "] is not finite");
-    return 0;
-}
-
 extern "C" int dzg_solver_reoptimize(dzg_solver *s, const dzg_reopt *chg)
 {
     if (!s || !chg) return fail(DZG_E_ARG, "reoptimize: NULL argument");
     if (!chg->rhs && !chg->c && !chg->set_constant)
         return fail(DZG_E_ARG, "reoptimize: nothing to change (rhs and c are NULL, set_constant is 0)");
-    DzgDev &d = s->d;
-    const int m = d.m, n = d.n;
-    TRY(reopt_finite("rhs", chg->rhs, m));
-    TRY(reopt_finite("c", chg->c, n));
+    const int m = s->d.m, n = s->d.n;
+    TRY(finite_block("reoptimize: ", "rhs", chg->rhs, m, 1, m));
+    TRY(finite_block("reoptimize: ", "c", chg->c, n, 1, n));
     if (chg->set_constant && !std::isfinite(chg->constant))
         return fail(DZG_E_ARG, "reoptimize: constant is not finite");
-    if (d.csc || d.world > 1)
-        return fail(DZG_E_ARG, "reoptimize is not supported on CSC storage or sharded solvers");
-    const bool fast = s->numerics == DZG_NUMERICS_FAST;
-    if (fast && !s->rf_piv)
-        return fail(DZG_E_ARG, "reoptimize: a FAST solver needs its refactorisation workspace: create it "
-                               "with opts.refactor_interval != 0");
+    TRY(dense_one_gpu_only(s, "reoptimize"));
+    TRY(fast_needs_workspace(s, "reoptimize"));
     HIP_OK(hipSetDevice(s->opts.device));
     TRY(read_ctl(s));
-    DzgCtl *h = s->h_ctl;
-    const int status = h->status;
-    if (status == DZG_SINGULAR || status == DZG_PANIC || status < 0 || status > DZG_NEAR_TIE)
-        return fail(DZG_E_ARG, std::string("reoptimize: the solver's status is ") + dzg_status_str(status) +
-                                   ": its basis cannot be carried on from");
-    TRY(duals_workspace(s));
-    if (fast && !s->ro_ag) TRY(dev_alloc(s, &s->ro_ag, (size_t)m + 2));
-    if (fast) {
-        // a fresh inverse of the current basis first (the eta file emptied): if it cannot be had, nothing
-        // has changed.  The drift measurement is about a solve from the slack basis with the old data:
-        // off from here on (put back if the call fails)
-        double *const drift_ref = s->dr_b0;
-        s->dr_b0 = nullptr;
-        const int rrc = refactor_now(s, true);
-        if (rrc != 0) {
-            s->dr_b0 = drift_ref;
-            return rrc;
-        }
-        TRY(read_ctl(s));
-        if (h->status != status) { // k_ref_done met a singular block: the solve's outcome stays
-            HIP_OK(hipMemcpy(&d.ctl->status, &status, sizeof(int), hipMemcpyHostToDevice));
-            h->status = status;
-            s->dr_b0 = drift_ref;
-            return fail(DZG_E_DEVICE, "reoptimize: the current basis did not refactorise (singular block)");
-        }
-    }
-    return restart_state(s, chg->rhs, chg->c, chg->set_constant ? &chg->constant : nullptr);
+    TRY(carry_on_status_ok("reoptimize", s->h_ctl->status));
+    const double *constant = chg->set_constant ? &chg->constant : nullptr;
+    if (s->numerics != DZG_NUMERICS_FAST) return restart_state(s, chg->rhs, chg->c, constant);
+    // a fresh inverse first: if it cannot be had, nothing has changed.  The drift measurement is about a
+    // solve from the slack basis with the old data: off from here on, put back where the call fails with
+    // the data as they were: no inverse, or restart_state out of memory (it reserves before it writes;
+    // that now comes after the refactorisation: the same basis, only its eta file is empty)
+    double *const drift_ref = s->dr_b0;
+    s->dr_b0 = nullptr;
+    const int rrc = fresh_inverse(s, "reoptimize", "current");
+    const int rc = rrc != 0 ? rrc : restart_state(s, chg->rhs, chg->c, constant);
+    if (rrc != 0 || rc == DZG_E_NOMEM) s->dr_b0 = drift_ref;
+    return rc;
 }
 
 // The state of the current basis for new data (NULL: what the handle holds), written; FAST: the inverse
@@ -2953,26 +2982,20 @@ static int restart_state(dzg_solver *s, const double *rhs, const double *c, cons
         }
         if (q) dzg_launch_price_raw(DZG_PRICE_TREE, m, d.lda, d.A, d.nbcode, q, s->du_y, s->du_dzy, st);
     } else {
-        // the LU of every STRICT FTRAN / BTRAN on a copy of the device view whose control block reads
-        // DZG_RUNNING: B x = rhs in place in x, B^T y = c_B as dzg_solver_duals solves it, then
-        // neg_t_dot in the reference's order
-        std::vector<int> basis((size_t)(m ? m : 1)), nonbasis((size_t)(q ? q : 1)), codes((size_t)(q ? q : 1));
+        // the LU of every STRICT FTRAN / BTRAN: B x = rhs in place in x, B^T y = c_B as
+        // dzg_solver_duals solves it, then neg_t_dot in the reference's order
+        BasisLists lists;
+        TRY(fetch_lists(s, lists));
         std::vector<double> cb((size_t)(m ? m : 1)), ones((size_t)(m ? m : 1), 1.0);
-        if (m) HIP_OK(hipMemcpy(basis.data(), d.basis, sizeof(int) * m, hipMemcpyDeviceToHost));
-        if (q) HIP_OK(hipMemcpy(nonbasis.data(), d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost));
-        for (int p = 0; p < m; ++p) cb[(size_t)p] = s->c_host[(size_t)basis[(size_t)p]];
-        for (int k = 0; k < q; ++k) codes[(size_t)k] = s->var_col_host[(size_t)nonbasis[(size_t)k]];
+        for (int p = 0; p < m; ++p) cb[(size_t)p] = s->c_host[(size_t)lists.basis[(size_t)p]];
         if (m) {
             HIP_OK(hipMemcpyAsync(d.x, s->x0_host.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(d.xbar, ones.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
             HIP_OK(hipMemcpyAsync(s->du_y, cb.data(), sizeof(double) * m, hipMemcpyHostToDevice, st));
         }
-        if (q) HIP_OK(hipMemcpyAsync(s->du_codes, codes.data(), sizeof(int) * q, hipMemcpyHostToDevice, st));
-        HIP_OK(hipStreamSynchronize(st)); // (cb, ones and codes are locals)
-        DzgDev dd = d;
-        dd.ctl = s->du_ctl;
-        dd.dx = d.x;
-        dd.v = s->du_y;
+        TRY(upload_codes(s, lists));
+        HIP_OK(hipStreamSynchronize(st)); // (cb and ones are locals)
+        const DzgDev dd = strict_view(s, d.x);
         if (m) {
             dzg_launch_strict_solve(dd, 0, st);
             dzg_launch_strict_solve(dd, 1, st);
@@ -2996,17 +3019,6 @@ static int restart_state(dzg_solver *s, const double *rhs, const double *c, cons
 }
 
 // ---- rows and columns added to a live LP, re-optimised from its basis (k_extend.hip) ----
-// (a p x r block stored with leading dimension ld, p entries contiguous)
-static int extend_finite(const char *name, const double *v, int64_t len, int64_t count, int64_t ld)
-{
-    for (int64_t j = 0; v && j < count; ++j)
-        for (int64_t i = 0; i < len; ++i)
-            if (!std::isfinite(v[j * ld + i]))
-                return fail(DZG_E_ARG, std::string("extend: ") + name + "[" + std::to_string(j * ld + i) +
-                                           "] is not finite");
-    return 0;
-}
-
 // The successor's matrix (zeroed, lda' x n_struct'): the resident block re-laid, the new rows transposed
 // in from a staging block, the new columns by the path of dzg_solver_upload_columns.
 static int remove_fill_matrix(dzg_solver *s, const SuccessorSrc &src);
@@ -3039,8 +3051,7 @@ static int successor_fill_matrix(dzg_solver *s, const SuccessorSrc &src)
     return 0;
 }
 
-static int successor_begin(dzg_solver *s, const char *what, DzgCtl *h0, std::vector<int> &basis0,
-                           std::vector<int> &nonbasis0);
+static int successor_begin(dzg_solver *s, const char *what, DzgCtl *h0, BasisLists &lists0);
 static int successor_swap(dzg_solver *s, const dzg_lp &lp, const SuccessorSrc &src, const DzgCtl &h0,
                           const char *what);
 
@@ -3052,8 +3063,7 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
     if (p == 0 && r == 0) return fail(DZG_E_ARG, "extend: nothing to add (n_rows and n_cols are 0)");
     const int64_t m = s->d.m, n = s->d.n, ns = s->d.ns, q = s->d.q;
     const int64_t m2 = m + p, n2 = n + p + r, ns2 = ns + r, q2 = q + r;
-    if (s->d.csc || s->d.world > 1)
-        return fail(DZG_E_ARG, "extend is not supported on CSC storage or sharded solvers");
+    TRY(dense_one_gpu_only(s, "extend"));
     if (n2 >= (1ll << 31) - 64) return fail(DZG_E_ARG, "extend: index range");
     if (p > 0 && (!ext->rhs || (ns > 0 && !ext->rows)))
         return fail(DZG_E_ARG, "extend: n_rows > 0 needs rows and rhs");
@@ -3061,13 +3071,14 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
     if (r > 0 && (!ext->c_cols || (m2 > 0 && !ext->cols)))
         return fail(DZG_E_ARG, "extend: n_cols > 0 needs cols and c_cols");
     if (r > 0 && ext->ld_cols < m2) return fail(DZG_E_ARG, "extend: ld_cols < m + n_rows");
-    if (p > 0) TRY(extend_finite("rows", ext->rows, ns, p, ext->ld_rows));
-    if (p > 0) TRY(extend_finite("rhs", ext->rhs, p, 1, p));
-    if (r > 0) TRY(extend_finite("cols", ext->cols, m2, r, ext->ld_cols));
-    if (r > 0) TRY(extend_finite("c_cols", ext->c_cols, r, 1, r));
+    if (p > 0) TRY(finite_block("extend: ", "rows", ext->rows, ns, p, ext->ld_rows));
+    if (p > 0) TRY(finite_block("extend: ", "rhs", ext->rhs, p, 1, p));
+    if (r > 0) TRY(finite_block("extend: ", "cols", ext->cols, m2, r, ext->ld_cols));
+    if (r > 0) TRY(finite_block("extend: ", "c_cols", ext->c_cols, r, 1, r));
     DzgCtl h0;
-    std::vector<int> basis0, nonbasis0;
-    TRY(successor_begin(s, "extend", &h0, basis0, nonbasis0));
+    BasisLists lists0;
+    TRY(successor_begin(s, "extend", &h0, lists0));
+    const std::vector<int> &basis0 = lists0.basis, &nonbasis0 = lists0.nonbasis;
 
     // the extended LP on the host: everything but the matrix
     std::vector<int64_t> basis((size_t)(m2 ? m2 : 1)), nonbasis((size_t)(q2 ? q2 : 1)), var_col((size_t)(n2 ? n2 : 1));
@@ -3104,26 +3115,14 @@ extern "C" int dzg_solver_extend(dzg_solver *s, const dzg_extend *ext)
 // (everything but the matrix, which `src` names) built as a successor next to the live state, left in
 // restart_state's state with the counters and the log carried over, and swapped into the caller's
 // handle; any failure leaves `s` as it was.
-static int successor_begin(dzg_solver *s, const char *what, DzgCtl *h0, std::vector<int> &basis0,
-                           std::vector<int> &nonbasis0)
+static int successor_begin(dzg_solver *s, const char *what, DzgCtl *h0, BasisLists &lists0)
 {
-    const int64_t m = s->d.m, q = s->d.q;
-    if (s->numerics == DZG_NUMERICS_FAST && !s->rf_piv)
-        return fail(DZG_E_ARG, std::string(what) + ": a FAST solver needs its refactorisation workspace: "
-                                                   "create it with opts.refactor_interval != 0");
+    TRY(fast_needs_workspace(s, what));
     HIP_OK(hipSetDevice(s->opts.device));
     TRY(read_ctl(s));
     *h0 = *s->h_ctl;
-    if (h0->status == DZG_SINGULAR || h0->status == DZG_PANIC || h0->status < 0 || h0->status > DZG_NEAR_TIE)
-        return fail(DZG_E_ARG, std::string(what) + ": the solver's status is " + dzg_status_str(h0->status) +
-                                   ": its basis cannot be carried on from");
-    hipStream_t st = s->st;
-    basis0.assign((size_t)(m ? m : 1), 0);
-    nonbasis0.assign((size_t)(q ? q : 1), 0);
-    if (m) HIP_OK(hipMemcpyAsync(basis0.data(), s->d.basis, sizeof(int) * m, hipMemcpyDeviceToHost, st));
-    if (q) HIP_OK(hipMemcpyAsync(nonbasis0.data(), s->d.nonbasis, sizeof(int) * q, hipMemcpyDeviceToHost, st));
-    HIP_OK(hipStreamSynchronize(st));
-    return 0;
+    TRY(carry_on_status_ok(what, h0->status));
+    return fetch_lists(s, lists0);
 }
 
 static int successor_swap(dzg_solver *s, const dzg_lp &lp, const SuccessorSrc &src, const DzgCtl &h0,
@@ -3148,8 +3147,7 @@ static int successor_swap(dzg_solver *s, const dzg_lp &lp, const SuccessorSrc &s
         t->extend_ms[1] = ms_since(tr);
     }
     TRY(read_ctl(t));
-    if (t->h_ctl->status != DZG_RUNNING)
-        return fail(DZG_E_DEVICE, std::string(what) + ": the new basis did not refactorise (singular block)");
+    if (t->h_ctl->status != DZG_RUNNING) return singular_block(what, "new"); // (t goes: nothing to put back)
     t->extend_ms[0] = ms_since(t0) - t->extend_ms[1];
     // what carries on: the pivot count and everything counted per pivot, the log
     DzgCtl *h = t->h_ctl;
@@ -3242,8 +3240,7 @@ extern "C" int dzg_solver_remove(dzg_solver *s, const dzg_remove *rem, int64_t *
     if (p == 0 && r == 0) return fail(DZG_E_ARG, "remove: nothing to remove (n_rows and n_cols are 0)");
     if ((p > 0 && !rem->rows) || (r > 0 && !rem->cols))
         return fail(DZG_E_ARG, "remove: a count > 0 needs its list (NULL argument)");
-    if (s->d.csc || s->d.world > 1)
-        return fail(DZG_E_ARG, "remove is not supported on CSC storage or sharded solvers");
+    TRY(dense_one_gpu_only(s, "remove"));
     const int64_t m = s->d.m, n = s->d.n, ns = s->d.ns, q = s->d.q;
     std::vector<char> drop_row((size_t)m, 0), drop_col((size_t)ns, 0);
     TRY(remove_mark("rows", rem->rows, p, drop_row));
@@ -3252,8 +3249,9 @@ extern "C" int dzg_solver_remove(dzg_solver *s, const dzg_remove *rem, int64_t *
     if (m2 < 1 || ns2 < 1)
         return fail(DZG_E_ARG, "remove: at least one row and one structural column must stay");
     DzgCtl h0;
-    std::vector<int> basis0, nonbasis0;
-    TRY(successor_begin(s, "remove", &h0, basis0, nonbasis0));
+    BasisLists lists0;
+    TRY(successor_begin(s, "remove", &h0, lists0));
+    const std::vector<int> &basis0 = lists0.basis, &nonbasis0 = lists0.nonbasis;
 
     // what may go: a row whose slack is basic, a structural column whose variable is nonbasic
     const std::vector<int> &code0 = s->var_col_host;
