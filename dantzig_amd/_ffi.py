@@ -53,6 +53,7 @@ EXPORTS = [
     "dzg_debug_extend_ms",
     "dzg_solver_remove",
     "dzg_batch_solve_from", "dzg_debug_batch_restart_ms",
+    "dzg_batch_solve_fast_from", "dzg_debug_batch_fast_restart_ms",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -321,6 +322,10 @@ def lib() -> C.CDLL:
                                               C.c_void_p, C.c_void_p]
         _lib.dzg_debug_batch_restart_ms.restype = C.c_double
         _lib.dzg_debug_batch_restart_ms.argtypes = []
+        _lib.dzg_batch_solve_fast_from.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                                   C.c_int64, C.c_void_p]
+        _lib.dzg_debug_batch_fast_restart_ms.restype = C.c_double
+        _lib.dzg_debug_batch_fast_restart_ms.argtypes = []
         _lib.dzg_debug_matrix.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
         _lib.dzg_debug_matrix_rows.restype = C.c_int64
         _lib.dzg_debug_matrix_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]

@@ -895,7 +895,7 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
 
 
 def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
-                     refactor_every: int = 0, **opts) -> list:
+                     refactor_every: int = 0, start=None, **opts) -> list:
     """dzg_batch_solve_fast: every LP of `lps` in FAST numerics, one workgroup per LP with the
     explicit basis inverse in LDS, in one call.
 
@@ -905,7 +905,16 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
     same call; STRICT: solve_batch's path), near_tie_action, tie_tol, max_iter, epsilon.  Result i
     is LP i's CoreResult; `.numerics` says which numerics produced it, and near_ties, first_near_tie,
     min_margin, margins, max_pivot_error and refactors mean what they mean for a single FAST solve.
-    pivots_per_launch 0 = 128; refactor_every 0 = 64 pivots between two rebuilds of the inverse."""
+    pivots_per_launch 0 = 128; refactor_every 0 = 64 pivots between two rebuilds of the inverse.
+
+    start (dzg_batch_solve_fast_from): one entry per LP with the meaning solve_batch(start=...) gives
+    it -- None, a CoreResult of either numerics (one that ended singular or panicked counts as None)
+    or a (basis, nonbasis) pair; `lps[i]` is then the LP to solve now in slack-basis form.  A warm LP
+    gets the FAST restart state of its start basis (x = B^-1 rhs and fresh reduced costs from the
+    inverse a launch builds, xbar = zbar = 1) and is pivoted on from there; iterations and pivots
+    count from 0, refactors includes the restart's inversion.  A singular start basis ends
+    "singular" with 0 iterations in FAST; under AUTO the STRICT batch solves it, and every other LP
+    FAST gave up on, from the same start."""
     lps = list(lps)
     allowed = {"numerics", "near_tie_action", "tie_tol", "max_iter", "epsilon", "device"}
     unknown = set(opts) - allowed
@@ -916,11 +925,23 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
     if int(pivots_per_launch) < 0 or int(refactor_every) < 0:
         raise ValueError("solve_batch_fast: pivots_per_launch and refactor_every are >= 0")
 
-    def invoke(c_lps, count, o, res):
-        return _ffi.lib().dzg_batch_solve_fast(c_lps, C.c_int64(count), C.byref(o),
-                                               C.c_int64(int(pivots_per_launch)),
-                                               C.c_int64(int(refactor_every)), res)
-    return _batch_fast(lps, log, log_cap, opts, "dzg_batch_solve_fast", invoke)
+    if start is None:
+        def invoke(c_lps, count, o, res):
+            return _ffi.lib().dzg_batch_solve_fast(c_lps, C.c_int64(count), C.byref(o),
+                                                   C.c_int64(int(pivots_per_launch)),
+                                                   C.c_int64(int(refactor_every)), res)
+        return _batch_fast(lps, log, log_cap, opts, "dzg_batch_solve_fast", invoke)
+    starts = _batch_starts(lps, start)
+
+    def invoke_from(c_lps, count, o, res):
+        c_start = (_ffi.BatchStart * max(count, 1))()
+        for i, s in enumerate(starts):
+            if s is not None:
+                c_start[i].basis, c_start[i].nonbasis = ptr(s[0]), ptr(s[1])
+        return _ffi.lib().dzg_batch_solve_fast_from(c_lps, c_start, C.c_int64(count), C.byref(o),
+                                                    C.c_int64(int(pivots_per_launch)),
+                                                    C.c_int64(int(refactor_every)), res)
+    return _batch_fast(lps, log, log_cap, opts, "dzg_batch_solve_fast_from", invoke_from)
 
 
 def _batch_fast(lps, log, log_cap, opts, name, invoke) -> list:

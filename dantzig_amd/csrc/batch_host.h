@@ -9,6 +9,8 @@
 //                Layout places the packed arrays in one device arena; fill_upload() writes the part
 //                of the upload buffer that does not depend on the numerics
 //   rounds       run_rounds(): every live bucket, one readback of the bucket counters, swap the lists
+//   warm starts  start_valid(), warm_lists(), drop_from_first_round(): what the restart pass of
+//                either numerics needs around its own kernel
 //   results      HostView + unpack_common(): what both numerics report alike
 #pragma once
 
@@ -255,6 +257,43 @@ inline int64_t var_code(const dzg_lp &lp, int64_t v)
     return lp.var_col ? lp.var_col[v] : (v < lp.n_struct ? v : -1 - (v - lp.n_struct));
 }
 
+// A warm LP's own basis is all slack, one per row; its start is a partition of 0 .. n-1.
+inline bool start_valid(const dzg_lp &lp, const dzg_batch_start &s, std::string &why)
+{
+    if (!s.basis) return true;
+    const int64_t m = lp.m, n = lp.n;
+    if (n > m && !s.nonbasis) {
+        why = "start: nonbasis is NULL beside a basis";
+        return false;
+    }
+    std::vector<char> seen((size_t)m, 0);
+    for (int64_t p = 0; p < m; ++p) {
+        const int64_t code = var_code(lp, lp.basis[p]);
+        if (code >= 0 || seen[(size_t)(-1 - code)]) {
+            why = "start: the LP's own basis is not all slack (basis[" + std::to_string(p) + "])";
+            return false;
+        }
+        seen[(size_t)(-1 - code)] = 1;
+    }
+    seen.assign((size_t)n, 0);
+    for (int64_t k = 0; k < n; ++k) {
+        const int64_t v = k < m ? s.basis[k] : s.nonbasis[k - m];
+        if (v < 0 || v >= n || seen[(size_t)v]) {
+            why = "start: basis/nonbasis is not a partition of 0..n-1";
+            return false;
+        }
+        seen[(size_t)v] = 1;
+    }
+    return true;
+}
+
+inline bool any_warm(const dzg_batch_start *start, int count)
+{
+    for (int i = 0; start && i < count; ++i)
+        if (start[i].basis) return true;
+    return false;
+}
+
 // The descriptors, A, var_col, the starting state and the first round's lists (LP indices grouped by
 // bucket) into the upload buffer.  An LP with a start basis (start[i].basis != NULL, dzg_batch_solve_from)
 // goes up as k_batch_restart reads it: the start's basis and nonbasis, the right-hand side by
@@ -388,6 +427,52 @@ StatusLists lists_by_status(const int *status, const dzg_lp *lps, int count, Pre
         out.seg[(size_t)b + 1] = (int)out.list.size();
     }
     return out;
+}
+
+// ---- the restart pass of a warm batch (k_batch.hip and k_batch_fast.hip run one before the first
+// round): its lists and its clock
+
+// The LPs with a start basis, grouped by bucket, in batch order within a bucket.
+inline StatusLists warm_lists(const dzg_lp *lps, const dzg_batch_start *start, int count)
+{
+    StatusLists out;
+    for (int b = 0; b < kBuckets; ++b) {
+        for (int i = 0; i < count; ++i)
+            if (start[i].basis && bucket_of(lps[i].m) == b) out.list.push_back(i);
+        out.seg[(size_t)b + 1] = (int)out.list.size();
+    }
+    return out;
+}
+
+// Two events around the restart launches.
+struct Events {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    Events() = default;
+    Events(const Events &) = delete;
+    Events &operator=(const Events &) = delete;
+    ~Events()
+    {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+    }
+};
+
+// The first round's lists (the host's copy, as fill_upload wrote it) without the LPs that gone(i)
+// names, in the order they had; `live` follows and the lists go up again.
+template <class Gone>
+int drop_from_first_round(unsigned char *host, unsigned char *dev, const Layout &L, const Packed &P,
+                          std::array<int, kBuckets> &live, hipStream_t st, Gone gone)
+{
+    int *list = (int *)(host + L.list);
+    const Segments seg = segments(P.bucket_n);
+    for (int b = 0; b < kBuckets; ++b) {
+        int n = 0;
+        for (int k = seg[(size_t)b]; k < seg[(size_t)b + 1]; ++k)
+            if (!gone(list[k])) list[seg[(size_t)b] + n++] = list[k];
+        live[(size_t)b] = n;
+    }
+    DZG_HIP(hipMemcpyAsync(dev + L.list, list, sizeof(int) * L.N, hipMemcpyHostToDevice, st));
+    return 0;
 }
 
 // ---- results

@@ -211,16 +211,11 @@ int restart_pass(Ctx &C, std::array<int, kBuckets> &live)
 {
     unsigned char *dev = C.D.arena;
     hipStream_t st = C.D.st;
-    std::vector<int> warm;
-    bh::Segments wseg{};
-    for (int b = 0; b < kBuckets; ++b) {
-        for (int i = 0; i < C.N; ++i)
-            if (C.is_warm(i) && bh::bucket_of(C.lps[i].m) == b) warm.push_back(i);
-        wseg[(size_t)b + 1] = (int)warm.size();
-    }
+    const bh::StatusLists warm = bh::warm_lists(C.lps, C.start, C.N);
+    const bh::Segments &wseg = warm.seg;
     // the next round's list is free until the first round appends to it
     int *wlist = (int *)(dev + C.L.list2);
-    DZG_HIP(hipMemcpyAsync(wlist, warm.data(), sizeof(int) * warm.size(), hipMemcpyHostToDevice, st));
+    DZG_HIP(hipMemcpyAsync(wlist, warm.list.data(), sizeof(int) * warm.list.size(), hipMemcpyHostToDevice, st));
     DzgBatchRestartArgs a;
     a.lp = C.g.lp;
     a.A = C.g.A;
@@ -233,14 +228,7 @@ int restart_pass(Ctx &C, std::array<int, kBuckets> &live)
     a.zbar = C.g.zbar;
     a.c = (const double *)(dev + C.c);
     a.status = C.g.status;
-    struct Events {
-        hipEvent_t e0 = nullptr, e1 = nullptr;
-        ~Events()
-        {
-            if (e0) (void)hipEventDestroy(e0);
-            if (e1) (void)hipEventDestroy(e1);
-        }
-    } ev;
+    bh::Events ev;
     DZG_HIP(hipEventCreate(&ev.e0));
     DZG_HIP(hipEventCreate(&ev.e1));
     DZG_HIP(hipEventRecord(ev.e0, st));
@@ -259,17 +247,9 @@ int restart_pass(Ctx &C, std::array<int, kBuckets> &live)
     DZG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
     t_restart_ms = ms;
     if (std::all_of(status.begin(), status.end(), [](int s) { return s == DZG_RUNNING; })) return 0;
-    // the first round's lists without the singular starts, in the order fill_upload gave them
-    int *list = (int *)(C.host.data() + C.L.list);
-    const bh::Segments seg = bh::segments(C.P.bucket_n);
-    for (int b = 0; b < kBuckets; ++b) {
-        int n = 0;
-        for (int k = seg[(size_t)b]; k < seg[(size_t)b + 1]; ++k)
-            if (status[(size_t)list[k]] == DZG_RUNNING) list[seg[(size_t)b] + n++] = list[k];
-        live[(size_t)b] = n;
-    }
-    DZG_HIP(hipMemcpyAsync(dev + C.L.list, list, sizeof(int) * C.N, hipMemcpyHostToDevice, st));
-    return 0;
+    // the first round's lists without the singular starts
+    return bh::drop_from_first_round(C.host.data(), dev, C.L, C.P, live, st,
+                                     [&](int i) { return status[(size_t)i] != DZG_RUNNING; });
 }
 
 // ---- duals of the LPs that ended OPTIMAL: one workgroup each, bucket by bucket
@@ -535,36 +515,6 @@ void write_results(const Ctx &C)
 // move), what `ex` asks for: the duals of the LPs that end OPTIMAL (k_duals.hip), their ranges
 // (k_ranging.hip, which reads the duals' fresh d), the rays of the LPs that end UNBOUNDED or
 // INFEASIBLE (k_rays.hip).
-// A warm LP's own basis is all slack, one per row; its start is a partition of 0 .. n-1.
-static bool start_valid(const dzg_lp &lp, const dzg_batch_start &s, std::string &why)
-{
-    if (!s.basis) return true;
-    const int64_t m = lp.m, n = lp.n;
-    if (n > m && !s.nonbasis) {
-        why = "start: nonbasis is NULL beside a basis";
-        return false;
-    }
-    std::vector<char> seen((size_t)m, 0);
-    for (int64_t p = 0; p < m; ++p) {
-        const int64_t code = bh::var_code(lp, lp.basis[p]);
-        if (code >= 0 || seen[(size_t)(-1 - code)]) {
-            why = "start: the LP's own basis is not all slack (basis[" + std::to_string(p) + "])";
-            return false;
-        }
-        seen[(size_t)(-1 - code)] = 1;
-    }
-    seen.assign((size_t)n, 0);
-    for (int64_t k = 0; k < n; ++k) {
-        const int64_t v = k < m ? s.basis[k] : s.nonbasis[k - m];
-        if (v < 0 || v >= n || seen[(size_t)v]) {
-            why = "start: basis/nonbasis is not a partition of 0..n-1";
-            return false;
-        }
-        seen[(size_t)v] = 1;
-    }
-    return true;
-}
-
 static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, int64_t pivots_per_launch,
                        dzg_result *res, BatchExtras ex, const dzg_batch_start *start = nullptr)
 {
@@ -587,7 +537,7 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
         return dzg_set_error(DZG_E_ARG, "batch: STRICT numerics only (FAST is not batched)");
     const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
     const int rc_lps = bh::check_batch(lps, count, [&](int64_t i, std::string &why) {
-        if (start && !start_valid(lps[i], start[i], why)) return false;
+        if (start && !bh::start_valid(lps[i], start[i], why)) return false;
         return !ex.ranging || dzg_ranging_req_valid(&ex.req[i], lps[i].m, lps[i].n, why);
     });
     if (rc_lps) return rc_lps;

@@ -4,6 +4,8 @@
 // of the LP's own: margins, near_ties, first_near_tie, min_margin and the STOP / COUNT actions mean
 // what they mean in the single-LP FAST solver.  dzg_batch_solve_fast with AUTO numerics runs STOP and
 // hands every LP that ends DZG_NEAR_TIE, DZG_SINGULAR or DZG_PANIC to the STRICT batch (k_batch.hip).
+// dzg_batch_solve_fast_from starts the LPs that come with a basis from that basis: k_batch_fast_restart
+// (below) gives each of them its restart state before the first round.
 //
 //   layout      W[p * ld + r] = (B^-1)[basis position p][constraint row r], ld = m | 1.  BTRAN reads
 //               row p with lanes along r (contiguous); FTRAN gives every thread a row and walks the
@@ -472,7 +474,167 @@ __global__ __launch_bounds__(BLOCK) void k_batch_fast(FArgs g, const int *__rest
     }
 }
 
+// sum_j a[j * stride] * b[j] in ftran's order: four interleaved partial sums, j ascending, then
+// (s0 + s1) + (s2 + s3); every product rounded before it is added
+__device__ __forceinline__ double dot4(const double *a, int stride, const double *b, int m)
+{
+    double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+    int j = 0;
+    for (; j + 3 < m; j += 4) {
+        s0 = s0 + a[j * stride] * b[j];
+        s1 = s1 + a[(j + 1) * stride] * b[j + 1];
+        s2 = s2 + a[(j + 2) * stride] * b[j + 2];
+        s3 = s3 + a[(j + 3) * stride] * b[j + 3];
+    }
+    if (j < m) s0 = s0 + a[j * stride] * b[j];
+    if (j + 1 < m) s1 = s1 + a[(j + 1) * stride] * b[j + 1];
+    if (j + 2 < m) s2 = s2 + a[(j + 2) * stride] * b[j + 2];
+    return (s0 + s1) + (s2 + s3);
+}
+
+// The restart state of a warm LP (dzg_batch_solve_fast_from): what
+// dzg_solver_reoptimize leaves in FAST numerics, from the inverse k_batch_fast builds at step 0.
+//
+//      W   = build_inverse(B)                           the start's basis, as it lies in global memory
+//      x_i = sum_j W[i][j] rhs[j]                       rhs by constraint row (fill_upload left it in x)
+//      y_r = sum_p W[p][r] c[basis[p]]                  one thread per r: a wave reads a row of W
+//      z_k = -dz_k - c[N_k],  dz = price(v = y)         stored entries only; a slack is one negation
+//      xbar = zbar = 1
+//
+// One workgroup per warm LP, once, before the first round; k_batch_fast's LDS carve-up (y lies in dx,
+// rhs and then c_B in acol).  Both sums run in dot4's order, which depends on m alone.  No refinement
+// step.  A zero or non-finite pivot of the inversion, or a non-finite entry of x or z, ends the LP:
+// DZG_SINGULAR in its control block and in status[id], the array the host reads back before the
+// first round (a control block is 50 times an int).
+template <int BLOCK, int PL>
+__global__ __launch_bounds__(BLOCK) void k_batch_fast_restart(FArgs g, const double *__restrict__ cost,
+                                                              int *__restrict__ status,
+                                                              const int *__restrict__ list)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_mem[];
+    const int id = list[blockIdx.x];
+    const DzgBatchLp L = g.lp[id];
+    const int m = L.m, q = L.n - L.m, mmax = g.mmax;
+    const int ld = m | 1;
+    double *W = s_mem;
+    double *acol = s_mem + (long long)mmax * (mmax + 1);
+    double *ys = acol + mmax;
+    DzgCtl *sc = (DzgCtl *)(ys + mmax); // not used here: the carve-up is k_batch_fast's
+    int *piv = (int *)((char *)sc + kCtlBytes);
+    int *s_flag = piv + mmax; // [0], [1]: build_inverse's; [2]: a non-finite entry of x or z
+    const double *A = g.A + L.a_off;
+    const int *var_col = g.var_col + L.vc_off;
+    const int *basis = g.basis + L.m_off, *nonbasis = g.nonbasis + L.q_off;
+    const double *c = cost + L.vc_off;
+    double *x = g.x + L.m_off, *xbar = g.xbar + L.m_off;
+    double *z = g.z + L.q_off, *zbar = g.zbar + L.q_off, *dz = g.dz + L.q_off;
+    FState *gs = g.state + id;
+    const bool lead = threadIdx.x == 0;
+
+    if (lead) s_flag[2] = 0;
+    int inverted = 0;
+    const int bad = m > 0 ? build_inverse<BLOCK, PL>(W, ld, m, A, var_col, basis, acol, piv, s_flag, inverted) : 0;
+    if (lead) gs->refactors = inverted;
+    if (bad) {
+        if (lead) gs->ctl.status = status[id] = DZG_SINGULAR;
+        return;
+    }
+    for (int i = threadIdx.x; i < m; i += BLOCK) acol[i] = x[i];
+    __syncthreads();
+    for (int i = threadIdx.x; i < m; i += BLOCK) {
+        const double xi = dot4(W + i * ld, 1, acol, m);
+        x[i] = xi;
+        xbar[i] = 1.0;
+        if (isinf(xi) || isnan(xi)) s_flag[2] = 1;
+    }
+    __syncthreads(); // rhs is read
+    for (int p = threadIdx.x; p < m; p += BLOCK) acol[p] = c[basis[p]];
+    __syncthreads();
+    for (int r = threadIdx.x; r < m; r += BLOCK) ys[r] = dot4(W + r, ld, acol, m);
+    __syncthreads();
+    DzgCand2 unused = dzg_cand2_none();
+    price<BLOCK, PL, false>(ys, m, q, A, var_col, nonbasis, dz, z, zbar, 0.0, 0.0, unused);
+    __syncthreads(); // dz (global) is complete
+    for (int k = threadIdx.x; k < q; k += BLOCK) {
+        const double zk = -dz[k] - c[nonbasis[k]];
+        z[k] = zk;
+        zbar[k] = 1.0;
+        if (isinf(zk) || isnan(zk)) s_flag[2] = 1;
+    }
+    __syncthreads();
+    if (lead && s_flag[2]) gs->ctl.status = status[id] = DZG_SINGULAR;
+}
+
 namespace bh = dzg_bh;
+
+// The warm LPs list[0..n) of row bucket b, one workgroup each: launch_bucket's instantiations and LDS
+void launch_restart_bucket(int b, const FArgs &g, const double *cost, int *status, const int *list, int n,
+                           hipStream_t st)
+{
+    const size_t lds = fast_lds_bytes(g.mmax);
+    if (b == 3) { // more than 64 KiB of dynamic LDS, as in launch_bucket
+        static const hipError_t attr =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_batch_fast_restart<256, 64>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)fast_lds_bytes(DZG_BATCH_MAX_ROWS));
+        (void)attr;
+    }
+    bh::for_each_chunk(b, n, [&](int c0, int grid) {
+        const dim3 block(bh::kBlock[b]);
+        if (b == 0)
+            hipLaunchKernelGGL((k_batch_fast_restart<64, 16>), dim3(grid), block, lds, st, g, cost, status,
+                               list + c0);
+        else if (b == 1)
+            hipLaunchKernelGGL((k_batch_fast_restart<64, 32>), dim3(grid), block, lds, st, g, cost, status,
+                               list + c0);
+        else if (b == 2)
+            hipLaunchKernelGGL((k_batch_fast_restart<128, 64>), dim3(grid), block, lds, st, g, cost, status,
+                               list + c0);
+        else
+            hipLaunchKernelGGL((k_batch_fast_restart<256, 64>), dim3(grid), block, lds, st, g, cost, status,
+                               list + c0);
+    });
+}
+
+thread_local double t_restart_ms = 0.0; // dzg_debug_batch_fast_restart_ms
+
+// ---- the restart state of the warm LPs: c goes up, one workgroup each, bucket by bucket, before the
+// first round.  A singular start leaves the first round's lists; `live` follows.
+int restart_pass(const dzg_lp *lps, const dzg_batch_start *start, const bh::Packed &P, const bh::Layout &L,
+                 unsigned char *host, unsigned char *dev, size_t s_c, size_t s_status, const FArgs &g,
+                 hipStream_t st, std::array<int, bh::kBuckets> &live)
+{
+    const int N = L.N;
+    std::vector<double> cost((size_t)P.nvc);
+    for (int i = 0; i < N; ++i)
+        std::copy(lps[i].c, lps[i].c + lps[i].n, cost.begin() + P.desc[(size_t)i].vc_off);
+    DZG_HIP(hipMemcpyAsync(dev + s_c, cost.data(), sizeof(double) * cost.size(), hipMemcpyHostToDevice, st));
+    const bh::StatusLists warm = bh::warm_lists(lps, start, N);
+    // the next round's list is free until the first round appends to it
+    int *wlist = (int *)(dev + L.list2);
+    DZG_HIP(hipMemcpyAsync(wlist, warm.list.data(), sizeof(int) * warm.list.size(), hipMemcpyHostToDevice, st));
+    bh::Events ev;
+    DZG_HIP(hipEventCreate(&ev.e0));
+    DZG_HIP(hipEventCreate(&ev.e1));
+    DZG_HIP(hipEventRecord(ev.e0, st));
+    for (int b = 0; b < bh::kBuckets; ++b) {
+        const int cnt = warm.seg[(size_t)b + 1] - warm.seg[(size_t)b];
+        if (cnt == 0) continue;
+        FArgs gb = g;
+        gb.mmax = P.mmax[b];
+        launch_restart_bucket(b, gb, (const double *)(dev + s_c), (int *)(dev + s_status),
+                              wlist + warm.seg[(size_t)b], cnt, st);
+        DZG_HIP(hipGetLastError());
+    }
+    DZG_HIP(hipEventRecord(ev.e1, st));
+    int *status = (int *)(host + s_status);
+    DZG_HIP(hipMemcpyAsync(status, dev + s_status, sizeof(int) * N, hipMemcpyDeviceToHost, st));
+    DZG_HIP(hipStreamSynchronize(st)); // (cost and the lists are uploaded: they may go)
+    float ms = 0.0f;
+    DZG_HIP(hipEventElapsedTime(&ms, ev.e0, ev.e1));
+    t_restart_ms = ms;
+    if (std::all_of(status, status + N, [](int s) { return s == DZG_RUNNING; })) return 0;
+    return bh::drop_from_first_round(host, dev, L, P, live, st, [&](int i) { return status[i] != DZG_RUNNING; });
+}
 
 template <bool DUMP>
 void launch_bucket(int b, const FArgs &g, const int *list, int n, int *next_list, int *next_count,
@@ -550,10 +712,15 @@ void write_fast(const dzg_lp &lp, const DzgBatchLp &d, const FState &fs, const i
 // With w_out (dzg_debug_batch_fast_inverse) the budget is `pivots_per_launch` pivots in one launch of
 // the DUMP instantiations: iter_stop is that budget and the launch has one step more, so that
 // fast_status ends it -- after W was built, also when the budget is 0 -- and W comes down with the state.
-static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o, int64_t pivots_per_launch,
-                            int64_t refactor_every_arg, dzg_result *res, double *w_out = nullptr)
+// An LP with a start basis (dzg_batch_solve_fast_from) is laid out by fill_upload as k_batch_fast_restart
+// reads it and gets its restart state from one launch per bucket between the upload and the first round;
+// c (by variable) goes up behind the solve's sections, for those launches alone.
+static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int64_t count, const dzg_opts &o,
+                            int64_t pivots_per_launch, int64_t refactor_every_arg, dzg_result *res,
+                            double *w_out = nullptr)
 {
     const bool dump = w_out != nullptr;
+    const bool warm = bh::any_warm(start, (int)count);
     const long long max_iter = dump ? std::min<int64_t>(pivots_per_launch, 1 << 30)
                                     : (o.max_iter > 0 ? o.max_iter : 10000000);
     if (const int rc = bh::use_device(o.device)) return rc;
@@ -563,17 +730,20 @@ static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o,
     bh::Layout L(P);
     const size_t s_state = L.ar.add(sizeof(FState) * N);
     const size_t s_woff = L.ar.add(dump ? sizeof(long long) * N : 0);
+    const size_t s_rst = L.ar.add(warm ? sizeof(int) * N : 0); // the restart's statuses: DZG_RUNNING
     L.end_upload();
     const size_t s_lmg = L.ar.add(sizeof(double) * P.nlog);
     std::vector<long long> w_off((size_t)N + 1, 0);
     for (int i = 0; i < N; ++i) w_off[(size_t)i + 1] = w_off[(size_t)i] + (long long)lps[i].m * lps[i].m;
     const size_t s_w = L.ar.add(dump ? sizeof(double) * (size_t)w_off[(size_t)N] : 0);
     L.end_download();
+    const size_t s_c = L.ar.add(warm ? sizeof(double) * (size_t)P.nvc : 0);
 
     std::vector<unsigned char> host(L.download_end, 0);
-    bh::fill_upload(host.data(), L, P, lps);
+    bh::fill_upload(host.data(), L, P, lps, start);
     FState *fs = (FState *)(host.data() + s_state);
     for (int i = 0; i < N; ++i) start_ctl(fs[i].ctl, o, max_iter);
+    if (warm) std::fill_n((int *)(host.data() + s_rst), N, (int)DZG_RUNNING);
     if (dump) std::memcpy(host.data() + s_woff, w_off.data(), sizeof(long long) * N);
     bh::Device D;
     if (const int rc = bh::upload(D, L, host.data())) return rc;
@@ -590,9 +760,12 @@ static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o,
     g.refactor_every = (int)(refactor_every_arg > 0 ? std::min<int64_t>(refactor_every_arg, 1 << 30)
                                                     : DZG_BATCH_FAST_DEFAULT_REFACTOR);
     g.mmax = 0;
+    std::array<int, bh::kBuckets> live = bh::live_of(P.bucket_n);
+    if (warm)
+        if (const int rc = restart_pass(lps, start, P, L, host.data(), dev, s_c, s_rst, g, D.st, live)) return rc;
     const int rc_rounds = bh::run_rounds(
         (int *)(dev + L.list), (int *)(dev + L.list2), (int *)(dev + L.count), bh::segments(P.bucket_n),
-        bh::live_of(P.bucket_n), D.st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
+        live, D.st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
             FArgs gb = g;
             gb.mmax = P.mmax[b];
             if (dump)
@@ -617,9 +790,11 @@ static int batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts &o,
     return 0;
 }
 
-extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
-                                    int64_t pivots_per_launch, int64_t refactor_every, dzg_result *res)
+extern "C" int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                                         const dzg_opts *opts, int64_t pivots_per_launch,
+                                         int64_t refactor_every, dzg_result *res)
 {
+    t_restart_ms = 0.0;
     // ---- host checks first: malformed input is DZG_E_ARG on any machine
     if (const int rc = bh::check_batch(lps, count, res, pivots_per_launch)) return rc;
     if (refactor_every < 0) return dzg_set_error(DZG_E_ARG, "batch: refactor_every < 0");
@@ -627,15 +802,20 @@ extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_
     if (opts) o = *opts; else dzg_opts_default(&o);
     if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_FAST && o.numerics != DZG_NUMERICS_AUTO)
         return dzg_set_error(DZG_E_ARG, "batch: opts.numerics");
-    if (o.numerics == DZG_NUMERICS_STRICT) return dzg_batch_solve(lps, count, &o, pivots_per_launch, res);
-    if (const int rc = bh::check_batch(lps, count)) return rc;
+    if (o.numerics == DZG_NUMERICS_STRICT)
+        return dzg_batch_solve_from(lps, start, count, &o, pivots_per_launch, res, nullptr);
+    const int rc_lps = bh::check_batch(lps, count, [&](int64_t i, std::string &why) {
+        return !start || bh::start_valid(lps[i], start[i], why);
+    });
+    if (rc_lps) return rc_lps;
     if (count == 0) return 0;
     const bool is_auto = o.numerics == DZG_NUMERICS_AUTO;
     if (is_auto) o.near_tie_action = DZG_NEAR_TIE_STOP;
-    const int rc = batch_solve_fast(lps, count, o, pivots_per_launch, refactor_every, res);
+    const int rc = batch_solve_fast(lps, start, count, o, pivots_per_launch, refactor_every, res);
     if (rc < 0 || !is_auto) return rc;
     // ---- AUTO: only the reference's own arithmetic can arbitrate a tie -- the LPs FAST gave up on
-    // are solved again from their first pivot by the STRICT batch, into the same result slots
+    // are solved again by the STRICT batch, each from the start it had here (a cold one from its
+    // first pivot), into the same result slots
     std::vector<int64_t> redo;
     for (int64_t i = 0; i < count; ++i)
         if (res[i].status == DZG_NEAR_TIE || res[i].status == DZG_SINGULAR || res[i].status == DZG_PANIC)
@@ -643,17 +823,27 @@ extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_
     if (redo.empty()) return 0;
     std::vector<dzg_lp> lps2(redo.size());
     std::vector<dzg_result> res2(redo.size());
+    std::vector<dzg_batch_start> start2(redo.size(), dzg_batch_start{nullptr, nullptr});
     for (size_t k = 0; k < redo.size(); ++k) {
         lps2[k] = lps[redo[k]];
         res2[k] = res[redo[k]];
+        if (start) start2[k] = start[redo[k]];
     }
     dzg_opts os = o;
     os.numerics = DZG_NUMERICS_STRICT;
-    const int rc2 = dzg_batch_solve(lps2.data(), (int64_t)redo.size(), &os, 0, res2.data());
+    const int rc2 = dzg_batch_solve_from(lps2.data(), start2.data(), (int64_t)redo.size(), &os, 0, res2.data(), nullptr);
     if (rc2 < 0) return rc2;
     for (size_t k = 0; k < redo.size(); ++k) res[redo[k]] = res2[k];
     return 0;
 }
+
+extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                                    int64_t pivots_per_launch, int64_t refactor_every, dzg_result *res)
+{
+    return dzg_batch_solve_fast_from(lps, nullptr, count, opts, pivots_per_launch, refactor_every, res);
+}
+
+extern "C" double dzg_debug_batch_fast_restart_ms(void) { return t_restart_ms; }
 
 // Test hook (tests/test_gpu_batch_fast_inverse.py): the W = B^-1 a FAST batch launch keeps in LDS.
 // Every LP's W is built from its starting basis as a launch builds it at step 0, at most `pivots`
@@ -671,5 +861,5 @@ extern "C" int dzg_debug_batch_fast_inverse(const dzg_lp *lps, int64_t count, co
         return dzg_set_error(DZG_E_ARG, "dzg_debug_batch_fast_inverse: FAST numerics only");
     if (const int rc = bh::check_batch(lps, count)) return rc;
     if (count == 0) return 0;
-    return batch_solve_fast(lps, count, o, pivots, refactor_every, res, w_out);
+    return batch_solve_fast(lps, nullptr, count, o, pivots, refactor_every, res, w_out);
 }

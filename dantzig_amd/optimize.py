@@ -650,10 +650,10 @@ class _BatchModel:
     __slots__ = ("problem", "objective", "rhs", "form", "order", "last")
 
 
-def sessions(problems, **core_opts) -> "SessionBatch":
+def sessions(problems, fast: bool = False, **core_opts) -> "SessionBatch":
     """A SessionBatch over `problems` (Minimize / Maximize models): the batched sibling of
-    Optimize.session()."""
-    return SessionBatch(problems, **core_opts)
+    Optimize.session().  fast=True: the batch runs FAST numerics (SessionBatch)."""
+    return SessionBatch(problems, fast=fast, **core_opts)
 
 
 class SessionBatch:
@@ -673,15 +673,26 @@ class SessionBatch:
     `pivots` holds one list per call with one count per model, `cold` the number of models each call
     started cold.  core_opts: fields of dzg_opts over rust.set_options()'s; numerics is STRICT (AUTO
     means STRICT here).  ValueError for a model that does not go through the STRICT batch: more than
-    128 rows in standard form, or an integer variable."""
+    128 rows in standard form, or an integer variable.
 
-    def __init__(self, problems, **core_opts) -> None:
+    fast=True: every call is core.solve_batch_fast, the later ones with start=...: one workgroup per
+    model keeps the explicit basis inverse in LDS.  numerics is then FAST or AUTO (the default: a
+    model whose FAST solve comes within rounding of a tie, or ends singular, is solved by the STRICT
+    batch in the same call, from the same start); `strict_fallbacks` holds, per call, the number of
+    models whose result is STRICT's (a warm model often is one of them: the split pair x+ - x- of
+    the lowering leaves a reduced cost at zero up to rounding)."""
+
+    def __init__(self, problems, fast: bool = False, **core_opts) -> None:
         problems = list(problems)
         for i, p in enumerate(problems):
             if not isinstance(p, Optimize):
                 raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
         self._opts = {**rs._options, **core_opts}
-        if self._opts.get("numerics", core.AUTO) not in (core.STRICT, core.AUTO):
+        self._fast = bool(fast)
+        if self._fast:
+            if self._opts.get("numerics", core.AUTO) not in (core.FAST, core.AUTO):
+                raise ValueError("sessions(fast=True): numerics is FAST or AUTO")
+        elif self._opts.get("numerics", core.AUTO) not in (core.STRICT, core.AUTO):
             raise ValueError("sessions: the batch runs STRICT numerics only (numerics=STRICT or AUTO)")
         self._models = []
         for i, p in enumerate(problems):
@@ -691,6 +702,7 @@ class SessionBatch:
             self._models.append(st)
         self.pivots: list = []
         self.cold: list = []
+        self.strict_fallbacks: list = []
 
     @staticmethod
     def _lower(i: int, p: "Optimize", objective, rhs: dict):
@@ -741,8 +753,8 @@ class SessionBatch:
         lps = [core.CoreLP(a=f.a, c=f.c, basis=f.basis, nonbasis=f.nonbasis, x=f.x, z=f.z, var_col=f.var_col,
                            constant=f.constant) for _, _, f, _, _ in staged]
         start = [st.last if warm else None for st, (_, _, _, _, warm) in zip(self._models, staged)]
-        results = core.solve_batch(lps, log=False, start=start if any(s is not None for s in start) else None,
-                                   **self._opts)
+        solve = core.solve_batch_fast if self._fast else core.solve_batch
+        results = solve(lps, log=False, start=start if any(s is not None for s in start) else None, **self._opts)
         out = []
         for i, (st, (objective, new_rhs, form, order, _), res) in enumerate(zip(self._models, staged, results)):
             st.objective, st.rhs, st.form, st.order, st.last = objective, new_rhs, form, order, res
@@ -759,6 +771,8 @@ class SessionBatch:
                                     sense=st.problem.sense))
         self.pivots.append([r.iterations for r in results])
         self.cold.append(sum(s is None for s in start))
+        if self._fast:
+            self.strict_fallbacks.append(sum(r.numerics == "strict" for r in results))
         if not return_exceptions:
             for o in out:
                 if isinstance(o, Exception):

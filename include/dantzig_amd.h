@@ -805,6 +805,35 @@ int dzg_batch_solve_from(const dzg_lp *lps, const dzg_batch_start *start, int64_
  * calling thread's last dzg_batch_solve_from; 0 when it had no warm LP. */
 double dzg_debug_batch_restart_ms(void);
 
+/* dzg_batch_solve_fast with a start basis per LP (csrc/k_batch_fast.hip, k_batch_fast_restart).
+ *   lps[i] is the LP to solve now in slack-basis form and start[i] names the basis to start from, as
+ *   for dzg_batch_solve_from.  An entry with start[i].basis == NULL, and every entry when start ==
+ *   NULL, is solved exactly as dzg_batch_solve_fast solves it, bit for bit.  Cold and warm LPs mix
+ *   freely; an LP's result does not depend on its place in the batch.
+ * A warm LP gets dzg_solver_reoptimize's FAST restart state before the first pivot, from one launch
+ * of k_batch_fast_restart per bucket, with W = B^-1 as a launch of the FAST batch builds it:
+ *   x = W rhs;   z_k = a_{N_k} . y - c[N_k] with y = W^T c_B (stored entries only);   xbar = zbar =
+ *   1.0;   no refinement step.  iterations and the log count from 0 for this call; refactors counts
+ *   every inversion of a basis that is not all slack, the restart's included.
+ * A start whose inversion meets a zero or non-finite pivot, or whose restart x or z holds a non-finite
+ * entry, ends DZG_SINGULAR without a pivot: iterations = 0, basis / nonbasis as handed in.
+ * opts->numerics: STRICT is dzg_batch_solve_from(lps, start, count, opts, pivots_per_launch, res,
+ * NULL).  FAST honours near_tie_action and tie_tol.  AUTO, and opts == NULL, runs FAST with
+ * near_tie_action = STOP, and every LP that ends DZG_NEAR_TIE, DZG_SINGULAR or DZG_PANIC is solved
+ * again in the same call by dzg_batch_solve_from, from the same start (a cold entry cold), into the
+ * same result slot, which is then bit for bit what dzg_batch_solve_from gives for that LP;
+ * res[i].numerics_used says which numerics produced res[i].
+ * Host checks, before any device work: every check of dzg_batch_solve_fast (refactor_every < 0
+ * included) and every start check of dzg_batch_solve_from, with the same dzg_last_error texts.
+ * Nothing stays on the device between calls. */
+int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                              const dzg_opts *opts, int64_t pivots_per_launch,
+                              int64_t refactor_every, dzg_result *res);
+/* Device time (ms, between two events on the call's stream) of the k_batch_fast_restart launches of
+ * the calling thread's last dzg_batch_solve_fast or dzg_batch_solve_fast_from; 0 when it had no warm
+ * LP. */
+double dzg_debug_batch_fast_restart_ms(void);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean

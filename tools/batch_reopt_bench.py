@@ -14,6 +14,22 @@ dzg_debug_batch_restart_ms), the statuses, and the largest relative difference b
 the cold objective of an LP that ended optimal both ways.  No threshold on time: the tool reports.
 
     python tools/batch_reopt_bench.py [--lps 4096] [--m 64] [--ns 128] [--repeats 5] [--out profiles/batch_reopt_bench.json]
+
+--fast measures the FAST batch from its last bases (dzg_batch_solve_fast_from) instead.  Workloads:
+4 096 LPs at 64 x 128 and 1 024 LPs at 128 x 256 (or the one --lps / --m / --ns name), solved cold once
+by solve_batch_fast (AUTO); then per scale three sides, alternately, --repeats times each after one
+warm-up round:
+
+    warm_fast    solve_batch_fast(changed, start=previous)   AUTO: FAST, what it gives up on in STRICT
+    warm_strict  solve_batch(changed, start=previous)        dzg_batch_solve_from
+    cold_fast    solve_batch_fast(changed)                   AUTO, every LP from the slack basis
+
+Per side: wall times, minimum, spread, total pivots, statuses; for the FAST sides the number of LPs
+handed to STRICT; for warm_fast the device time of the restart launches
+(dzg_debug_batch_fast_restart_ms) and its share of the call; and per pair of sides whether the
+difference of the minima exceeds both spreads.
+
+    python tools/batch_reopt_bench.py --fast [--repeats 5] [--out profiles/batch_fast_reopt_bench.json]
 """
 from __future__ import annotations
 
@@ -40,8 +56,87 @@ def side(times, results) -> dict:
                 statuses={s: sum(r.status == s for r in results) for s in sorted({r.status for r in results})})
 
 
+FAST_WORKLOADS = ((4096, 64, 128), (1024, 128, 256))
+
+
+def beats(a: dict, b: dict) -> dict:
+    """Side a against side b: b's minimum over a's, and whether a is faster by more than both spreads."""
+    return dict(ratio=round(b["min_s"] / a["min_s"], 3),
+                faster_by_more_than_both_spreads=bool(b["min_s"] - a["min_s"] > max(a["spread_s"], b["spread_s"])),
+                slower_by_more_than_both_spreads=bool(a["min_s"] - b["min_s"] > max(a["spread_s"], b["spread_s"])))
+
+
+def fast_workload(n_lps: int, m: int, ns: int, repeats: int, ppl: int) -> dict:
+    data = [core.gen_dense_lp(seed=1_000_000 + i, m=m, n_struct=ns) for i in range(n_lps)]
+    data = [(np.array(a), b, c) for a, b, c in data]
+    lps = [core.CoreLP.from_inequality_form(a, b, c) for a, b, c in data]
+    kw = dict(log=False, pivots_per_launch=ppl)
+    previous = core.solve_batch_fast(lps, **kw)
+    doc = dict(lps=n_lps, m=m, n_struct=ns,
+               first_cold=dict(wall_s=round(previous[0].solve_ms / 1e3, 4),
+                               total_pivots=int(sum(r.iterations for r in previous)),
+                               handed_to_strict=int(sum(r.numerics == "strict" for r in previous))),
+               scales=[])
+    sides = dict(warm_fast=lambda ch: core.solve_batch_fast(ch, start=previous, **kw),
+                 warm_strict=lambda ch: core.solve_batch(ch, start=previous, **kw),
+                 cold_fast=lambda ch: core.solve_batch_fast(ch, **kw))
+    for scale in SCALES:
+        changed = []
+        for i, (a, b, c) in enumerate(data):
+            b2, c2 = moved(i, b, c, scale=scale)
+            changed.append(core.CoreLP.from_inequality_form(a, b2, c2))
+        times = {name: [] for name in sides}
+        last, restart_ms = {}, []
+        for rep in range(repeats + 1):   # round 0 is the warm-up
+            for name, run in sides.items():
+                last[name] = run(changed)
+                if rep == 0:
+                    continue
+                times[name].append(last[name][0].solve_ms / 1e3)
+                if name == "warm_fast":
+                    restart_ms.append(float(_ffi.lib().dzg_debug_batch_fast_restart_ms()))
+        out = {name: side(times[name], last[name]) for name in sides}
+        for name in ("warm_fast", "cold_fast"):
+            out[name]["handed_to_strict"] = int(sum(r.numerics == "strict" for r in last[name]))
+        both = [(w.objective, c.objective) for w, c in zip(last["warm_fast"], last["warm_strict"])
+                if w.status == c.status == "optimal"]
+        diff = max((abs(w - c) / max(1.0, abs(c)) for w, c in both), default=0.0)
+        entry = dict(scale=scale, **out,
+                     restart_launches_ms=[round(t, 3) for t in restart_ms],
+                     restart_launches_min_ms=round(min(restart_ms), 3),
+                     restart_share_of_warm_fast=round(min(restart_ms) / 1e3 / out["warm_fast"]["min_s"], 4),
+                     warm_fast_vs_warm_strict=beats(out["warm_fast"], out["warm_strict"]),
+                     warm_fast_vs_cold_fast=beats(out["warm_fast"], out["cold_fast"]),
+                     same_statuses=bool(all(x.status == y.status
+                                            for x, y in zip(last["warm_fast"], last["warm_strict"]))),
+                     optimal_both_ways=len(both), max_rel_objective_diff=float(diff))
+        doc["scales"].append(entry)
+        print(json.dumps(dict(lps=n_lps, m=m, n_struct=ns, **entry)), flush=True)
+    return doc
+
+
+def main_fast(args) -> int:
+    given = (args.lps, args.m, args.ns)
+    workloads = FAST_WORKLOADS if given == FAST_WORKLOADS[0] else (given,)
+    head = [core.CoreLP.from_inequality_form(*core.gen_dense_lp(seed=1_000_000 + i, m=workloads[0][1],
+                                                                n_struct=workloads[0][2])) for i in range(64)]
+    first = core.solve_batch_fast(head, log=False)   # warm-up: every path, every kernel
+    core.solve_batch_fast(head, start=first, log=False)
+    core.solve_batch(head, start=first, log=False)
+    doc = dict(tool="tools/batch_reopt_bench.py --fast", repeats=args.repeats,
+               pivots_per_launch=args.ppl or "default",
+               workloads=[fast_workload(n, m, ns, args.repeats, args.ppl) for n, m, ns in workloads])
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(doc, f, indent=1)
+            f.write("\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--fast", action="store_true", help="measure the FAST batch from its last bases (see above)")
     ap.add_argument("--lps", type=int, default=4096)
     ap.add_argument("--m", type=int, default=64)
     ap.add_argument("--ns", type=int, default=128)
@@ -49,6 +144,8 @@ def main() -> int:
     ap.add_argument("--ppl", type=int, default=0, help="pivots per launch (0 = the library's default)")
     ap.add_argument("--out", default=None, help="write the JSON document to this file as well")
     args = ap.parse_args()
+    if args.fast:
+        return main_fast(args)
     data = [core.gen_dense_lp(seed=1_000_000 + i, m=args.m, n_struct=args.ns) for i in range(args.lps)]
     data = [(np.array(a), b, c) for a, b, c in data]
     lps = [core.CoreLP.from_inequality_form(a, b, c) for a, b, c in data]
