@@ -359,6 +359,10 @@ def _user_values(res, form, order) -> dict:
             for i, v in enumerate(order)}
 
 
+# what dzg_solver_reoptimize / _extend / _remove say when the handle's basis is the obstacle
+_NO_CARRY_ON = ("did not refactorise", "cannot be carried on from")
+
+
 class Session:
     """A model kept on the GPU between solves (Optimize.session): the first solve() lowers the model,
     uploads it and solves it from the slack basis; every later solve(objective=..., rhs=...) changes
@@ -370,6 +374,8 @@ class Session:
     and that is slack at the current basis leaves it on the GPU (core.Solver.remove) and the solve
     carries on from the same basis; any other removal -- a constraint of the original model, a
     binding one -- makes the next solve() a cold rebuild from the slack basis (counted in `rebuilds`).
+    A solve() whose live solver cannot restart from its last basis (a singular or panic end; a FAST
+    end on a basis that does not refactorise) starts over from the slack basis too (`restarts`).
     Besides that only b and the objective may change: variable bounds, the coefficients of an existing
     row, new variables and integer variables are out of scope.
 
@@ -387,6 +393,7 @@ class Session:
         self._extended = 0      # ... of which the solver holds this many already
         self._removed: list = []  # constraints to take off the live solver at the next solve
         self.rebuilds = 0         # cold rebuilds remove_constraints has caused
+        self.restarts = 0         # cold starts because the last basis could not be carried on from
         self._opts = {**rs._options, **core_opts}
         self._opts.setdefault("refactor_interval", -1)  # (FAST: reserves what reoptimize needs)
         self._solver = None
@@ -483,15 +490,25 @@ class Session:
                 rows += range(at, at + k)
             at += k
         original = any(id(c) in gone for c in self._constraints)
-        if not original and (not rows or bool(self._solver.removable()[0][rows].all())):
-            if rows:
+        live = not original and (not rows or bool(self._solver.removable()[0][rows].all()))
+        stuck = False
+        if live and rows:
+            try:
                 self._solver.remove(rows=rows)
+            except _ffi.DantzigAmdError as exc:      # (see solve(): a basis that cannot be carried on from)
+                if not any(s in str(exc) for s in _NO_CARRY_ON):
+                    raise
+                live, stuck = False, True
+        if live:
             self._extended -= sum(id(c) in gone for c in self._added[:self._extended])
             self._added = [c for c in self._added if id(c) not in gone]
         else:
             self.close()
             self._constraints = [c for c in self._constraints if id(c) not in gone]
-            self.rebuilds += 1
+            if stuck:       # (not a rebuild the removal itself asked for)
+                self.restarts += 1
+            else:
+                self.rebuilds += 1
         for key in gone:
             self._rhs.pop(key, None)
 
@@ -554,10 +571,21 @@ class Session:
                              z=form.z, var_col=form.var_col, constant=form.constant)
             self._solver = core.Solver(lp, **self._opts)
         else:
-            if pending:
-                self._solver.extend(rows=np.array([row for row, _ in pending]), rhs=[b for _, b in pending])
-                self._extended = len(self._added)
-            self._solver.reoptimize(b=b_all, c=c_all, constant=form.constant)
+            try:
+                if pending:
+                    self._solver.extend(rows=np.array([row for row, _ in pending]), rhs=[b for _, b in pending])
+                    self._extended = len(self._added)
+                self._solver.reoptimize(b=b_all, c=c_all, constant=form.constant)
+            except _ffi.DantzigAmdError as exc:
+                # The basis the last solve ended on cannot be carried on from: a singular / panic end, or a
+                # FAST run that counted near ties and ended on a basis that does not refactorise (two
+                # parallel columns, such as the halves of a free variable, both basic).  The model is whole
+                # on the host, so the session starts over from the slack basis instead of failing.
+                if not any(s in str(exc) for s in _NO_CARRY_ON):
+                    raise
+                self.close()
+                self.restarts += 1
+                return self.solve()
         self._form, self._order = form, order
         self._solver.run(0)
         res = self._solver.result(log=False)
