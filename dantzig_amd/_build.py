@@ -39,6 +39,7 @@ def _deps():
             os.path.join(CSRC, "chain_barrier.h"), os.path.join(CSRC, "batch_strict.h"),
             os.path.join(CSRC, "batch_host.h"), os.path.join(CSRC, "batch_restart.h"),
             os.path.join(CSRC, "mip_internal.h"), os.path.join(CSRC, "duals.h"), os.path.join(CSRC, "ranging.h"), os.path.join(CSRC, "rays.h"),
+            os.path.join(CSRC, "opts.h"),
             os.path.join(os.path.dirname(HERE), "include", "dantzig_amd.h")]
     return hdrs
 

@@ -732,23 +732,25 @@ struct DzgDev {
     // opts.shard_rows (k_rowshard.hip): this rank owns the rows [rs_r0, rs_r1) of x, xbar, dx, Binv0
     // and U; rs == 0: all of them (rs_r0 = 0, rs_r1 = m)
     int rs, rs_r0, rs_r1;
-    int fold_k;          // k_chain_post finishes the row-wise pricing pass itself while k stays below
-                         // this (default: always; DZG_CHAIN_FOLD_K is the A/B switch)
+    int ftran_nt_k;      // FTRAN loads the rows of Binv0 nontemporally from this width on, plainly below
+                         // (fast_gemv_row_head<.., NT>): 8 m k bytes of inverse beyond 1.5 x the 256-MB
+                         // Infinity Cache
     long long rs_mcol;   // doubles of a record's column section (0: the matrix is replicated)
-    int ftran_variant;   // how FTRAN loads the rows of Binv0 (fast_gemv_row_head<.., VAR>): >= 0 forced
-                         // (DZG_FTRAN_VARIANT), -1: nontemporal from k = ftran_nt_k on, plain below
-    int ftran_nt_k;      // 8 m k bytes of inverse beyond 1.5 x the 256-MB Infinity Cache
     double *wk;          // [DZG_RMAX][ldw] Wc's gather KEPT CURRENT from pivot to pivot by the chain kernels:
                          // at every kernel boundary of a chain batch wk[t][c] == W[t][drow[c]] bit for bit
                          // (t < neta, c < k), so that every workgroup of k_chain_pre can form all of BTRAN's
                          // compact row itself and price its tile (k_chain.hip, PRICE).  NULL: not kept -- the host
                          // sets it per batch, only where the batch can price in the tail; the kernels then neither
                          // store nor renumber.  No padding, nothing beyond k is defined.
+    long long pad_;      // (never read: keeps the struct at 792 bytes, see below)
 };
-// The struct is a kernel argument by value.  d.wk took the eight bytes that fold_k and the padding behind it
-// held at the struct's end (fold_k went into the hole behind rs_r1): every other member is where it was and the
-// argument segment of every kernel is as long as it was.  Eight bytes more, with nothing else changed, cost the
-// 32768 x 65536 workload 0.8 % (profiles/price_in_pre.txt, job F): measure that workload when the struct grows.
+// The struct is a kernel argument by value, so its length is part of every kernel's argument segment.  It has no
+// hole from rs on: rs, rs_r0, rs_r1 and ftran_nt_k fill sixteen bytes, rs_mcol and wk eight each.  The length
+// counts in both directions on the 32768 x 65536 workload: eight bytes more, with nothing else changed, cost it
+// 0.8 % (profiles/price_in_pre.txt, job F), and ending the struct at wk, eight bytes shorter, about 1 % (seven
+// runs of seven at 20 950-21 080 iterations/s, against 21 120-21 330 in eighteen of twenty-one runs at 792 bytes,
+// with pad_ or with the members that were here before; profiles/dzgdev_length.txt) -- hence pad_.  Measure that
+// workload when the struct changes.
 
 #ifdef __HIPCC__
 // column of the entering variable: the local matrix (single GPU) or the winner's exchange

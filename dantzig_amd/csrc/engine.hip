@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "duals.h"
+#include "opts.h"
 #include "ranging.h"
 #include "rays.h"
 
@@ -411,13 +412,7 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
     *out = nullptr;
     std::string why;
     if (!validate(lp, why, src != nullptr)) return fail(DZG_E_ARG, "invalid dzg_lp: " + why);
-    dzg_opts o;
-    if (opts_in) o = *opts_in; else dzg_opts_default(&o);
-    if (o.max_iter <= 0) o.max_iter = 10000000;
-    if (o.poll_interval <= 0) o.poll_interval = 32;
-    if (o.epsilon == 0.0) o.epsilon = 1e-12;
-    if (o.auto_strict_rows <= 0) o.auto_strict_rows = 192;
-    if (o.tie_tol == 0.0) o.tie_tol = 1e-11;
+    dzg_opts o = dzg_opts_resolved(opts_in);
 
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -446,9 +441,8 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
     if (d.lda == 0) d.lda = 16;
     d.eps = o.epsilon;
     // FTRAN's loads of Binv0's rows (k > 512): nontemporal, eight steps in flight -- 125.4 -> 102.9 us
-    // for k_chain_pre at k = 7 700 (profiles/r04_ftran_row_loads_ab.txt); DZG_FTRAN_VARIANT=0: plain loads
-    d.ftran_variant = -1;
-    if (const char *fv = std::getenv("DZG_FTRAN_VARIANT")) d.ftran_variant = std::atoi(fv);
+    // for k_chain_pre at k = 7 700 -- from the width on at which the inverse outgrows 1.5 x the Infinity
+    // Cache; below it plain loads are faster (profiles/r04_ftran_row_loads_ab.txt)
     {
         const double kk = 384e6 / (8.0 * (double)(lp->m > 0 ? lp->m : 1));
         d.ftran_nt_k = kk > 2e9 ? 2000000000 : (int)kk;
@@ -456,8 +450,6 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
     }
     d.beta_split = 1;
     if (const char *bs = std::getenv("DZG_CHAIN_BETA_SPLIT")) d.beta_split = bs[0] != '0';
-    d.fold_k = 0x7fffffff;
-    if (const char *fk = std::getenv("DZG_CHAIN_FOLD_K")) d.fold_k = std::atoi(fk);
     d.world = o.world > 1 ? o.world : 1;
     d.rank = d.world > 1 ? o.rank : 0;
     d.col0 = 0;
@@ -523,10 +515,7 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
         d.cptr = dcp; d.ridx = dri; d.cval = dcv;
         // One GPU, FAST numerics: the basis lives on its k x k structural block (k_sparse.hip),
         // which needs row access to the matrix as well: a CSR copy, columns ascending in a row.
-        const int want = o.numerics == DZG_NUMERICS_AUTO
-                             ? (m <= o.auto_strict_rows ? DZG_NUMERICS_STRICT : DZG_NUMERICS_FAST)
-                             : o.numerics;
-        if (d.world == 1 && want == DZG_NUMERICS_FAST && m <= (1 << 20)) {
+        if (d.world == 1 && dzg_opts_numerics(o, m) == DZG_NUMERICS_FAST && m <= (1 << 20)) {
             d.spb = 1;
             std::vector<long long> rp((size_t)m + 1, 0);
             for (int r : ri) rp[(size_t)r + 1] += 1;
@@ -689,9 +678,7 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
     TRY(dev_alloc(s, &d.log_margin, (size_t)cap));
 
     // --- numerics
-    s->numerics = o.numerics == DZG_NUMERICS_AUTO
-                      ? (m <= o.auto_strict_rows ? DZG_NUMERICS_STRICT : DZG_NUMERICS_FAST)
-                      : o.numerics;
+    s->numerics = dzg_opts_numerics(o, m);
     if (s->numerics != DZG_NUMERICS_STRICT && s->numerics != DZG_NUMERICS_FAST)
         return fail(DZG_E_ARG, "opts.numerics");
     if (d.world > 1 && s->numerics != DZG_NUMERICS_FAST)
@@ -783,12 +770,13 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
         TRY(dev_alloc(s, &d.fpx_h, np)); TRY(dev_alloc(s, &d.fpz_h, np));
         TRY(dev_alloc(s, &d.rx_h, np)); TRY(dev_alloc(s, &d.rz_h, np));
         if (o.refactor_interval != 0) TRY(refactor_workspace(s));
+        // (the CU count: both barrier-synchronised iterations below fit their grids to it)
+        hipDeviceProp_t prop;
+        HIP_OK(hipGetDeviceProperties(&prop, o.device));
+        const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
         if (d.spb && !o.seven_launches) {
             // the four-launch iteration (k_sp_pre / k_sp_mid, k_sparse.hip) synchronises its phases with
             // device-wide barriers: every workgroup of its grid must be resident at once
-            hipDeviceProp_t prop;
-            HIP_OK(hipGetDeviceProperties(&prop, o.device));
-            const int cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
             const char *off = std::getenv("DZG_SP_FUSED");
             if (!(off && off[0] == '0') && (long long)dzg_sp_fused_resident_per_cu() * cus >= dzg_sp_grid(m)) {
                 TRY(dev_alloc(s, &s->chain_bar, (size_t)DZG_CHAIN_BAR_WORDS));
@@ -807,9 +795,7 @@ static int solver_create(const dzg_lp *lp, const dzg_opts *opts_in, dzg_solver *
             // the chain's barriers need every workgroup resident at once: one per CU, and the
             // runtime must agree that a workgroup of either kernel fits a CU at all (registers,
             // 136 KB of LDS); otherwise the barrier-free seven launches run
-            hipDeviceProp_t prop;
-            HIP_OK(hipGetDeviceProperties(&prop, o.device));
-            int grid = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 1;
+            int grid = cus;
             if (grid > 256) grid = 256; // (k_chain_pre reads <= 256 candidates)
             const int per_cu = dzg_chain_resident_per_cu();
             if (per_cu < 1) grid = 0;
@@ -3428,7 +3414,6 @@ static int core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, S
     // (duals of a FAST run: reserve the refactorisation workspace, as a non-slack start does)
     if (fresh && o.refactor_interval == 0) o.refactor_interval = -1;
     const bool automatic = o.numerics == DZG_NUMERICS_AUTO;
-    const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
     // AUTO above auto_strict_rows = FAST that must prove it followed the reference: up to
     // DZG_AUTO_STRICT_RESTART_ROWS rows it stops at the first decision that is within rounding of
     // a tie (and when it loses its footing: DZG_SINGULAR, DZG_PANIC -- degenerate or badly scaled
@@ -3436,7 +3421,7 @@ static int core_solve(const dzg_lp *lp, const dzg_opts *opts, dzg_result *res, S
     // the state vectors of a FAST run carry FAST's rounding, so no later point can be handed over
     // bit-exactly.  Above that size STRICT is out of reach and FAST reports what it met.
     const int restart_rows = o.auto_restart_rows != 0 ? o.auto_restart_rows : DZG_AUTO_STRICT_RESTART_ROWS;
-    const bool can_restart = automatic && lp->m > strict_rows && lp->m <= restart_rows;
+    const bool can_restart = automatic && dzg_opts_numerics(o, lp->m) == DZG_NUMERICS_FAST && lp->m <= restart_rows;
     if (can_restart && o.tie_tol >= 0.0) o.near_tie_action = DZG_NEAR_TIE_STOP;
     int rc = solve_once(lp, &o, res, ex);
     if (rc < 0) return rc;

@@ -133,10 +133,10 @@ __device__ __forceinline__ double fast_beta_fold(double s0, double s1, double s2
 // compact row of Binv0 against the gathered column `ag` (padded with a zero to an even length);
 // (tail) minus this lane's share of the eta file, then the sum over the LPR lanes.  The summation
 // order depends on LPR, k and neta only.  Rows i >= m: zero (the lanes still take part in the tail).
-// VAR (the loads of the row only; the sums and their order are the same in every variant):
-//   0  plain loads, four steps' loads in flight          1  nontemporal loads
-//   2  nontemporal loads, eight steps' loads in flight
-template <int LPR, int VAR = 0>
+// NT (the loads of the row only; the sums and their order are the same in both forms):
+//   false  plain loads, four steps' loads in flight
+//   true   nontemporal loads, eight steps' loads in flight
+template <int LPR, bool NT = false>
 __device__ __forceinline__ double fast_gemv_row_head(int i, int m, int k2,
                                                      const double *__restrict__ binv, long long ldb,
                                                      const double *__restrict__ ag, int sub)
@@ -145,9 +145,8 @@ __device__ __forceinline__ double fast_gemv_row_head(int i, int m, int k2,
     const double *row = binv + (long long)i * ldb;
     double a0 = 0.0, a1 = 0.0;
     int c = 2 * sub;
-    if (VAR != 0) {
-        constexpr int UN = VAR == 2 ? 8 : 4;
-#pragma unroll UN
+    if (NT) {
+#pragma unroll 8
         for (; c + 2 * LPR < k2; c += 4 * LPR) {
             const double2_t r0 = __builtin_nontemporal_load(reinterpret_cast<const double2_t *>(row + c));
             const double2_t r1 = __builtin_nontemporal_load(reinterpret_cast<const double2_t *>(row + c + 2 * LPR));
@@ -200,14 +199,14 @@ __device__ __forceinline__ double fast_gemv_row_tail(double acc, int i, int m, i
     return acc;
 }
 
-template <int LPR, int VAR = 0>
+template <int LPR, bool NT = false>
 __device__ __forceinline__ double fast_gemv_row(int i, int m, int k2, int neta,
                                                 const double *__restrict__ binv, long long ldb,
                                                 const double *__restrict__ ag,
                                                 const double *__restrict__ U, long long ldu,
                                                 const double *__restrict__ beta, int sub)
 {
-    const double acc = fast_gemv_row_head<LPR, VAR>(i, m, k2, binv, ldb, ag, sub);
+    const double acc = fast_gemv_row_head<LPR, NT>(i, m, k2, binv, ldb, ag, sub);
     return fast_gemv_row_tail<LPR>(acc, i, m, neta, U, ldu, beta, sub);
 }
 

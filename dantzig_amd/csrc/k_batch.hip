@@ -36,6 +36,7 @@
 #include "batch_strict.h"
 #include "common.h"
 #include "duals.h"
+#include "opts.h"
 #include "ranging.h"
 #include "rays.h"
 
@@ -535,7 +536,7 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
     if (opts) o = *opts; else dzg_opts_default(&o);
     if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_AUTO)
         return dzg_set_error(DZG_E_ARG, "batch: STRICT numerics only (FAST is not batched)");
-    const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
+    const long long max_iter = dzg_opts_resolved(&o).max_iter;
     const int rc_lps = bh::check_batch(lps, count, [&](int64_t i, std::string &why) {
         if (start && !bh::start_valid(lps[i], start[i], why)) return false;
         return !ex.ranging || dzg_ranging_req_valid(&ex.req[i], lps[i].m, lps[i].n, why);
@@ -546,7 +547,7 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
 
     Ctx C(lps, start, (int)count, res, ex, max_iter);
     C.g.max_iter = max_iter;
-    C.g.eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
+    C.g.eps = dzg_opts_resolved(&o).epsilon;
     C.g.ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30) : DZG_BATCH_DEFAULT_PPL);
     if (const int rc = pack_and_upload(C)) return rc;
     unsigned char *dev = C.D.arena;

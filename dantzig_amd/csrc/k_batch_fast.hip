@@ -45,6 +45,7 @@
 #include "batch_strict.h"
 #include "common.h"
 #include "fast_decide.h"
+#include "opts.h"
 
 namespace {
 
@@ -722,7 +723,7 @@ static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int
     const bool dump = w_out != nullptr;
     const bool warm = bh::any_warm(start, (int)count);
     const long long max_iter = dump ? std::min<int64_t>(pivots_per_launch, 1 << 30)
-                                    : (o.max_iter > 0 ? o.max_iter : 10000000);
+                                    : dzg_opts_resolved(&o).max_iter;
     if (const int rc = bh::use_device(o.device)) return rc;
 
     const int N = (int)count;
@@ -753,7 +754,7 @@ static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int
     bh::wire(g, dev, L);
     g.state = (FState *)(dev + s_state);
     g.log_margin = (double *)(dev + s_lmg);
-    g.eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
+    g.eps = dzg_opts_resolved(&o).epsilon;
     g.ppl = dump ? (int)max_iter + 1
           : (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
                                         : DZG_BATCH_FAST_DEFAULT_PPL);

@@ -354,20 +354,11 @@ __device__ __forceinline__ void chain_dot_head(const DzgDev &d, int r0, int r1, 
     // streams past the caches (nontemporal loads, eight steps in flight: 125.4 -> 102.9 us per FTRAN
     // at k = 7 700 of config 3), a smaller one is re-read from it pivot after pivot and plain loads
     // are faster (55.4 against 60.4 us at k = 4 049): profiles/r04_ftran_row_loads_ab.txt
-    const int variant = d.ftran_variant >= 0 ? d.ftran_variant : (k >= d.ftran_nt_k ? 2 : 0);
-    if (LPR == 64 && variant == 1) {
+    if (LPR == 64 && k >= d.ftran_nt_k) {
 #pragma unroll
         for (int pass = 0; pass < MAXP; ++pass) {
             const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
-            accs[pass] = fast_gemv_row_head<LPR, 1>(i < r1 ? i : d.m, d.m, k2, d.binv, d.ldb, s_ag, sub);
-        }
-        return;
-    }
-    if (LPR == 64 && variant == 2) {
-#pragma unroll
-        for (int pass = 0; pass < MAXP; ++pass) {
-            const int i = r0 + (pass * CH_NW + wave) * RPW + grp;
-            accs[pass] = fast_gemv_row_head<LPR, 2>(i < r1 ? i : d.m, d.m, k2, d.binv, d.ldb, s_ag, sub);
+            accs[pass] = fast_gemv_row_head<LPR, true>(i < r1 ? i : d.m, d.m, k2, d.binv, d.ldb, s_ag, sub);
         }
         return;
     }

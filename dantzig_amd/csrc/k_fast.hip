@@ -29,8 +29,6 @@
 // the heads of these kernels: each workgroup reduces the small arrays of per-workgroup
 // partial candidates left by the previous kernel (deterministic max-loc, lowest position on
 // ties), workgroup 0 publishes the decision in the control block for the next kernel.
-#include <cstdlib>
-
 #include "common.h"
 #include "fast_decide.h"
 #include "fast_rows.h"
@@ -196,8 +194,8 @@ __device__ __forceinline__ void gemv_rows(const DzgCtl *ctl, int need_kind, int 
         // (one wave per row of a wide inverse: the row streams past the caches, eight steps' loads in
         // flight -- profiles/r04_ftran_row_loads_ab.txt; the sums are the same sums)
         double acc = (LPR == 64 && nt)
-                         ? fast_gemv_row<LPR, 2>(i, m, k2, neta, binv, ldb, ag, U, ldu, beta, sub)
-                         : fast_gemv_row<LPR, 0>(i, m, k2, neta, binv, ldb, ag, U, ldu, beta, sub);
+                         ? fast_gemv_row<LPR, true>(i, m, k2, neta, binv, ldb, ag, U, ldu, beta, sub)
+                         : fast_gemv_row<LPR, false>(i, m, k2, neta, binv, ldb, ag, U, ldu, beta, sub);
         if (i < m && sub == 0) {
             acc = fast_gemv_unit(acc, bcode[i], code, acolp);
             dx[i] = acc;
@@ -432,78 +430,12 @@ __global__ __launch_bounds__(256) void k_fast_gather_w(const DzgCtl *ctl, const 
 // eta index in steps of 4: D = C - A*B with v_mfma_f64_16x16x4_f64.  Operand lane maps
 // (cdna_hip_programming.md section 3): A[i = l&15][kk = l>>4], B[kk = l>>4][j = l&15],
 // C/D[row = (l>>4) + 4*reg][col = l&15].
-template <bool PRELOAD>
-__global__ __launch_bounds__(256) void k_fast_flush_mfma(const DzgCtl *ctl, int m,
-                                                         double *__restrict__ binv, long long ldb,
-                                                         const double *__restrict__ U, long long ldu,
-                                                         const double *__restrict__ Wc,
-                                                         long long ldw)
-{
-    const int neta = ctl->neta, k = ctl->ncompact;
-    if (neta < R_ || k <= 0) return;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c0 = blockIdx.x * 64;
-    const int i0 = (blockIdx.y * 4 + wave) * 16;
-    if (c0 >= k || i0 >= m) return;
-    const int li = lane & 15, lk = lane >> 4;
-    double4_t acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int row = i0 + lk + 4 * g, col = c0 + 16 * j + li;
-            acc[j][g] = (row < m && col < k) ? binv[(long long)row * ldb + col] : 0.0;
-        }
-    }
-    const int arow = i0 + li;
-    const int arowc = arow < m ? arow : 0;
-    // The eta file is full (neta == R_ = 64): 16 steps of 4 etas, trip count known.  All operands
-    // of the 64 MFMAs -- 16 values of U and 64 of Wc per lane -- are fetched BEFORE the first MFMA,
-    // in one trip to L2 / HBM beside the tile of Binv0 itself: 161 us per flush at k = 4 060 against
-    // 170 us fetched step by step (DZG_FLUSH_STEPS=1 selects that form for comparison).
-    if (PRELOAD) {
-        double av[R_ / 4], bv[R_ / 4][4];
-#pragma unroll
-        for (int s = 0; s < R_ / 4; ++s) {
-            const int t = 4 * s + lk;
-            av[s] = U[(long long)t * ldu + arowc];
-            const double *wrow = Wc + (long long)t * ldw + c0 + li;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) bv[s][j] = wrow[16 * j];
-        }
-#pragma unroll
-        for (int s = 0; s < R_ / 4; ++s) {
-            const double a = arow < m ? -av[s] : 0.0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bv[s][j], acc[j], 0, 0, 0);
-        }
-    } else {
-        for (int s = 0; s < R_ / 4; ++s) {
-            const int t = 4 * s + lk;
-            const double a = arow < m ? -U[(long long)t * ldu + arowc] : 0.0;
-            const double *wrow = Wc + (long long)t * ldw + c0 + li;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const double b = wrow[16 * j];
-                acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int row = i0 + lk + 4 * g, col = c0 + 16 * j + li;
-            if (row < m && col < k) binv[(long long)row * ldb + col] = acc[j][g];
-        }
-    }
-}
-
-// The same product with the 64 x 64 tile of Wc the four waves of a workgroup share staged through
-// LDS: fetched once per workgroup (one trip, beside the strip of U and the tile of Binv0) instead of
-// once per wave -- 40 KB from the L2 per 8 KB of Binv0 became 16.  Same operands, same order of the
-// eta steps: the same bits.
+// It folds only a FULL eta file (neta == R_ = 64): 16 steps of 4 etas, trip count known.  All
+// operands of a wave's 64 MFMAs are fetched BEFORE the first one, in one trip to L2 / HBM beside the
+// tile of Binv0 itself (161 us per flush at k = 4 060 against 170 us fetched step by step), and the
+// 64 x 64 tile of Wc the four waves of a workgroup share goes through LDS: fetched once per
+// workgroup instead of once per wave -- 40 KB from the L2 per 8 KB of Binv0 became 16 (313.6 ->
+// 241.0 us per flush at k = 7 700).  Neither changes an operand or the order of the eta steps.
 #define FLD 72 // LDS row stride in doubles (t -> t + 1 moves 16 banks on)
 __global__ __launch_bounds__(256) void k_fast_flush_mfma_lds(const DzgCtl *ctl, int m,
                                                              double *__restrict__ binv, long long ldb,
@@ -766,8 +698,7 @@ void dzg_launch_fast_gemv(const DzgDev &d, int need_kind, const double *xrecv, h
 {
     const DzgPivotArgs pa = dzg_pivot_args(d);
 #define GEMV_ARGS d.ctl, need_kind, d.m, d.binv, d.ldb, d.ag, d.U, d.ldw, d.beta, d.A, d.lda, d.col0, xrecv,  \
-                  d.xstride, d.bcode, d.x, d.xbar, d.dx, d.rx_r, d.rx_k, d.rx_h, pa,                         \
-                  (d.ftran_variant >= 0 ? (d.ftran_variant ? 0 : 0x7fffffff) : d.ftran_nt_k)
+                  d.xstride, d.bcode, d.x, d.xbar, d.dx, d.rx_r, d.rx_k, d.rx_h, pa, d.ftran_nt_k
     if (need_kind == DZG_STEP_DUAL)
         hipLaunchKernelGGL((k_fast_gemv<true>), dim3(DZG_NB_GEMV), dim3(256), 0, st, GEMV_ARGS);
     else
@@ -801,17 +732,8 @@ void dzg_launch_fast_flush(const DzgDev &d, hipStream_t st)
     const int r0 = d.rs ? d.rs_r0 : 0, rows = (d.rs ? d.rs_r1 : d.m) - r0;
     double *binv = d.binv + (long long)r0 * d.ldb;
     const double *U = d.U + r0;
-    static const bool steps = std::getenv("DZG_FLUSH_STEPS") != nullptr; // (A/B switch, tools)
-    static const bool no_lds = std::getenv("DZG_FLUSH_NO_LDS") != nullptr; // (A/B switch, tools)
-    if (rows <= 0) {
-    } else if (!steps && !no_lds)
+    if (rows > 0)
         hipLaunchKernelGGL(k_fast_flush_mfma_lds, dim3((kmax + 63) / 64, (rows + 63) / 64), dim3(256), 0, st,
-                           d.ctl, rows, binv, d.ldb, U, d.ldw, d.Wc, d.ldw);
-    else if (steps)
-        hipLaunchKernelGGL(k_fast_flush_mfma<false>, dim3((kmax + 63) / 64, (rows + 63) / 64), dim3(256), 0, st,
-                           d.ctl, rows, binv, d.ldb, U, d.ldw, d.Wc, d.ldw);
-    else
-        hipLaunchKernelGGL(k_fast_flush_mfma<true>, dim3((kmax + 63) / 64, (rows + 63) / 64), dim3(256), 0, st,
                            d.ctl, rows, binv, d.ldb, U, d.ldw, d.Wc, d.ldw);
     hipLaunchKernelGGL(k_fast_flush_done, dim3(1), dim3(1), 0, st, d.ctl, ((kmax + 63) / 64) * 64);
 }

@@ -84,21 +84,14 @@ int dzg_price_partials(int kernel)
 // partial count of the pass dzg_launch_price_fast(d, kernel) will run
 // workgroups of the live-entry pricing pass (= its ratio partials): 1 024 -- with 2 048 the launch
 // after it reduces twice the candidates for nothing (config 4: 15 060 -> 15 870 it/s at k = 1 000,
-// 13 250 -> 13 690 at k = 4 126; 512: 15 610 / 13 580); DZG_RL_GRID for A/B
-static int rl_grid(void)
-{
-    static const int g = [] {
-        const char *e = std::getenv("DZG_RL_GRID");
-        const int v = e ? std::atoi(e) : 1024;
-        return v < 1 ? 1 : (v > DZG_PRICE_CSC_BLOCKS ? DZG_PRICE_CSC_BLOCKS : v);
-    }();
-    return g;
-}
+// 13 250 -> 13 690 at k = 4 126; 512: 15 610 / 13 580)
+constexpr int kRlGrid = 1024;
+static_assert(kRlGrid <= DZG_PRICE_CSC_BLOCKS, "rz_r / rz_k / rl_work hold DZG_PRICE_CSC_BLOCKS partials");
 
 int dzg_price_partials_dev(const DzgDev &d, int kernel)
 {
     if (!d.csc) return dzg_price_partials(kernel);
-    if (d.spb && d.lcnt && kernel != DZG_PRICE_SEQ) return rl_grid();
+    if (d.spb && d.lcnt && kernel != DZG_PRICE_SEQ) return kRlGrid;
     return DZG_PRICE_CSC_BLOCKS;
 }
 
@@ -179,9 +172,8 @@ int dzg_price_small_partials(const DzgDev &d) { return (int)((d.ldt + PRS_TILE -
 // pass itself (k_chain_post, FOLD) and the finishing launch is left out
 int dzg_price_rows_certain(const DzgDev &d, int kernel)
 {
-    // (fold_k: an A/B switch, DZG_CHAIN_FOLD_K; the default is "whenever the pass is row-wise")
     return !d.csc && d.At && d.q > 0 && resolve(kernel) == DZG_PRICE_TREE && d.k_hint > 0 &&
-           d.k_hint < d.rows_T && d.k_hint < d.fold_k;
+           d.k_hint < d.rows_T;
 }
 
 // FAST numerics: structural positions from plist, ratio-test partials for the dual step
@@ -212,7 +204,7 @@ void dzg_launch_price_fast(const DzgDev &d, int kernel, hipStream_t st, int need
     if (d.csc) {
         if (d.spb && d.lcnt && kernel != DZG_PRICE_SEQ) { // sparse basis: the live entries only
             if (d.q > 0)
-                hipLaunchKernelGGL(k_price_csc_rl, dim3(rl_grid()), dim3(256), 0, st, d.ctl,
+                hipLaunchKernelGGL(k_price_csc_rl, dim3(kRlGrid), dim3(256), 0, st, d.ctl,
                                    d.cptr, d.lcnt, d.lent, d.q, d.plist, d.pcode, d.nbcode, d.v,
                                    d.dz, d.z, d.zbar, d.rz_r, d.rz_k, d.rz_h, d.rl_work);
             return;

@@ -278,7 +278,7 @@ __global__ __launch_bounds__(256) void k_range_cost_y(const DzgDev d, int k, Dzg
 // major), so a lane reads 16 consecutive rows of its column per tile: within a tile lane group lk
 // takes rows 16 lk .. 16 lk + 15, one per MFMA step -- both operands use the same assignment of
 // rows to the instruction's k slots, which is all the product needs.
-// Lane maps as at k_ref_gemm (k_refactor.hip): A[i = l&15][k = l>>4], B[k = l>>4][j = l&15],
+// Lane maps as at k_ref_gemm_lds (k_refactor.hip): A[i = l&15][k = l>>4], B[k = l>>4][j = l&15],
 // D[row = (l>>4) + 4 reg][col = l&15]; here i = direction, j = nonbasic position.
 // A slack at a nonbasic position has no column in A: its delta is Y[dir][row] - g, read beside the
 // product.  Rows m .. ldy-1 of Y are zero and rows >= m of A are not read.

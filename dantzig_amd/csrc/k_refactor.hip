@@ -23,8 +23,6 @@
 //      position of the basic slack of row r' (one more MFMA GEMM), eta file emptied.
 //
 // 2 k^3 + 2 (m-k) k^2 flops, all but the panels in GEMM form.
-#include <cstdlib>
-
 #include "common.h"
 
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -32,80 +30,19 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 #define NB 64
 
 // ---------------------------------------------------------------------------------
-// C[M x N] (+)= alpha * A[M x K] * B[K x N], all row-major.  One wave owns a 16 x 64 strip of C
-// (4 MFMA tiles) and walks K in steps of 4.  ZERO_C: C = -A*B (no read of C); otherwise
-// C -= A*B.  crow (optional) maps strip rows to rows of C (scatter).
+// k_ref_gemm_lds: C[M x N] (+)= alpha * A[M x K] * B[K x N], all row-major.  One wave owns a
+// 16 x 64 strip of C (4 MFMA tiles) and walks K in steps of 4.  ZERO_C: C = -A*B (no read of C);
+// otherwise C -= A*B.  crow (optional) maps strip rows to rows of C (scatter).
 // Lane maps (cdna_hip_programming.md section 3): A[i = l&15][k = l>>4], B[k = l>>4][j = l&15],
 // C/D[row = (l>>4) + 4*reg][col = l&15].
-// ---------------------------------------------------------------------------------
-template <bool ZERO_C>
-__global__ __launch_bounds__(256) void k_ref_gemm(int M, int N, int K, const double *__restrict__ A,
-                                                  long long lda, const double *__restrict__ B,
-                                                  long long ldb, double *__restrict__ C,
-                                                  long long ldc, const int *__restrict__ crow,
-                                                  int crow0 = 0, int crow1 = 0)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int c0 = blockIdx.x * 64;
-    const int i0 = (blockIdx.y * 4 + wave) * 16;
-    if (c0 >= N || i0 >= M) return;
-    // (crow0, crow1) != (0, 0) (a row-sharded basis side): only the rows of C in [crow0, crow1) exist on this
-    // device; crow ascends, so a strip whose first and last target lie outside has nothing to do
-    const bool ranged = crow && !(crow0 == 0 && crow1 == 0); // (0, 0): every row
-    if (ranged) {
-        const int first = crow[i0], last = crow[i0 + 15 < M ? i0 + 15 : M - 1];
-        if (last < crow0 || first >= crow1) return;
-    }
-    const int li = lane & 15, lk = lane >> 4;
-    double4_t acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int row = i0 + lk + 4 * g, col = c0 + 16 * j + li;
-            double cv = 0.0;
-            if (!ZERO_C && row < M && col < N)
-                cv = C[(long long)(crow ? crow[row] : row) * ldc + col];
-            acc[j][g] = cv;
-        }
-    }
-    const int arow = i0 + li;
-    const double *ap = A + (long long)(arow < M ? arow : 0) * lda;
-    for (int t0 = 0; t0 < K; t0 += 4) {
-        const int t = t0 + lk;
-        const bool tin = t < K;
-        const double a = (arow < M && tin) ? -ap[t] : 0.0;
-        const double *bp = B + (long long)(tin ? t : 0) * ldb;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int col = c0 + 16 * j + li;
-            const double b = (tin && col < N) ? bp[col] : 0.0;
-            acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[j], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int row = i0 + lk + 4 * g, col = c0 + 16 * j + li;
-            if (row < M && col < N) {
-                const int cr = crow ? crow[row] : row;
-                if (!ranged || (cr >= crow0 && cr < crow1)) C[(long long)cr * ldc + col] = acc[j][g];
-            }
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------
-// k_ref_gemm_lds: the same product with B staged through LDS.  The four waves of a workgroup own
-// four 16 x 64 strips of the SAME 64 columns of C, so they multiply by the same K x 64 panel of B:
-// it is fetched once per workgroup, 64 rows of K at a time (32 KB, coalesced 16-byte loads, one
-// trip), and every MFMA takes its B operand from LDS; only A (one value per lane and 4 MFMAs, four
-// steps per trip) and the C tile itself still come from memory.  In k_ref_gemm every wave loads
-// its own copy of B from L2 -- 5 loads per 4 MFMAs, the L1 at its limit: 25 % of the fp64 MFMA
-// peak on the rank-64 updates of the factorisation.  Occupancy stays at 4 waves per SIMD (128
-// VGPRs, 36 KB of LDS per workgroup): latency is hidden by waves, as there.
-// Same lane maps, same order of the K steps: bit-identical results.
+// B is staged through LDS.  The four waves of a workgroup own four 16 x 64 strips of the SAME 64
+// columns of C, so they multiply by the same K x 64 panel of B: it is fetched once per workgroup,
+// 64 rows of K at a time (32 KB, coalesced 16-byte loads, one trip), and every MFMA takes its B
+// operand from LDS; only A (one value per lane and 4 MFMAs, four steps per trip) and the C tile
+// itself still come from memory.  With every wave loading its own copy of B from L2 -- 5 loads per
+// 4 MFMAs, the L1 at its limit -- the rank-64 updates of the factorisation ran at 25 % of the fp64
+// MFMA peak.  Occupancy is 4 waves per SIMD (128 VGPRs, 36 KB of LDS per workgroup): latency is
+// hidden by waves.  Staging changes neither an operand nor the order of the K steps.
 // ---------------------------------------------------------------------------------
 #define GKC 64  // rows of B per LDS panel
 #define GLD 72  // LDS row stride in doubles (k -> k + 1 moves 16 banks on)
@@ -123,7 +60,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const int c0 = blockIdx.x * 64;
     const int i0 = (blockIdx.y * 4 + wave) * 16;
     const int li = lane & 15, lk = lane >> 4;
-    // (see k_ref_gemm; the test is on the WORKGROUP's 64 rows: the barriers below stay uniform)
+    // (crow0, crow1) != (0, 0) (a row-sharded basis side): only the rows of C in [crow0, crow1) exist on this
+    // device; crow ascends, so a workgroup whose first and last target lie outside has nothing to do
+    // (the test is on the WORKGROUP's 64 rows: the barriers below stay uniform)
     const bool ranged = crow && !(crow0 == 0 && crow1 == 0); // (0, 0): every row
     if (ranged) {
         const int b0 = blockIdx.y * 64;
@@ -838,7 +777,7 @@ __global__ __launch_bounds__(256) void k_ref_trsm_u(int j0, int nbw, const doubl
 // T[row0 .. row0 + 64, cbeg .. cend) <- Minv * T[...] in place, Minv a 64 x 64 block inverse
 // (k_ref_swap), on the matrix cores.  A workgroup owns 64 columns: their 64 x 64 tile of T goes into
 // LDS whole before anything is written back, so the product may overwrite its own operand.  Lane
-// maps as in k_ref_gemm.  grid ceil((cend - cbeg) / 64)
+// maps as in k_ref_gemm_lds.  grid ceil((cend - cbeg) / 64)
 __global__ __launch_bounds__(256) void k_ref_tri_apply(const double *__restrict__ Minv,
                                                        double *__restrict__ T, long long ldt, int row0,
                                                        int cbeg, int cend)
@@ -981,15 +920,9 @@ static void gemm_sub(int M, int N, int K, const double *A, long long lda, const 
                      long long ldb, double *C, long long ldc, hipStream_t st)
 {
     if (M <= 0 || N <= 0 || K <= 0) return;
-    // B through LDS (k_ref_gemm_lds) at every shape: the skinny products of the panel pairs too (one
-    // trip for the B panel and four for A, where the strip kernel makes sixteen dependent ones);
-    // DZG_REF_GEMM_STRIPS keeps the strip kernel for comparison
-    if (!std::getenv("DZG_REF_GEMM_STRIPS")) {
-        hipLaunchKernelGGL((k_ref_gemm_lds<false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, st, M,
-                           N, K, A, lda, B, ldb, C, ldc, (const int *)nullptr);
-        return;
-    }
-    hipLaunchKernelGGL((k_ref_gemm<false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, st, M, N,
+    // B through LDS at every shape: the skinny products of the panel pairs too (one trip for the B
+    // panel and four for A, where a wave that walks K with loads of its own makes sixteen dependent ones)
+    hipLaunchKernelGGL((k_ref_gemm_lds<false>), dim3((N + 63) / 64, (M + 63) / 64), dim3(256), 0, st, M, N,
                        K, A, lda, B, ldb, C, ldc, (const int *)nullptr);
 }
 
@@ -1190,12 +1123,8 @@ void dzg_launch_refactor_c(const DzgDev &d, int k, int nl, double *G, double *X,
         // (lpos ascends: a row-sharded rank's rows are a contiguous run of the list, the workgroups
         // outside it return at once)
         const int row0 = d.rs ? d.rs_r0 : 0, row1 = d.rs ? d.rs_r1 : 0;
-        if (!std::getenv("DZG_REF_GEMM_STRIPS"))
-            hipLaunchKernelGGL((k_ref_gemm_lds<true>), dim3((k + 63) / 64, (nl + 63) / 64), dim3(256), 0, st,
-                               nl, k, k, Wk, ldg, Xf, ldg, d.binv, d.ldb, (const int *)lpos, row0, row1);
-        else
-            hipLaunchKernelGGL((k_ref_gemm<true>), dim3((k + 63) / 64, (nl + 63) / 64), dim3(256), 0, st,
-                               nl, k, k, Wk, ldg, Xf, ldg, d.binv, d.ldb, (const int *)lpos, row0, row1);
+        hipLaunchKernelGGL((k_ref_gemm_lds<true>), dim3((k + 63) / 64, (nl + 63) / 64), dim3(256), 0, st, nl,
+                           k, k, Wk, ldg, Xf, ldg, d.binv, d.ldb, (const int *)lpos, row0, row1);
     }
     hipLaunchKernelGGL(k_ref_done, dim3(1), dim3(1), 0, st, d.ctl, singular);
 }

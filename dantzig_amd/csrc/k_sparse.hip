@@ -874,7 +874,7 @@ __global__ __launch_bounds__(256) void k_sp_update(
 }
 
 // ---------------------------------------------------------------------------------
-// Flush: X[0:k, 0:k] -= Ub^T[:, 0:neta] * Wc.  Same tiling as k_fast_flush_mfma (one wave owns a
+// Flush: X[0:k, 0:k] -= Ub^T[:, 0:neta] * Wc.  Same tiling as k_fast_flush_mfma_lds (one wave owns a
 // 16 x 64 strip, v_mfma_f64_16x16x4_f64 along the eta index); here both operands are compact.
 // ---------------------------------------------------------------------------------
 typedef double double4_t __attribute__((ext_vector_type(4)));
@@ -885,8 +885,8 @@ __global__ __launch_bounds__(256) void k_sp_flush_mfma(const DzgCtl *ctl, double
                                                        long long ldu, const double *__restrict__ W,
                                                        long long ldw)
 {
-    // (a flush folds a FULL eta file, like k_fast_flush_mfma: one enqueued behind an iteration that
-    // did not pivot is a no-op)
+    // (a flush folds a FULL eta file, like k_fast_flush_mfma_lds: one enqueued behind an iteration
+    // that did not pivot is a no-op)
     __shared__ double s_w[R_ * SPF_LD];
     const int neta = ctl->neta, k = ctl->ncompact;
     if (neta < R_ || k <= 0 || ctl->status != DZG_RUNNING) return;

@@ -29,6 +29,7 @@
 
 #include "../../include/dantzig_amd.h"
 #include "mip_internal.h"
+#include "opts.h"
 
 int dzg_set_error(int code, const std::string &msg); // engine.hip
 
@@ -135,9 +136,8 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
     const int64_t node_limit = mo.node_limit > 0 ? mo.node_limit : 100000;
     const int npr = mo.nodes_per_round > 0 ? mo.nodes_per_round : 1024;
     const int ppl = (int)(mo.pivots_per_launch > 0 ? std::min<int64_t>(mo.pivots_per_launch, 1 << 30) : 16);
-    const long long max_iter = o.max_iter > 0 ? o.max_iter : 10000000;
-    const double eps = o.epsilon != 0.0 ? o.epsilon : 1e-12;
-    const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
+    const long long max_iter = dzg_opts_resolved(&o).max_iter;
+    const double eps = dzg_opts_resolved(&o).epsilon;
     const int nvars = (int)model->nvars;
 
     std::vector<int> ints;
@@ -179,8 +179,7 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
         build(node_md, b, true);
         StructInfo info;
         info.m = b.m;
-        const bool strict = o.numerics == DZG_NUMERICS_STRICT ||
-                            (o.numerics == DZG_NUMERICS_AUTO && b.m <= strict_rows);
+        const bool strict = dzg_opts_numerics(o, b.m) == DZG_NUMERICS_STRICT;
         if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS) {
             std::vector<int> k_of((size_t)(nvars ? nvars : 1), -1);
             for (int k = 0; k < nint; ++k) k_of[(size_t)ints[(size_t)k]] = k;

@@ -19,6 +19,7 @@
 
 #include "../../include/dantzig_amd.h"
 #include "mip_internal.h"
+#include "opts.h"
 
 namespace {
 
@@ -587,14 +588,12 @@ static int model_solve_batch(const dzg_model *models, int64_t count, const dzg_o
             return dzg_set_error(DZG_E_ARG, "model batch: ry[" + std::to_string(i) + "]: var, con, lb or ub is NULL");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
-    const int strict_rows = o.auto_strict_rows > 0 ? o.auto_strict_rows : 192;
     std::vector<Built> built((size_t)count);
     std::vector<int64_t> batched;
     for (int64_t i = 0; i < count; ++i) {
         Built &b = built[(size_t)i];
         build(&models[i], b, true);
-        const bool strict = o.numerics == DZG_NUMERICS_STRICT ||
-                            (o.numerics == DZG_NUMERICS_AUTO && b.m <= strict_rows);
+        const bool strict = dzg_opts_numerics(o, b.m) == DZG_NUMERICS_STRICT;
         if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS) batched.push_back(i);
     }
     std::vector<CoreRanging> crs((size_t)(rg ? count : 0));
