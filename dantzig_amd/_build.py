@@ -17,7 +17,7 @@ OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libdantzig_amd.so")
 ARCH = "gfx950"
 SOURCES = ["engine.hip", "k_vector.hip", "k_price.hip", "k_strict.hip", "k_fast.hip", "k_chain.hip", "k_sparse.hip", "k_refactor.hip", "k_rowshard.hip", "k_drift.hip", "k_restart.hip", "k_extend.hip", "k_remove.hip", "k_batch.hip", "k_batch_fast.hip",
-           "k_batch_restart.hip", "k_mip.hip", "k_duals.hip", "k_ranging.hip", "k_rays.hip", "model.cpp", "mip.cpp", "lpgen.cpp"]
+           "k_batch_restart.hip", "k_batch_resident.hip", "k_mip.hip", "k_duals.hip", "k_ranging.hip", "k_rays.hip", "model.cpp", "mip.cpp", "lpgen.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
          "-Wno-unused-result", "-Wno-unused-value"]
 
@@ -37,7 +37,7 @@ def _deps():
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "k_price_kernels.h"), os.path.join(CSRC, "price_small.h"),
             os.path.join(CSRC, "fast_decide.h"), os.path.join(CSRC, "fast_rows.h"),
             os.path.join(CSRC, "chain_barrier.h"), os.path.join(CSRC, "batch_strict.h"),
-            os.path.join(CSRC, "batch_host.h"), os.path.join(CSRC, "batch_restart.h"),
+            os.path.join(CSRC, "batch_host.h"), os.path.join(CSRC, "batch_restart.h"), os.path.join(CSRC, "batch_steps.h"),
             os.path.join(CSRC, "mip_internal.h"), os.path.join(CSRC, "duals.h"), os.path.join(CSRC, "ranging.h"), os.path.join(CSRC, "rays.h"),
             os.path.join(CSRC, "opts.h"),
             os.path.join(os.path.dirname(HERE), "include", "dantzig_amd.h")]

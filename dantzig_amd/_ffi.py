@@ -54,6 +54,8 @@ EXPORTS = [
     "dzg_solver_remove",
     "dzg_batch_solve_from", "dzg_debug_batch_restart_ms",
     "dzg_batch_solve_fast_from", "dzg_debug_batch_fast_restart_ms",
+    "dzg_batch_create", "dzg_batch_destroy", "dzg_batch_update", "dzg_batch_set_start",
+    "dzg_batch_resolve", "dzg_debug_batch_traffic",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -165,6 +167,11 @@ class Reopt(C.Structure):
 
 class BatchStart(C.Structure):
     _fields_ = [("basis", C.c_void_p), ("nonbasis", C.c_void_p)]
+
+
+class BatchChange(C.Structure):
+    _fields_ = [("lp", C.c_int64), ("rhs", C.c_void_p), ("c", C.c_void_p), ("constant", C.c_double),
+                ("set_constant", C.c_int32), ("reserved", C.c_int32)]
 
 
 class Extend(C.Structure):
@@ -326,6 +333,14 @@ def lib() -> C.CDLL:
                                                    C.c_int64, C.c_void_p]
         _lib.dzg_debug_batch_fast_restart_ms.restype = C.c_double
         _lib.dzg_debug_batch_fast_restart_ms.argtypes = []
+        _lib.dzg_batch_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
+                                          C.c_void_p]
+        _lib.dzg_batch_destroy.restype = None
+        _lib.dzg_batch_destroy.argtypes = [C.c_void_p]
+        _lib.dzg_batch_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
+        _lib.dzg_batch_set_start.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_batch_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.dzg_debug_batch_traffic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_debug_matrix.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
         _lib.dzg_debug_matrix_rows.restype = C.c_int64
         _lib.dzg_debug_matrix_rows.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]

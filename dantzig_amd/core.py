@@ -1001,6 +1001,218 @@ def _batch_fast(lps, log, log_cap, opts, name, invoke) -> list:
     return out
 
 
+class BatchSolver:
+    """dzg_batch: a batch of small LPs kept on the GPU between solves, the batched sibling of
+    Solver.reoptimize.  The matrices go up once; update() / update_many() change right-hand sides
+    (by constraint row), costs (by variable) and constants, and solve() re-solves the LPs it lists,
+    each from the basis its last solve ended on (cold before the first solve and after one that ended
+    singular or panicked; set_start overrides).  A solve is, result for result and bit for bit,
+    solve_batch_fast(lps_now, start=last results) -- with numerics=STRICT, solve_batch's.
+
+    lps: dense CoreLPs of at most 128 rows in slack-basis form.  log_cap: pivots of log kept per LP
+    and solve.  opts: fields of dzg_opts with solve_batch_fast's meaning (numerics STRICT, FAST or AUTO,
+    the default; near_tie_action, tie_tol, max_iter, epsilon, device).  ValueError for anything the
+    host checks refuse, before a byte goes to the device."""
+
+    def __init__(self, lps, log_cap: int = 4096, pivots_per_launch: int = 0, refactor_every: int = 0, **opts):
+        lps = list(lps)
+        if opts.get("numerics", AUTO) not in (STRICT, FAST, AUTO):
+            raise ValueError("BatchSolver: numerics is STRICT, FAST or AUTO")
+        try:
+            o = _ffi.default_opts(**opts)
+        except TypeError as exc:
+            raise ValueError(f"BatchSolver: {exc}") from None
+        if int(pivots_per_launch) < 0 or int(refactor_every) < 0 or int(log_cap) < 0:
+            raise ValueError("BatchSolver: pivots_per_launch, refactor_every and log_cap are >= 0")
+        for i, lp in enumerate(lps):
+            if lp.block is not None:
+                raise ValueError(f"lps[{i}]: a column-block LP cannot be batched")
+            if lp.a is None and lp.n_struct > 0:
+                raise ValueError(f"lps[{i}]: CSC input cannot be batched (dense `a` only)")
+            if lp.m > _ffi.BATCH_MAX_ROWS:
+                raise ValueError(f"lps[{i}]: {lp.m} rows; the batch takes at most {_ffi.BATCH_MAX_ROWS}")
+            if lp.xbar is not None or lp.zbar is not None:
+                raise ValueError(f"lps[{i}]: xbar / zbar given; a resident LP is given in slack-basis form")
+        self._h = None
+        self._shapes = [(lp.m, lp.n) for lp in lps]
+        self._lps = [_ShapeOnly(lp) for lp in lps]      # what _batch_starts reads of an LP
+        self._log_cap = int(log_cap)
+        marshalled = [_c_lp(lp) for lp in lps]
+        count = len(lps)
+        c_lps = (_ffi.Lp * max(count, 1))(*[c for c, _ in marshalled])
+        h = C.c_void_p()
+        rc = _ffi.lib().dzg_batch_create(c_lps, C.c_int64(count), C.byref(o), C.c_int64(int(pivots_per_launch)),
+                                         C.c_int64(int(refactor_every)), C.c_int64(self._log_cap), C.byref(h))
+        if rc == _ffi.E_ARG:   # the host checks, as the other batch entry points raise them
+            raise ValueError(f"dzg_batch_create: {_ffi.lib().dzg_last_error().decode()}")
+        _ffi.check(rc, "dzg_batch_create")
+        self._h = h
+
+    def __len__(self) -> int:
+        return len(self._shapes)
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("BatchSolver: the handle is closed")
+        return self._h
+
+    def _index(self, i, what: str) -> int:
+        if isinstance(i, bool) or not isinstance(i, (int, np.integer)):
+            raise ValueError(f"{what}: an LP is named by its index in the batch, not {i!r}")
+        if not 0 <= int(i) < len(self._shapes):
+            raise ValueError(f"{what}: LP {int(i)} out of range (the batch holds {len(self._shapes)})")
+        return int(i)
+
+    def update(self, i: int, b=None, c=None, constant=None) -> None:
+        """LP i's right-hand side (m, by constraint row), costs (n, by variable) and / or constant from
+        its next solve on."""
+        self.update_many([(i, b, c, constant)])
+
+    def update_many(self, changes) -> None:
+        """update() for several LPs in one call: (i, b, c, constant) tuples, None = keep.  An LP is
+        listed once per call.  ValueError, and nothing changed, for a bad entry."""
+        h = self._handle()
+        changes = [tuple(ch) + (None,) * (4 - len(tuple(ch))) for ch in changes]
+        keep, seen = [], set()
+        chg = (_ffi.BatchChange * max(len(changes), 1))()
+        for k, (i, b, c, constant) in enumerate(changes):
+            i = self._index(i, f"changes[{k}]")
+            if i in seen:
+                raise ValueError(f"changes[{k}]: LP {i} listed twice")
+            seen.add(i)
+            m, n = self._shapes[i]
+            if b is None and c is None and constant is None:
+                raise ValueError(f"changes[{k}]: LP {i}: no b, no c, no constant")
+            chg[k].lp = i
+            for name, arr, size in (("b", b, m), ("c", c, n)):
+                if arr is None:
+                    continue
+                arr = f64(arr)
+                if arr.shape != (size,):
+                    raise ValueError(f"changes[{k}]: LP {i}: {name} has {arr.size} entries, the LP {size}")
+                bad = np.flatnonzero(~np.isfinite(arr))
+                if bad.size:
+                    raise ValueError(f"changes[{k}]: LP {i}: {name}[{int(bad[0])}] is not finite")
+                keep.append(arr)
+                setattr(chg[k], "rhs" if name == "b" else "c", arr.ctypes.data)
+            if constant is not None:
+                if not np.isfinite(float(constant)):
+                    raise ValueError(f"changes[{k}]: LP {i}: constant is not finite")
+                chg[k].constant, chg[k].set_constant = float(constant), 1
+        rc = _ffi.lib().dzg_batch_update(h, chg, C.c_int64(len(changes)))
+        if rc == _ffi.E_ARG:
+            raise ValueError(f"dzg_batch_update: {_ffi.lib().dzg_last_error().decode()}")
+        _ffi.check(rc, "dzg_batch_update")
+
+    def set_start(self, i: int, start) -> None:
+        """The basis LP i starts its next solve from: None (cold), a CoreResult (one that ended singular
+        or panicked counts as None) or a (basis, nonbasis) pair."""
+        h = self._handle()
+        i = self._index(i, "set_start")
+        starts = [None] * len(self._lps)
+        starts[i] = start
+        try:
+            s = _batch_starts(self._lps, starts)[i]
+        except ValueError as exc:
+            raise ValueError(str(exc).replace(f"start[{i}]", f"set_start({i})")) from None
+        if s is None:
+            rc = _ffi.lib().dzg_batch_set_start(h, C.c_int64(i), None, None)
+        else:
+            rc = _ffi.lib().dzg_batch_set_start(h, C.c_int64(i), ptr(s[0]), ptr(s[1]))
+        if rc == _ffi.E_ARG:
+            raise ValueError(f"dzg_batch_set_start: {_ffi.lib().dzg_last_error().decode()}")
+        _ffi.check(rc, "dzg_batch_set_start")
+
+    def solve(self, which=None, log: bool = True) -> list:
+        """Solve the LPs `which` lists (None: all, in index order); result k is LP which[k]'s
+        CoreResult, as solve_batch_fast reports it."""
+        import time
+
+        h = self._handle()
+        if which is None:
+            ids = list(range(len(self._shapes)))
+        else:
+            ids = [self._index(i, f"which[{k}]") for k, i in enumerate(which)]
+            if len(set(ids)) != len(ids):
+                dup = next(i for k, i in enumerate(ids) if i in ids[:k])
+                raise ValueError(f"which: LP {dup} listed twice")
+        count = len(ids)
+        mo = np.concatenate([[0], np.cumsum([self._shapes[i][0] for i in ids])]).astype(np.int64)
+        qo = np.concatenate([[0], np.cumsum([self._shapes[i][1] - self._shapes[i][0] for i in ids])]).astype(np.int64)
+        basis, x, xbar = np.zeros(mo[-1] + 1, np.int64), np.zeros(mo[-1] + 1), np.zeros(mo[-1] + 1)
+        nonbasis, z, zbar = np.zeros(qo[-1] + 1, np.int64), np.zeros(qo[-1] + 1), np.zeros(qo[-1] + 1)
+        cap = self._log_cap if log else 0
+        logs = np.zeros((count, max(cap, 1)), dtype=_PIVOT_DTYPE)
+        margins = np.full((count, max(cap, 1)), np.inf)
+        res = (_ffi.Result * max(count, 1))()
+        for k in range(count):
+            r = res[k]
+            r.basis = basis.ctypes.data + 8 * int(mo[k])
+            r.x = x.ctypes.data + 8 * int(mo[k])
+            r.xbar = xbar.ctypes.data + 8 * int(mo[k])
+            r.nonbasis = nonbasis.ctypes.data + 8 * int(qo[k])
+            r.z = z.ctypes.data + 8 * int(qo[k])
+            r.zbar = zbar.ctypes.data + 8 * int(qo[k])
+            r.log = logs.ctypes.data + logs.strides[0] * k if cap > 0 else None
+            r.margins = margins.ctypes.data + margins.strides[0] * k if cap > 0 else None
+            r.log_cap = cap
+        c_which = i64(ids)
+        t0 = time.perf_counter()
+        rc = _ffi.lib().dzg_batch_resolve(h, None if which is None else ptr(c_which), C.c_int64(count), res)
+        wall_ms = (time.perf_counter() - t0) * 1e3
+        if rc == _ffi.E_ARG:
+            raise ValueError(f"dzg_batch_resolve: {_ffi.lib().dzg_last_error().decode()}")
+        _ffi.check(rc, "dzg_batch_resolve")
+        out = []
+        for k in range(count):
+            r = res[k]
+            cnt = int(min(r.iterations, cap))
+            arr = logs[k, :cnt]
+            pivots = list(zip(arr["kind"].tolist(), arr["entering"].tolist(), arr["leaving"].tolist(),
+                              arr["mu"].tolist()))
+            a0, a1, b0, b1 = int(mo[k]), int(mo[k + 1]), int(qo[k]), int(qo[k + 1])
+            fast = r.numerics_used != STRICT
+            out.append(CoreResult(
+                status=STATUS_NAMES.get(r.status, str(r.status)), status_code=r.status,
+                numerics="fast" if fast else "strict", iterations=int(r.iterations), objective=float(r.objective),
+                basis=basis[a0:a1].copy(), nonbasis=nonbasis[b0:b1].copy(), x=x[a0:a1].copy(),
+                xbar=xbar[a0:a1].copy(), z=z[b0:b1].copy(), zbar=zbar[b0:b1].copy(), pivots=pivots,
+                solve_ms=wall_ms, margins=margins[k, :cnt].copy() if fast and log else None, **_counters(r)))
+        return out
+
+    def traffic(self) -> tuple[int, int, float]:
+        """(host-to-device bytes, device-to-host bytes, stage + restart device ms) of the last solve()."""
+        nbytes, ms = (C.c_int64 * 2)(), (C.c_double * 1)()
+        _ffi.check(_ffi.lib().dzg_debug_batch_traffic(self._handle(), nbytes, ms), "dzg_debug_batch_traffic")
+        return int(nbytes[0]), int(nbytes[1]), float(ms[0])
+
+    def close(self) -> None:
+        if self._h is not None:
+            _ffi.lib().dzg_batch_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _ShapeOnly:
+    """What BatchSolver keeps of a CoreLP for _batch_starts: m, n and the slack-basis codes."""
+
+    def __init__(self, lp: CoreLP):
+        self.m, self.n, self.n_struct = lp.m, lp.n, lp.n_struct
+        self.basis = i64(lp.basis).copy()
+        self.var_col = None if lp.var_col is None else i64(lp.var_col).copy()
+
+
 def core_solve_full_csc(m: int, n: int, col_ptr, row_idx, val, c, constant, basis, nonbasis, x, z,
                         log_cap: int = 1 << 16, **opts) -> CoreResult:
     """dzg_core_solve_full_csc: Level 1 on the reference's own `Simplex` fields -- ONE CSC over all n

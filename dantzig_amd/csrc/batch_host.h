@@ -386,9 +386,10 @@ inline int download(Device &D, const Layout &L, unsigned char *host)
 // launch(bucket, list, n, next_list, next_count) runs entries list[0..n) of a bucket; a kernel
 // appends the entries that are still running to next_list through atomicAdd(next_count, 1).
 // cur / nxt: two device lists laid out by `seg`; counts: kBuckets device ints; live: entries per bucket.
+// rounds (optional): counts the readbacks, kBuckets ints each.
 template <class Launch>
 int run_rounds(int *cur, int *nxt, int *counts, const Segments &seg, std::array<int, kBuckets> live,
-               hipStream_t st, Launch launch)
+               hipStream_t st, Launch launch, int *rounds = nullptr)
 {
     for (;;) {
         bool any = false;
@@ -402,6 +403,7 @@ int run_rounds(int *cur, int *nxt, int *counts, const Segments &seg, std::array<
         if (!any) return 0;
         DZG_HIP(hipMemcpyAsync(live.data(), counts, sizeof(int) * kBuckets, hipMemcpyDeviceToHost, st));
         DZG_HIP(hipStreamSynchronize(st));
+        if (rounds) ++*rounds;
         std::swap(cur, nxt);
     }
 }

@@ -33,6 +33,7 @@
 
 #include "batch_host.h"
 #include "batch_restart.h"
+#include "batch_steps.h"
 #include "batch_strict.h"
 #include "common.h"
 #include "duals.h"
@@ -109,6 +110,20 @@ void launch_bucket(int b, const BArgs &g, const int *list, int n, int *next_list
     });
 }
 
+// The kernel arguments of a solve that lies as R says (mmax is the launch's own).
+BArgs strict_args(const dzg_steps::StrictRun &R)
+{
+    BArgs g;
+    bh::wire(g, R.dev, *R.L);
+    g.status = (int *)(R.dev + R.status);
+    g.iter = (long long *)(R.dev + R.iter);
+    g.max_iter = R.max_iter;
+    g.eps = R.eps;
+    g.ppl = R.ppl;
+    g.mmax = 0;
+    return g;
+}
+
 // What a call asks for beside the solve, and where it goes.
 struct BatchExtras {
     bool duals = false, ranging = false, rays = false;
@@ -138,6 +153,7 @@ struct Ctx {
     size_t rlist = 0, rd = 0, ry = 0, rscal = 0;
     std::vector<unsigned char> host;
     bh::Device D;
+    dzg_steps::StrictRun R; // where the solve lies; max_iter, eps and ppl are batch_solve's to set
     BArgs g;
     std::vector<unsigned char> cx0;    // c .. x0 as uploaded
     std::vector<unsigned char> dhost;  // y .. scal as downloaded
@@ -198,9 +214,13 @@ int pack_and_upload(Ctx &C)
         }
         DZG_HIP(hipMemcpyAsync(dev + C.c, C.cx0.data(), C.cx0.size(), hipMemcpyHostToDevice, C.D.st));
     }
-    bh::wire(C.g, dev, L);
-    C.g.status = (int *)(dev + C.status);
-    C.g.iter = (long long *)(dev + C.iter);
+    C.R.dev = dev;
+    C.R.L = &C.L;
+    C.R.status = C.status;
+    C.R.iter = C.iter;
+    C.R.c = C.c;
+    C.R.st = C.D.st;
+    C.g = strict_args(C.R);
     return 0;
 }
 
@@ -217,29 +237,11 @@ int restart_pass(Ctx &C, std::array<int, kBuckets> &live)
     // the next round's list is free until the first round appends to it
     int *wlist = (int *)(dev + C.L.list2);
     DZG_HIP(hipMemcpyAsync(wlist, warm.list.data(), sizeof(int) * warm.list.size(), hipMemcpyHostToDevice, st));
-    DzgBatchRestartArgs a;
-    a.lp = C.g.lp;
-    a.A = C.g.A;
-    a.var_col = C.g.var_col;
-    a.basis = C.g.basis;
-    a.nonbasis = C.g.nonbasis;
-    a.x = C.g.x;
-    a.xbar = C.g.xbar;
-    a.z = C.g.z;
-    a.zbar = C.g.zbar;
-    a.c = (const double *)(dev + C.c);
-    a.status = C.g.status;
     bh::Events ev;
     DZG_HIP(hipEventCreate(&ev.e0));
     DZG_HIP(hipEventCreate(&ev.e1));
     DZG_HIP(hipEventRecord(ev.e0, st));
-    for (int b = 0; b < kBuckets; ++b) {
-        const int cnt = wseg[(size_t)b + 1] - wseg[(size_t)b];
-        if (cnt == 0) continue;
-        a.mmax = C.P.mmax[b];
-        dzg_launch_batch_restart(b, a, wlist + wseg[(size_t)b], cnt, st);
-        DZG_HIP(hipGetLastError());
-    }
+    if (const int rc = dzg_steps::strict_restart(C.R, wlist, wseg, C.P.mmax)) return rc;
     DZG_HIP(hipEventRecord(ev.e1, st));
     std::vector<int> status((size_t)C.N);
     DZG_HIP(hipMemcpyAsync(status.data(), dev + C.status, sizeof(int) * C.N, hipMemcpyDeviceToHost, st));
@@ -498,10 +500,7 @@ void write_results(const Ctx &C)
     const long long *iters = (const long long *)(C.host.data() + C.iter);
     for (int i = 0; i < C.N; ++i) {
         dzg_result &r = C.res[i];
-        r.status = C.stat()[i];
-        r.numerics_used = DZG_NUMERICS_STRICT;
-        r.iterations = iters[i];
-        bh::unpack_common(C.lps[i], C.P.desc[(size_t)i], view, r);
+        dzg_steps::strict_unpack(C.lps[i], C.P.desc[(size_t)i], view, C.stat()[i], iters[i], r);
         if (C.ex.rays) write_ray(C, i);
         if (C.ex.ranging) write_ranging(C, i);
         if (C.ex.duals) write_duals(C, i);
@@ -511,6 +510,58 @@ void write_results(const Ctx &C)
 } // namespace
 
 #define DZG_BATCH_DEFAULT_PPL 16
+
+// ---- the steps of batch_steps.h
+int dzg_steps::strict_ppl(int64_t pivots_per_launch)
+{
+    return (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30) : DZG_BATCH_DEFAULT_PPL);
+}
+
+int dzg_steps::strict_restart(const StrictRun &R, const int *wlist, const bh::Segments &wseg, const int *mmax)
+{
+    const BArgs g = strict_args(R);
+    DzgBatchRestartArgs a;
+    a.lp = g.lp;
+    a.A = g.A;
+    a.var_col = g.var_col;
+    a.basis = g.basis;
+    a.nonbasis = g.nonbasis;
+    a.x = g.x;
+    a.xbar = g.xbar;
+    a.z = g.z;
+    a.zbar = g.zbar;
+    a.c = (const double *)(R.dev + R.c);
+    a.status = g.status;
+    for (int b = 0; b < kBuckets; ++b) {
+        const int cnt = wseg[(size_t)b + 1] - wseg[(size_t)b];
+        if (cnt == 0) continue;
+        a.mmax = mmax[b];
+        dzg_launch_batch_restart(b, a, wlist + wseg[(size_t)b], cnt, R.st);
+        DZG_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int dzg_steps::strict_rounds(const StrictRun &R, int *cur, int *nxt, const bh::Segments &seg,
+                             const std::array<int, bh::kBuckets> &live, const int *mmax, int *rounds)
+{
+    const BArgs g = strict_args(R);
+    return bh::run_rounds(cur, nxt, (int *)(R.dev + R.L->count), seg, live, R.st,
+                          [&](int b, const int *list, int n, int *next_list, int *next_count) {
+                              BArgs gb = g;
+                              gb.mmax = mmax[b];
+                              launch_bucket(b, gb, list, n, next_list, next_count, R.st);
+                          }, rounds);
+}
+
+void dzg_steps::strict_unpack(const dzg_lp &lp, const DzgBatchLp &d, const bh::HostView &view, int status,
+                              long long iter, dzg_result &r)
+{
+    r.status = status;
+    r.numerics_used = DZG_NUMERICS_STRICT;
+    r.iterations = iter;
+    bh::unpack_common(lp, d, view, r);
+}
 
 // dzg_batch_solve and, behind the solve and on sections of their own (the solve's layout does not
 // move), what `ex` asks for: the duals of the LPs that end OPTIMAL (k_duals.hip), their ranges
@@ -546,22 +597,16 @@ static int batch_solve(const dzg_lp *lps, int64_t count, const dzg_opts *opts, i
     if (const int rc = bh::use_device(o.device)) return rc;
 
     Ctx C(lps, start, (int)count, res, ex, max_iter);
-    C.g.max_iter = max_iter;
-    C.g.eps = dzg_opts_resolved(&o).epsilon;
-    C.g.ppl = (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30) : DZG_BATCH_DEFAULT_PPL);
+    C.R.max_iter = max_iter;
+    C.R.eps = dzg_opts_resolved(&o).epsilon;
+    C.R.ppl = dzg_steps::strict_ppl(pivots_per_launch);
     if (const int rc = pack_and_upload(C)) return rc;
     unsigned char *dev = C.D.arena;
-    hipStream_t st = C.D.st;
     std::array<int, kBuckets> live = bh::live_of(C.P.bucket_n);
     if (C.warm)
         if (const int rc = restart_pass(C, live)) return rc;
-    const int rc_rounds = bh::run_rounds(
-        (int *)(dev + C.L.list), (int *)(dev + C.L.list2), (int *)(dev + C.L.count), bh::segments(C.P.bucket_n),
-        live, st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
-            BArgs gb = C.g;
-            gb.mmax = C.P.mmax[b];
-            launch_bucket(b, gb, list, n, next_list, next_count, st);
-        });
+    const int rc_rounds = dzg_steps::strict_rounds(C.R, (int *)(dev + C.L.list), (int *)(dev + C.L.list2),
+                                                   bh::segments(C.P.bucket_n), live, C.P.mmax);
     if (rc_rounds) return rc_rounds;
     if (const int rc = bh::download(C.D, C.L, C.host.data())) return rc;
     if (ex.duals)

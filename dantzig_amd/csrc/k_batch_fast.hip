@@ -42,6 +42,7 @@
 #include <vector>
 
 #include "batch_host.h"
+#include "batch_steps.h"
 #include "batch_strict.h"
 #include "common.h"
 #include "fast_decide.h"
@@ -600,10 +601,13 @@ thread_local double t_restart_ms = 0.0; // dzg_debug_batch_fast_restart_ms
 
 // ---- the restart state of the warm LPs: c goes up, one workgroup each, bucket by bucket, before the
 // first round.  A singular start leaves the first round's lists; `live` follows.
-int restart_pass(const dzg_lp *lps, const dzg_batch_start *start, const bh::Packed &P, const bh::Layout &L,
-                 unsigned char *host, unsigned char *dev, size_t s_c, size_t s_status, const FArgs &g,
-                 hipStream_t st, std::array<int, bh::kBuckets> &live)
+int restart_pass(const dzg_lp *lps, const dzg_batch_start *start, const bh::Packed &P, const dzg_steps::FastRun &R,
+                 unsigned char *host, std::array<int, bh::kBuckets> &live)
 {
+    const bh::Layout &L = *R.L;
+    unsigned char *dev = R.dev;
+    hipStream_t st = R.st;
+    const size_t s_c = R.c, s_status = R.rst;
     const int N = L.N;
     std::vector<double> cost((size_t)P.nvc);
     for (int i = 0; i < N; ++i)
@@ -617,15 +621,7 @@ int restart_pass(const dzg_lp *lps, const dzg_batch_start *start, const bh::Pack
     DZG_HIP(hipEventCreate(&ev.e0));
     DZG_HIP(hipEventCreate(&ev.e1));
     DZG_HIP(hipEventRecord(ev.e0, st));
-    for (int b = 0; b < bh::kBuckets; ++b) {
-        const int cnt = warm.seg[(size_t)b + 1] - warm.seg[(size_t)b];
-        if (cnt == 0) continue;
-        FArgs gb = g;
-        gb.mmax = P.mmax[b];
-        launch_restart_bucket(b, gb, (const double *)(dev + s_c), (int *)(dev + s_status),
-                              wlist + warm.seg[(size_t)b], cnt, st);
-        DZG_HIP(hipGetLastError());
-    }
+    if (const int rc = dzg_steps::fast_restart(R, wlist, warm.seg, P.mmax)) return rc;
     DZG_HIP(hipEventRecord(ev.e1, st));
     int *status = (int *)(host + s_status);
     DZG_HIP(hipMemcpyAsync(status, dev + s_status, sizeof(int) * N, hipMemcpyDeviceToHost, st));
@@ -703,10 +699,87 @@ void write_fast(const dzg_lp &lp, const DzgBatchLp &d, const FState &fs, const i
     r.refactors = fs.refactors;
 }
 
+// The kernel arguments of a solve that lies as R says (mmax is the launch's own).
+FArgs fast_args(const dzg_steps::FastRun &R)
+{
+    FArgs g;
+    bh::wire(g, R.dev, *R.L);
+    g.state = (FState *)(R.dev + R.state);
+    g.log_margin = (double *)(R.dev + R.margin);
+    g.eps = R.eps;
+    g.ppl = R.ppl;
+    g.refactor_every = R.refactor_every;
+    g.mmax = 0;
+    return g;
+}
+
 } // namespace
 
 #define DZG_BATCH_FAST_DEFAULT_PPL 128
 #define DZG_BATCH_FAST_DEFAULT_REFACTOR 64
+
+// ---- the steps of batch_steps.h
+int dzg_steps::fast_ppl(int64_t pivots_per_launch)
+{
+    return (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30) : DZG_BATCH_FAST_DEFAULT_PPL);
+}
+
+int dzg_steps::fast_refactor_every(int64_t refactor_every)
+{
+    return (int)(refactor_every > 0 ? std::min<int64_t>(refactor_every, 1 << 30) : DZG_BATCH_FAST_DEFAULT_REFACTOR);
+}
+
+size_t dzg_steps::fast_state_bytes() { return sizeof(FState); }
+
+void dzg_steps::fast_state_init(void *block, const dzg_opts &o, long long max_iter)
+{
+    std::memset(block, 0, sizeof(FState));
+    start_ctl(((FState *)block)->ctl, o, max_iter);
+}
+
+int dzg_steps::fast_restart(const FastRun &R, const int *wlist, const bh::Segments &wseg, const int *mmax)
+{
+    const FArgs g = fast_args(R);
+    for (int b = 0; b < bh::kBuckets; ++b) {
+        const int cnt = wseg[(size_t)b + 1] - wseg[(size_t)b];
+        if (cnt == 0) continue;
+        FArgs gb = g;
+        gb.mmax = mmax[b];
+        launch_restart_bucket(b, gb, (const double *)(R.dev + R.c), (int *)(R.dev + R.rst),
+                              wlist + wseg[(size_t)b], cnt, R.st);
+        DZG_HIP(hipGetLastError());
+    }
+    return 0;
+}
+
+int dzg_steps::fast_rounds(const FastRun &R, int *cur, int *nxt, const bh::Segments &seg,
+                           const std::array<int, bh::kBuckets> &live, const int *mmax, double *w_out,
+                           const long long *w_off, int *rounds)
+{
+    const FArgs g = fast_args(R);
+    return bh::run_rounds(cur, nxt, (int *)(R.dev + R.L->count), seg, live, R.st,
+                          [&](int b, const int *list, int n, int *next_list, int *next_count) {
+                              FArgs gb = g;
+                              gb.mmax = mmax[b];
+                              if (w_out)
+                                  launch_bucket<true>(b, gb, list, n, next_list, next_count, R.st, w_out, w_off);
+                              else
+                                  launch_bucket<false>(b, gb, list, n, next_list, next_count, R.st);
+                          }, rounds);
+}
+
+void dzg_steps::fast_unpack(const dzg_lp &lp, const DzgBatchLp &d, const bh::HostView &view, const void *block,
+                            const double *margins, dzg_result &r)
+{
+    const FState &fs = *(const FState *)block;
+    r.status = fs.ctl.status;
+    r.numerics_used = DZG_NUMERICS_FAST;
+    r.iterations = fs.ctl.iter;
+    bh::unpack_common(lp, d, view, r);
+    write_fast(lp, d, fs, view.basis, margins, r);
+}
+
+long long dzg_steps::fast_state_iter(const void *block) { return ((const FState *)block)->ctl.iter; }
 
 // The FAST batch itself: `o.near_tie_action` and `o.tie_tol` as given.  The driver is batch_host.h's,
 // as in k_batch.hip; the state block and the margins are FAST's own sections.
@@ -743,49 +816,37 @@ static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int
     std::vector<unsigned char> host(L.download_end, 0);
     bh::fill_upload(host.data(), L, P, lps, start);
     FState *fs = (FState *)(host.data() + s_state);
-    for (int i = 0; i < N; ++i) start_ctl(fs[i].ctl, o, max_iter);
+    for (int i = 0; i < N; ++i) dzg_steps::fast_state_init(&fs[i], o, max_iter);
     if (warm) std::fill_n((int *)(host.data() + s_rst), N, (int)DZG_RUNNING);
     if (dump) std::memcpy(host.data() + s_woff, w_off.data(), sizeof(long long) * N);
     bh::Device D;
     if (const int rc = bh::upload(D, L, host.data())) return rc;
     unsigned char *dev = D.arena;
 
-    FArgs g;
-    bh::wire(g, dev, L);
-    g.state = (FState *)(dev + s_state);
-    g.log_margin = (double *)(dev + s_lmg);
-    g.eps = dzg_opts_resolved(&o).epsilon;
-    g.ppl = dump ? (int)max_iter + 1
-          : (int)(pivots_per_launch > 0 ? std::min<int64_t>(pivots_per_launch, 1 << 30)
-                                        : DZG_BATCH_FAST_DEFAULT_PPL);
-    g.refactor_every = (int)(refactor_every_arg > 0 ? std::min<int64_t>(refactor_every_arg, 1 << 30)
-                                                    : DZG_BATCH_FAST_DEFAULT_REFACTOR);
-    g.mmax = 0;
+    dzg_steps::FastRun R;
+    R.dev = dev;
+    R.L = &L;
+    R.state = s_state;
+    R.margin = s_lmg;
+    R.rst = s_rst;
+    R.c = s_c;
+    R.eps = dzg_opts_resolved(&o).epsilon;
+    R.ppl = dump ? (int)max_iter + 1 : dzg_steps::fast_ppl(pivots_per_launch);
+    R.refactor_every = dzg_steps::fast_refactor_every(refactor_every_arg);
+    R.st = D.st;
     std::array<int, bh::kBuckets> live = bh::live_of(P.bucket_n);
     if (warm)
-        if (const int rc = restart_pass(lps, start, P, L, host.data(), dev, s_c, s_rst, g, D.st, live)) return rc;
-    const int rc_rounds = bh::run_rounds(
-        (int *)(dev + L.list), (int *)(dev + L.list2), (int *)(dev + L.count), bh::segments(P.bucket_n),
-        live, D.st, [&](int b, const int *list, int n, int *next_list, int *next_count) {
-            FArgs gb = g;
-            gb.mmax = P.mmax[b];
-            if (dump)
-                launch_bucket<true>(b, gb, list, n, next_list, next_count, D.st, (double *)(dev + s_w),
-                                    (const long long *)(dev + s_woff));
-            else
-                launch_bucket<false>(b, gb, list, n, next_list, next_count, D.st);
-        });
+        if (const int rc = restart_pass(lps, start, P, R, host.data(), live)) return rc;
+    const int rc_rounds = dzg_steps::fast_rounds(
+        R, (int *)(dev + L.list), (int *)(dev + L.list2), bh::segments(P.bucket_n), live, P.mmax,
+        dump ? (double *)(dev + s_w) : nullptr, dump ? (const long long *)(dev + s_woff) : nullptr);
     if (rc_rounds) return rc_rounds;
     if (const int rc = bh::download(D, L, host.data())) return rc;
 
     const bh::HostView view(host.data(), L);
     for (int i = 0; i < N; ++i) {
-        dzg_result &r = res[i];
-        r.status = fs[i].ctl.status;
-        r.numerics_used = DZG_NUMERICS_FAST;
-        r.iterations = fs[i].ctl.iter;
-        bh::unpack_common(lps[i], P.desc[(size_t)i], view, r);
-        write_fast(lps[i], P.desc[(size_t)i], fs[i], view.basis, (const double *)(host.data() + s_lmg), r);
+        dzg_steps::fast_unpack(lps[i], P.desc[(size_t)i], view, &fs[i], (const double *)(host.data() + s_lmg),
+                               res[i]);
     }
     if (dump) std::memcpy(w_out, host.data() + s_w, sizeof(double) * (size_t)w_off[(size_t)N]);
     return 0;

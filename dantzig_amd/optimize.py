@@ -678,10 +678,11 @@ class _BatchModel:
     __slots__ = ("problem", "objective", "rhs", "form", "order", "last")
 
 
-def sessions(problems, fast: bool = False, **core_opts) -> "SessionBatch":
+def sessions(problems, fast: bool = False, resident: bool = False, **core_opts) -> "SessionBatch":
     """A SessionBatch over `problems` (Minimize / Maximize models): the batched sibling of
-    Optimize.session().  fast=True: the batch runs FAST numerics (SessionBatch)."""
-    return SessionBatch(problems, fast=fast, **core_opts)
+    Optimize.session().  fast=True: the batch runs FAST numerics; resident=True: the batch stays on
+    the GPU between calls (SessionBatch)."""
+    return SessionBatch(problems, fast=fast, resident=resident, **core_opts)
 
 
 class SessionBatch:
@@ -708,10 +709,19 @@ class SessionBatch:
     model whose FAST solve comes within rounding of a tie, or ends singular, is solved by the STRICT
     batch in the same call, from the same start); `strict_fallbacks` holds, per call, the number of
     models whose result is STRICT's (a warm model often is one of them: the split pair x+ - x- of
-    the lowering leaves a reduced cost at zero up to rounding)."""
+    the lowering leaves a reduced cost at zero up to rounding).
 
-    def __init__(self, problems, fast: bool = False, **core_opts) -> None:
+    resident=True: the batch is a core.BatchSolver.  The first solve() puts
+    every model's matrix on the GPU; a later call sends the right-hand sides, costs and constants
+    that changed and nothing else, and returns what the stateless batch returns, bit for bit.  When a
+    change alters a model's standard form beyond b, c and the constant the handle is built again
+    from the new forms (`rebuilds` counts that) and the other models carry on from their last
+    bases.  close(), or leaving the `with` block, frees the GPU memory; a later solve() starts over."""
+
+    def __init__(self, problems, fast: bool = False, resident: bool = False, **core_opts) -> None:
         problems = list(problems)
+        if not isinstance(resident, (bool, np.bool_)):
+            raise TypeError(f"sessions: resident is True or False, not {resident!r}")
         for i, p in enumerate(problems):
             if not isinstance(p, Optimize):
                 raise TypeError(f"problems[{i}] is a {type(p).__name__}, not a Minimize / Maximize")
@@ -731,6 +741,9 @@ class SessionBatch:
         self.pivots: list = []
         self.cold: list = []
         self.strict_fallbacks: list = []
+        self._resident = bool(resident)
+        self._handle = None
+        self.rebuilds = 0
 
     @staticmethod
     def _lower(i: int, p: "Optimize", objective, rhs: dict):
@@ -781,8 +794,11 @@ class SessionBatch:
         lps = [core.CoreLP(a=f.a, c=f.c, basis=f.basis, nonbasis=f.nonbasis, x=f.x, z=f.z, var_col=f.var_col,
                            constant=f.constant) for _, _, f, _, _ in staged]
         start = [st.last if warm else None for st, (_, _, _, _, warm) in zip(self._models, staged)]
-        solve = core.solve_batch_fast if self._fast else core.solve_batch
-        results = solve(lps, log=False, start=start if any(s is not None for s in start) else None, **self._opts)
+        if self._resident:
+            results = self._solve_resident(lps, [f for _, _, f, _, _ in staged], start)
+        else:
+            solve = core.solve_batch_fast if self._fast else core.solve_batch
+            results = solve(lps, log=False, start=start if any(s is not None for s in start) else None, **self._opts)
         out = []
         for i, (st, (objective, new_rhs, form, order, _), res) in enumerate(zip(self._models, staged, results)):
             st.objective, st.rhs, st.form, st.order, st.last = objective, new_rhs, form, order, res
@@ -806,3 +822,53 @@ class SessionBatch:
                 if isinstance(o, Exception):
                     raise o
         return out
+
+    def _solve_resident(self, lps, forms, start) -> list:
+        """This call on the resident handle: start[i] is what the stateless call would hand model i
+        (None: cold).  The handle is built from `lps` when there is none or when a model's standard
+        form no longer fits the one it holds; otherwise only what moved is sent."""
+        fits = self._handle is not None and all(
+            f.same_shape_as(st.form) and np.array_equal(f.basis, st.form.basis)
+            and np.array_equal(f.nonbasis, st.form.nonbasis) for f, st in zip(forms, self._models))
+        if not fits:
+            if self._handle is not None:
+                self.close()
+                self.rebuilds += 1
+            opts = dict(self._opts)
+            if not self._fast:
+                opts["numerics"] = core.STRICT
+            self._handle = core.BatchSolver(lps, log_cap=0, **opts)
+            for i, s in enumerate(start):
+                if s is not None:
+                    self._handle.set_start(i, s)
+            return self._handle.solve(log=False)
+        changes = []
+        for i, (f, st) in enumerate(zip(forms, self._models)):
+            old = st.form
+            b = None
+            if f.x.tobytes() != old.x.tobytes():
+                b = np.empty(f.m)
+                b[-1 - f.var_col[f.basis]] = f.x      # by constraint row
+            c = f.c if f.c.tobytes() != old.c.tobytes() else None
+            same_constant = np.float64(f.constant).tobytes() == np.float64(old.constant).tobytes()
+            constant = None if same_constant else float(f.constant)
+            if b is not None or c is not None or constant is not None:
+                changes.append((i, b, c, constant))
+            if start[i] is None:
+                self._handle.set_start(i, None)
+        if changes:
+            self._handle.update_many(changes)
+        return self._handle.solve(log=False)
+
+    def close(self) -> None:
+        """Frees the resident handle (resident=True); the models' last bases stay on the host, so the
+        next solve() builds a new handle and carries on from them."""
+        if self._handle is not None:
+            self._handle.close()
+            self._handle = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

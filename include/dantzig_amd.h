@@ -834,6 +834,68 @@ int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, i
  * LP. */
 double dzg_debug_batch_fast_restart_ms(void);
 
+/* ---- A batch kept resident on the device between solves (csrc/k_batch_resident.hip) ------- */
+
+/* The batched sibling of dzg_solver_reoptimize: the matrices, var_col and the descriptors of `count`
+ * small LPs go up once; every later solve uploads the right-hand sides and costs that changed and
+ * nothing else.  The handle holds, per LP i: the matrix and var_col (fixed at create); the current
+ * rhs_i, c_i and constant_i; and last_i, the basis its last solve ended on -- none before the first
+ * solve and after a solve that ended DZG_SINGULAR or DZG_PANIC.  One call at a time per handle;
+ * several handles may live at once.  While it lives a handle holds one device allocation the size of
+ * a stateless call's (the log sections sized by log_cap) plus rhs, c and three copies of a basis.
+ * A HIP failure inside any call leaves the handle failed: every later call returns DZG_E_DEVICE;
+ * dzg_batch_destroy still frees everything.
+ * Out of scope: duals, ranging and rays on the handle; adding or removing rows, columns or LPs;
+ * the node LPs of dzg_mip_solve; folding the restart into the first launch. */
+typedef struct dzg_batch dzg_batch;
+
+/* lps[0..count): dense, m <= DZG_BATCH_MAX_ROWS, in slack-basis form (own basis all slack, one
+ * per row; xbar == zbar == NULL).  opts->numerics: STRICT, FAST or AUTO, with the meaning
+ * dzg_batch_solve_fast_from gives them (opts == NULL: AUTO).  pivots_per_launch / refactor_every
+ * as there.  log_cap >= 0: pivots of log kept per LP and per solve (0: none).
+ * Host checks (DZG_E_ARG, the LP's index in dzg_last_error, before any device work): every check of
+ * dzg_batch_solve_fast_from, an own basis that is not all slack, xbar / zbar given, log_cap < 0,
+ * out == NULL.  count == 0 is a valid, empty handle. */
+int  dzg_batch_create(const dzg_lp *lps, int64_t count, const dzg_opts *opts,
+                      int64_t pivots_per_launch, int64_t refactor_every, int64_t log_cap,
+                      dzg_batch **out);
+void dzg_batch_destroy(dzg_batch *b);
+
+typedef struct {
+    int64_t lp;            /* index in the batch                                   */
+    const double *rhs;     /* m, by constraint row (as dzg_reopt); NULL = keep      */
+    const double *c;       /* n, by variable, core sense; NULL = keep               */
+    double constant;       /* used when set_constant != 0                           */
+    int32_t set_constant, reserved;
+} dzg_batch_change;
+/* Updates accumulate until the LP is next solved; per array the last value wins.  DZG_E_ARG, the
+ * handle unchanged: NULL arguments with nchg > 0, lp out of range or listed twice in one call, an
+ * entry with rhs, c and set_constant all empty, a NaN or infinite entry (array and index named). */
+int dzg_batch_update(dzg_batch *b, const dzg_batch_change *chg, int64_t nchg);
+
+/* The basis LP `lp` starts its next solve from; basis == NULL: cold (the slack basis).
+ * DZG_E_ARG: not a partition of 0 .. n-1 (dzg_batch_solve_from's check). */
+int dzg_batch_set_start(dzg_batch *b, int64_t lp, const int64_t *basis, const int64_t *nonbasis);
+
+/* Solves the LPs which[0..nwhich) (which == NULL: all, in index order); res[k] belongs to
+ * which[k].  res is filled, result for result and bit for bit, as
+ *   dzg_batch_solve_fast_from(lps', start', nwhich, &opts, pivots_per_launch, refactor_every, res)
+ * fills it, where lps'[k] is LP which[k] in slack-basis form with its current data (basis and
+ * nonbasis those of create, x[p] the current right-hand side of the row whose slack sits at
+ * position p, z the array handed to create until c is first updated and -c[nonbasis[k]] after) and
+ * start'[k] = last_{which[k]}; the log is capped at min(res[k].log_cap, log_cap).  That covers
+ * numerics_used, AUTO's STRICT second attempt from the same start, a singular start ending
+ * DZG_SINGULAR with 0 iterations and the basis as it was, refactors and margins; STRICT numerics
+ * is dzg_batch_solve_from's result.  Afterwards last_i is updated for the LPs listed; the LPs not
+ * listed are not touched: their state on the device, their pending updates and last_i stay.
+ * DZG_E_ARG, nothing changed: res == NULL, an index out of range or listed twice, nwhich < 0. */
+int dzg_batch_resolve(dzg_batch *b, const int64_t *which, int64_t nwhich, dzg_result *res);
+
+/* Test and measurement hook: bytes[0] / bytes[1] = host-to-device / device-to-host bytes of the
+ * handle's last dzg_batch_resolve (every copy it enqueued, staged updates included);
+ * ms[0] = device time between two events around its stage + restart launches. */
+int dzg_debug_batch_traffic(const dzg_batch *b, int64_t bytes[2], double ms[1]);
+
 /* ---- Mixed-integer models: branch and bound over batched node LPs (csrc/mip.cpp, k_mip.hip) -- */
 
 /* Search knobs.  dzg_mip_opts_default() fills the defaults; in a zeroed struct the counts mean
