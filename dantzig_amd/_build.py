@@ -36,7 +36,7 @@ def _newest(paths) -> float:
 def _deps():
     hdrs = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "k_price_kernels.h"), os.path.join(CSRC, "price_small.h"),
             os.path.join(CSRC, "fast_decide.h"), os.path.join(CSRC, "fast_rows.h"),
-            os.path.join(CSRC, "chain_barrier.h"), os.path.join(CSRC, "batch_strict.h"),
+            os.path.join(CSRC, "chain_barrier.h"), os.path.join(CSRC, "batch_strict.h"), os.path.join(CSRC, "batch_fast.h"),
             os.path.join(CSRC, "batch_host.h"), os.path.join(CSRC, "batch_restart.h"), os.path.join(CSRC, "batch_steps.h"),
             os.path.join(CSRC, "mip_internal.h"), os.path.join(CSRC, "duals.h"), os.path.join(CSRC, "ranging.h"), os.path.join(CSRC, "rays.h"),
             os.path.join(CSRC, "opts.h"),

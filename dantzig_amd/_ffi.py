@@ -56,6 +56,8 @@ EXPORTS = [
     "dzg_batch_solve_fast_from", "dzg_debug_batch_fast_restart_ms",
     "dzg_batch_create", "dzg_batch_destroy", "dzg_batch_update", "dzg_batch_set_start",
     "dzg_batch_resolve", "dzg_debug_batch_traffic",
+    "dzg_mip_solve_nodes", "dzg_mip_last_fast_stats", "dzg_mip_node_opts_default",
+    "dzg_debug_mip_fast_node",
 ]
 
 BATCH_MAX_ROWS = 128  # DZG_BATCH_MAX_ROWS
@@ -208,6 +210,21 @@ class MipWarmStats(C.Structure):
                 ("warm_iterations", C.c_int64), ("restart_iterations", C.c_int64)]
 
 
+class MipNodeOpts(C.Structure):
+    _fields_ = [("numerics", C.c_int32), ("reserved", C.c_int32), ("pivots_per_launch", C.c_int64),
+                ("refactor_every", C.c_int64), ("route", C.c_void_p), ("route_cap", C.c_int64)]
+
+
+class MipFastStats(C.Structure):
+    _fields_ = [("nodes_fast", C.c_int64), ("nodes_rejected", C.c_int64),
+                ("fast_iterations", C.c_int64), ("strict_iterations", C.c_int64)]
+
+
+class MipDebugNode(C.Structure):
+    _fields_ = [("status", C.c_int32), ("route", C.c_int32), ("iterations", C.c_int64),
+                ("fast_iterations", C.c_int64), ("objective", C.c_double)]
+
+
 class MipNode(C.Structure):
     _fields_ = [("id", C.c_int64), ("parent", C.c_int64), ("branch_var", C.c_int64),
                 ("direction", C.c_int32), ("status", C.c_int32), ("bound", C.c_double),
@@ -350,6 +367,12 @@ def lib() -> C.CDLL:
         _lib.dzg_mip_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_mip_last_warm_stats.restype = None
         _lib.dzg_mip_last_warm_stats.argtypes = [C.c_void_p]
+        _lib.dzg_mip_node_opts_default.restype = None
+        _lib.dzg_mip_node_opts_default.argtypes = [C.c_void_p]
+        _lib.dzg_mip_solve_nodes.argtypes = [C.c_void_p] * 6
+        _lib.dzg_mip_last_fast_stats.restype = None
+        _lib.dzg_mip_last_fast_stats.argtypes = [C.c_void_p]
+        _lib.dzg_debug_mip_fast_node.argtypes = [C.c_void_p] * 6 + [C.c_int64, C.c_int64] + [C.c_void_p] * 7
         _lib.dzg_solver_upload_columns.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p,
                                                    C.c_int64]
     return _lib
@@ -476,6 +499,28 @@ def default_mip_opts(**kw) -> MipOpts:
             raise TypeError(f"unknown MIP option {k!r}")
         setattr(o, k, int(v) if k == "warm_start" else v)
     return o
+
+
+def default_mip_node_opts(**kw) -> MipNodeOpts:
+    """dzg_mip_node_opts (dzg_mip_solve_nodes): numerics takes STRICT / FAST or "strict" / "fast"."""
+    o = MipNodeOpts()
+    lib().dzg_mip_node_opts_default(C.byref(o))
+    for k, v in kw.items():
+        if k == "reserved" or not hasattr(o, k):
+            raise TypeError(f"unknown MIP node option {k!r}")
+        if k == "numerics" and isinstance(v, str):
+            if v not in ("strict", "fast"):
+                raise ValueError(f"node numerics must be 'strict' or 'fast', not {v!r}")
+            v = FAST if v == "fast" else STRICT
+        setattr(o, k, v)
+    return o
+
+
+def mip_last_fast_stats() -> MipFastStats:
+    """What the FAST node attempts did in this thread's last search (zeros after any other)."""
+    out = MipFastStats()
+    lib().dzg_mip_last_fast_stats(C.byref(out))
+    return out
 
 
 def mip_last_warm_stats() -> MipWarmStats:

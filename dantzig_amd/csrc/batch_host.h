@@ -387,10 +387,13 @@ inline int download(Device &D, const Layout &L, unsigned char *host)
 // appends the entries that are still running to next_list through atomicAdd(next_count, 1).
 // cur / nxt: two device lists laid out by `seg`; counts: kBuckets device ints; live: entries per bucket.
 // rounds (optional): counts the readbacks, kBuckets ints each.
+// tail (optional): kBuckets more device ints lie directly behind `counts`; they are never reset here
+// and come down with every readback, into tail[0..kBuckets).
 template <class Launch>
 int run_rounds(int *cur, int *nxt, int *counts, const Segments &seg, std::array<int, kBuckets> live,
-               hipStream_t st, Launch launch, int *rounds = nullptr)
+               hipStream_t st, Launch launch, int *rounds = nullptr, int *tail = nullptr)
 {
+    int back[2 * kBuckets];
     for (;;) {
         bool any = false;
         DZG_HIP(hipMemsetAsync(counts, 0, sizeof(int) * kBuckets, st));
@@ -401,8 +404,10 @@ int run_rounds(int *cur, int *nxt, int *counts, const Segments &seg, std::array<
             DZG_HIP(hipGetLastError());
         }
         if (!any) return 0;
-        DZG_HIP(hipMemcpyAsync(live.data(), counts, sizeof(int) * kBuckets, hipMemcpyDeviceToHost, st));
+        DZG_HIP(hipMemcpyAsync(back, counts, sizeof(int) * kBuckets * (tail ? 2 : 1), hipMemcpyDeviceToHost, st));
         DZG_HIP(hipStreamSynchronize(st));
+        std::copy(back, back + kBuckets, live.begin());
+        if (tail) std::copy(back + kBuckets, back + 2 * kBuckets, tail);
         if (rounds) ++*rounds;
         std::swap(cur, nxt);
     }

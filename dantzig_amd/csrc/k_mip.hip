@@ -25,14 +25,26 @@
 //     every carried x and z >= -DZG_MIP_WARM_TOL; otherwise the workgroup marks the node restarted
 //     and re-queues it, and its next slice initialises it cold.  k_mip_save copies the final state
 //     of the nodes the host branches on from the round arena into their slots.
+//   * FAST node LPs (dzg_mip_node_opts.numerics, DESIGN.md 7c "FAST node LPs").  k_mip_node_fast
+//     runs batch_fast.h's iteration, k_batch_fast's, on a control block of the node's own: cold
+//     from the slack basis, or warm from the parent's basis and nonbasis with the restart state of
+//     DESIGN.md 7l (W = B^-1, x = W rhs, y = W^T c_B, z = -dz - c_N; the slot's z is not used), the
+//     first launch pivoting on that same W.  An attempt that ends OPTIMAL is certified from its
+//     final basis: W is rebuilt, x and z are recomputed by the restart formulas and written over
+//     the carried ones, and the node stands only if all of them are >= -DZG_MIP_WARM_TOL.  Every
+//     other end puts the node on the strict list, which k_mip_node then solves cold in the same
+//     round.  Both kernels end in one epilogue (node_epilogue).
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
+#include "batch_fast.h"
 #include "batch_host.h"
+#include "batch_steps.h"
 #include "batch_strict.h"
 #include "common.h"
+#include "fast_decide.h"
 #include "mip_internal.h"
 
 using dzg_internal::MipNodeRecord;
@@ -84,6 +96,55 @@ struct MArgs {
 };
 
 constexpr int kWarmRestarted = 2; // MipNodeRecord::warm
+constexpr int kFastAccepted = 1, kFastRejected = 2; // MipNodeRecord::fast
+
+// Row r's right-hand side of node `id` (mip_internal.h, MipStructure)
+__device__ __forceinline__ double node_rhs(const double *b0, const int *ri, const double *bnd, int r)
+{
+    const int code = ri[r];
+    return code < 0 ? b0[r] : ((code & 1) ? bnd[code] : -bnd[code]);
+}
+
+// What follows an OPTIMAL node LP, from its final basis and x in global memory: the user values, the
+// objective, the integrality test and the branching choice into rec.  s_mem: m ints of LDS that
+// nothing else needs any more.  Every thread calls it; thread 0's rec is the one that counts.
+template <int BLOCK>
+__device__ __forceinline__ void node_epilogue(const MArgs &g, const SDesc &D, int id, int m, const int *basis,
+                                              const double *x, double *s_mem, MipNodeRecord &rec)
+{
+    const double *c = g.dpool + D.c_off;
+    const int *pv = g.ipool + D.pv_off, *nv = pv + g.nvars;
+    double *vals = g.values + (long long)id * g.nvars;
+    int *sb = (int *)s_mem; // the final basis, m entries
+    __syncthreads();
+    for (int p = threadIdx.x; p < m; p += BLOCK) sb[p] = basis[p];
+    __syncthreads();
+    // Simplex::solution (model.cpp solution_values): x+ - x-, 0.0 for a nonbasic part
+    for (int u = threadIdx.x; u < g.nvars; u += BLOCK) {
+        double val = 0.0;
+        const int jp = pv[u], jn = nv[u];
+        if (jp >= 0) {
+            double pos = 0.0, neg = 0.0;
+            for (int p = 0; p < m; ++p) {
+                if (sb[p] == jp) pos = x[p];
+                if (sb[p] == jn) neg = x[p];
+            }
+            val = pos - neg;
+        }
+        vals[u] = val;
+    }
+    __syncthreads(); // vals is read by thread 0 below
+    if (threadIdx.x == 0) {
+        double sum = 0.0; // objective_value, src/simplex.rs:345-352, basis-position order
+        for (int p = 0; p < m; ++p) {
+            const double prod = c[sb[p]] * x[p];
+            sum = sum + prod;
+        }
+        rec.objective = D.constant + sum;
+        dzg_internal::mip_branch_choice(vals, g.int_vars, g.nint, g.int_tol, &rec.branch, &rec.value,
+                                        &rec.integral);
+    }
+}
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restrict__ list,
@@ -210,41 +271,167 @@ __global__ __launch_bounds__(BLOCK) void k_mip_node(MArgs g, const int *__restri
     rec.objective = 0.0;
     rec.value = 0.0;
     rec.integral = 0;
-    if (status == DZG_OPTIMAL) {
-        const double *c = g.dpool + D.c_off;
-        const int *pv = g.ipool + D.pv_off, *nv = pv + g.nvars;
-        double *vals = g.values + (long long)id * g.nvars;
-        int *sb = (int *)s_mem; // the final basis, m entries (W is free after the loop)
-        __syncthreads();
-        for (int p = threadIdx.x; p < m; p += BLOCK) sb[p] = S.basis[p];
-        __syncthreads();
-        // Simplex::solution (model.cpp solution_values): x+ - x-, 0.0 for a nonbasic part
-        for (int u = threadIdx.x; u < g.nvars; u += BLOCK) {
-            double val = 0.0;
-            const int jp = pv[u], jn = nv[u];
-            if (jp >= 0) {
-                double pos = 0.0, neg = 0.0;
-                for (int p = 0; p < m; ++p) {
-                    if (sb[p] == jp) pos = S.x[p];
-                    if (sb[p] == jn) neg = S.x[p];
-                }
-                val = pos - neg;
-            }
-            vals[u] = val;
+    rec.fast = 0;
+    rec.fast_iterations = 0;
+    if (status == DZG_OPTIMAL) node_epilogue<BLOCK>(g, D, id, m, S.basis, S.x, s_mem, rec); // W is free after the loop
+    if (threadIdx.x == 0) {
+        // a node that k_mip_node_fast gave up on: its mark stays, its pivots are added
+        rec.fast = g.rec[id].fast;
+        rec.fast_iterations = g.rec[id].fast_iterations;
+        rec.iterations = rec.iterations + rec.fast_iterations;
+        g.rec[id] = rec;
+        g.status[id] = status;
+        g.iter[id] = it;
+    }
+}
+
+// What k_mip_node_fast needs beside MArgs.
+struct FNode {
+    dzg_bf::FState *state;      // one block per node of the round, written on the node's first slice
+    const dzg_bf::FState *tmpl; // the block every node starts from (the host's start_ctl)
+    NDesc *nd;                  // the round's descriptors again: a rejected node gives up its parent slot
+    int ppl, refactor_every;    // FAST pivots per launch; pivots between two inversions inside one
+};
+
+// One node LP in FAST numerics (the header of this file).  LDS is k_batch_fast's
+// carve-up, fast_lds_bytes(mmax).  A node that is still running goes to next_list as in k_mip_node; a
+// node whose attempt is discarded goes to strict_list with rec.fast = kFastRejected, iter = -1 and no
+// parent slot, so that k_mip_node solves it cold.  Every sum's order depends on m alone.
+template <int BLOCK, int PL>
+__global__ __launch_bounds__(BLOCK) void k_mip_node_fast(MArgs g, FNode f, const int *__restrict__ list,
+                                                         int *__restrict__ next_list,
+                                                         int *__restrict__ next_count,
+                                                         int *__restrict__ strict_list,
+                                                         int *__restrict__ strict_count)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_mem[];
+    const int id = list[blockIdx.x];
+    const NDesc N = g.nd[id];
+    const SDesc D = g.sd[N.sid];
+    const int m = D.m, q = D.n - D.m;
+    dzg_bf::FastLp P;
+    P.A = g.dpool + D.a_off;
+    P.var_col = g.ipool + D.vc_off;
+    P.basis = g.basis + N.m_off;
+    P.nonbasis = g.nonbasis + N.q_off;
+    P.x = g.x + N.m_off;
+    P.xbar = g.xbar + N.m_off;
+    P.z = g.z + N.q_off;
+    P.zbar = g.zbar + N.q_off;
+    P.dz = g.dz + N.q_off;
+    P.m = m;
+    P.q = q;
+    P.log_kind = P.log_enter = P.log_leave = nullptr;
+    P.log_mu = P.log_margin = nullptr;
+    P.log_off = P.log_cap = 0;
+    const dzg_bf::FastLds S = dzg_bf::carve(s_mem, g.mmax, m);
+    DzgCtl *sc = S.sc;
+    int *s_flag = S.s_flag; // [0], [1]: build_inverse's; [2]: a non-finite x or z; [3]: a failed sign check
+    const double *b0 = g.dpool + D.b0_off, *bnd = g.bnd + (long long)id * 2 * g.nint;
+    const double *c = g.dpool + D.c_off;
+    const int *ri = g.ipool + D.ri_off;
+    const auto rhs = [b0, ri, bnd](int r) { return node_rhs(b0, ri, bnd, r); };
+    dzg_bf::FState *gs = f.state + id;
+    const bool lead = threadIdx.x == 0;
+    const bool first = g.iter[id] < 0, warm = N.pslot >= 0;
+
+    const dzg_bf::FState *src = first ? f.tmpl : gs;
+    for (int i = threadIdx.x; i < (int)(sizeof(DzgCtl) / sizeof(int)); i += BLOCK)
+        ((int *)sc)[i] = ((const int *)&src->ctl)[i];
+    double max_err_life = src->max_err_life;
+    long long refactors = src->refactors;
+    if (lead) s_flag[2] = s_flag[3] = 0;
+    __syncthreads();
+
+    int status = DZG_RUNNING;
+    bool w_built = false;
+    if (first && warm) { // the parent's final basis and nonbasis; the restart state of that basis
+        const int *pi = g.pool_i + N.pslot * g.pool_si;
+        for (int r = threadIdx.x; r < m; r += BLOCK) P.basis[r] = pi[r];
+        for (int k = threadIdx.x; k < q; k += BLOCK) P.nonbasis[k] = pi[m + k];
+        __syncthreads(); // the inversion reads the basis
+        int inverted = 0;
+        const int bad = m > 0 ? dzg_bf::build_inverse<BLOCK, PL>(S.W, S.ld, m, P.A, P.var_col, P.basis, S.acol,
+                                                                 S.piv, s_flag, inverted)
+                              : 0;
+        refactors += inverted;
+        if (!bad) dzg_bf::restart_state<BLOCK, PL>(P, S, c, rhs);
+        if (bad || s_flag[2]) {
+            status = DZG_SINGULAR;
+            if (lead) sc->status = DZG_SINGULAR;
+            __syncthreads();
         }
-        __syncthreads(); // vals is read by thread 0 below
-        if (threadIdx.x == 0) {
-            double sum = 0.0; // objective_value, src/simplex.rs:345-352, basis-position order
-            for (int p = 0; p < m; ++p) {
-                const double prod = c[sb[p]] * S.x[p];
-                sum = sum + prod;
-            }
-            rec.objective = D.constant + sum;
-            dzg_internal::mip_branch_choice(vals, g.int_vars, g.nint, g.int_tol, &rec.branch,
-                                            &rec.value, &rec.integral);
+        w_built = true; // the first launch pivots on this W
+    } else if (first) { // k_mip_node's cold state (model.cpp build(), Simplex::new)
+        const int *bs = g.ipool + D.bs_off, *nb = g.ipool + D.nb_off;
+        const double *z0 = g.dpool + D.z0_off;
+        for (int r = threadIdx.x; r < m; r += BLOCK) {
+            P.x[r] = rhs(r);
+            P.xbar[r] = 1.0;
+            P.basis[r] = bs[r];
+        }
+        for (int k = threadIdx.x; k < q; k += BLOCK) {
+            P.nonbasis[k] = nb[k];
+            P.z[k] = z0[k];
+            P.zbar[k] = 1.0;
+        }
+        __syncthreads();
+    }
+    if (status == DZG_RUNNING)
+        status = dzg_bf::fast_steps<BLOCK, PL>(P, S, g.eps, f.ppl, f.refactor_every, w_built, max_err_life,
+                                               refactors);
+    const long long it = sc->iter; // every path here has passed a barrier since the last write
+    if (status == DZG_RUNNING) {
+        for (int i = threadIdx.x; i < (int)(sizeof(DzgCtl) / sizeof(int)); i += BLOCK)
+            ((int *)&gs->ctl)[i] = ((const int *)sc)[i];
+        if (lead) {
+            gs->max_err_life = max_err_life;
+            gs->refactors = refactors;
+            g.iter[id] = it;
+            next_list[atomicAdd(next_count, 1)] = id;
+        }
+        return;
+    }
+    // ---- the certificate: x and z of the final basis, recomputed; their signs, bars ignored, NaN fails
+    int accept = 0;
+    if (status == DZG_OPTIMAL) {
+        int inverted = 0;
+        const int bad = m > 0 ? dzg_bf::build_inverse<BLOCK, PL>(S.W, S.ld, m, P.A, P.var_col, P.basis, S.acol,
+                                                                 S.piv, s_flag, inverted)
+                              : 0;
+        if (!bad) {
+            dzg_bf::restart_state<BLOCK, PL>(P, S, c, rhs);
+            int neg = 0;
+            for (int p = threadIdx.x; p < m; p += BLOCK) neg |= !(P.x[p] >= -DZG_MIP_WARM_TOL);
+            for (int k = threadIdx.x; k < q; k += BLOCK) neg |= !(P.z[k] >= -DZG_MIP_WARM_TOL);
+            if (neg) s_flag[3] = 1; // every writer stores the same value
+            __syncthreads();
+            accept = !s_flag[2] && !s_flag[3];
         }
     }
-    if (threadIdx.x == 0) {
+    if (!accept) {
+        if (lead) {
+            g.rec[id].fast = kFastRejected;
+            g.rec[id].fast_iterations = it;
+            g.iter[id] = -1;
+            f.nd[id].pslot = -1;
+            strict_list[atomicAdd(strict_count, 1)] = id;
+        }
+        return;
+    }
+    MipNodeRecord rec;
+    rec.status = status;
+    rec.iterations = it;
+    rec.warm = warm ? 1 : 0;
+    rec.warm_iterations = warm ? it : 0;
+    rec.branch = -1;
+    rec.objective = 0.0;
+    rec.value = 0.0;
+    rec.integral = 0;
+    rec.fast = kFastAccepted;
+    rec.fast_iterations = it;
+    node_epilogue<BLOCK>(g, D, id, m, P.basis, P.x, s_mem, rec); // W is spent
+    if (lead) {
         g.rec[id] = rec;
         g.status[id] = status;
         g.iter[id] = it;
@@ -279,6 +466,36 @@ void launch_bucket(int b, const MArgs &g, const int *list, int n, int *next_list
             hipLaunchKernelGGL(k_mip_node<BLOCK>, dim3(grid), dim3(BLOCK), lds, st, g, list + c0, next_list,
                                next_count);
         });
+    });
+}
+
+// The FAST attempts list[0..n) of row bucket b: k_batch_fast's instantiations and LDS.
+void launch_bucket_fast(int b, const MArgs &g, const FNode &f, const int *list, int n, int *next_list,
+                        int *next_count, int *strict_list, int *strict_count, hipStream_t st)
+{
+    const size_t lds = dzg_bf::fast_lds_bytes(g.mmax);
+    if (b == 3) { // more than 64 KiB of dynamic LDS: say so once (a runtime that needs no telling ignores it)
+        static const hipError_t attr =
+            hipFuncSetAttribute(reinterpret_cast<const void *>(k_mip_node_fast<256, 64>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)dzg_bf::fast_lds_bytes(DZG_BATCH_MAX_ROWS));
+        (void)attr;
+    }
+    bh::for_each_chunk(b, n, [&](int c0, int grid) {
+        const dim3 block(bh::kBlock[b]);
+        // the pricing lanes per column follow the bucket's rows: 16, 32, then the whole wave
+        if (b == 0)
+            hipLaunchKernelGGL((k_mip_node_fast<64, 16>), dim3(grid), block, lds, st, g, f, list + c0, next_list,
+                               next_count, strict_list, strict_count);
+        else if (b == 1)
+            hipLaunchKernelGGL((k_mip_node_fast<64, 32>), dim3(grid), block, lds, st, g, f, list + c0, next_list,
+                               next_count, strict_list, strict_count);
+        else if (b == 2)
+            hipLaunchKernelGGL((k_mip_node_fast<128, 64>), dim3(grid), block, lds, st, g, f, list + c0, next_list,
+                               next_count, strict_list, strict_count);
+        else
+            hipLaunchKernelGGL((k_mip_node_fast<256, 64>), dim3(grid), block, lds, st, g, f, list + c0, next_list,
+                               next_count, strict_list, strict_count);
     });
 }
 
@@ -471,9 +688,48 @@ int mip_gpu_save_states(MipGpu *g, const int *pairs, int count)
     return 0;
 }
 
+int mip_gpu_plant_slot(MipGpu *g, int sid, const int *basis, const int *nonbasis)
+{
+    const MipStructure &s = g->structs[(size_t)sid];
+    const int slot = mip_gpu_slot_alloc(g, sid);
+    if (slot < 0) return dzg_set_error(DZG_E_ARG, "mip: this structure cannot use the parent-state pool");
+    DZG_HIP(hipSetDevice(g->device));
+    const long long si = DZG_BATCH_MAX_ROWS + g->pool_q, sz = g->pool_q > 0 ? g->pool_q : 1;
+    if (slot >= g->pool_cap) {
+        if (g->pool_cap > 0) return dzg_set_error(DZG_E_ARG, "mip: planted slots come before saved ones");
+        const int cap = 64;
+        DZG_HIP(hipMalloc((void **)&g->pool_i, sizeof(int) * si * cap));
+        DZG_HIP(hipMalloc((void **)&g->pool_z, sizeof(double) * sz * cap));
+        DZG_HIP(hipMemsetAsync(g->pool_z, 0, sizeof(double) * sz * cap, g->st));
+        g->pool_cap = cap;
+    }
+    DZG_HIP(hipMemcpyAsync(g->pool_i + slot * si, basis, sizeof(int) * s.m, hipMemcpyHostToDevice, g->st));
+    DZG_HIP(hipMemcpyAsync(g->pool_i + slot * si + s.m, nonbasis, sizeof(int) * (s.n - s.m), hipMemcpyHostToDevice,
+                           g->st));
+    DZG_HIP(hipStreamSynchronize(g->st)); // the arrays are the caller's
+    return slot;
+}
+
+int mip_gpu_read_state(MipGpu *g, int idx, int sid, int *basis, int *nonbasis, double *x, double *z)
+{
+    if (idx < 0 || idx >= g->last_count) return dzg_set_error(DZG_E_ARG, "mip: round index out of range");
+    DZG_HIP(hipSetDevice(g->device));
+    const MipStructure &s = g->structs[(size_t)sid];
+    NDesc N;
+    DZG_HIP(hipMemcpyAsync(&N, g->last.nd + idx, sizeof(NDesc), hipMemcpyDeviceToHost, g->st));
+    DZG_HIP(hipStreamSynchronize(g->st));
+    DZG_HIP(hipMemcpyAsync(basis, g->last.basis + N.m_off, sizeof(int) * s.m, hipMemcpyDeviceToHost, g->st));
+    DZG_HIP(hipMemcpyAsync(nonbasis, g->last.nonbasis + N.q_off, sizeof(int) * (s.n - s.m), hipMemcpyDeviceToHost,
+                           g->st));
+    DZG_HIP(hipMemcpyAsync(x, g->last.x + N.m_off, sizeof(double) * s.m, hipMemcpyDeviceToHost, g->st));
+    DZG_HIP(hipMemcpyAsync(z, g->last.z + N.q_off, sizeof(double) * (s.n - s.m), hipMemcpyDeviceToHost, g->st));
+    DZG_HIP(hipStreamSynchronize(g->st));
+    return 0;
+}
+
 int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const double *bnd, int count,
                         long long max_iter, double eps, int ppl, double int_tol, MipNodeRecord *rec,
-                        double *values)
+                        double *values, const MipFastRun *fast)
 {
     if (count <= 0) return 0;
     DZG_HIP(hipSetDevice(g->device));
@@ -504,15 +760,19 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
     bh::Arena ar;
     // uploaded: descriptors, bounds, the first list; then device-only state and results
     const size_t o_nd = ar.add(sizeof(NDesc) * count), o_bnd = ar.add(sizeof(double) * (nb2 + 1)),
-                 o_list = ar.add(sizeof(int) * count);
+                 o_list = ar.add(sizeof(int) * count),
+                 o_tmpl = ar.add(fast ? sizeof(dzg_bf::FState) : 0); // FAST: the block every node starts from
     const size_t upload_end = ar.top;
     const size_t o_iter = ar.add(sizeof(long long) * count), o_rec = ar.add(sizeof(MipNodeRecord) * count),
                  o_status = ar.add(sizeof(int) * count), o_list2 = ar.add(sizeof(int) * count),
-                 o_counts = ar.add(sizeof(int) * kBuckets), o_basis = ar.add(sizeof(int) * (nm + 1)),
+                 // the running counters, then (FAST) the strict list's, read back together
+                 o_counts = ar.add(sizeof(int) * 2 * kBuckets), o_basis = ar.add(sizeof(int) * (nm + 1)),
                  o_nonbasis = ar.add(sizeof(int) * (nq + 1)), o_x = ar.add(sizeof(double) * (nm + 1)),
                  o_xbar = ar.add(sizeof(double) * (nm + 1)), o_z = ar.add(sizeof(double) * (nq + 1)),
                  o_zbar = ar.add(sizeof(double) * (nq + 1)), o_dz = ar.add(sizeof(double) * (nq + 1)),
-                 o_vals = ar.add(sizeof(double) * ((size_t)count * g->nvars + 1));
+                 o_vals = ar.add(sizeof(double) * ((size_t)count * g->nvars + 1)),
+                 o_fstate = ar.add(fast ? sizeof(dzg_bf::FState) * count : 0),
+                 o_slist = ar.add(fast ? sizeof(int) * count : 0); // FAST: the rejected nodes, by bucket
     if (const size_t top = ar.top; top > g->rcap) { // one allocation, grown by half again so that few rounds reallocate
         if (g->rdev) {
             DZG_HIP(hipStreamSynchronize(g->st));
@@ -527,6 +787,7 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
     std::vector<unsigned char> host(upload_end, 0);
     std::memcpy(host.data() + o_nd, nd.data(), sizeof(NDesc) * count);
     if (nb2) std::memcpy(host.data() + o_bnd, bnd, sizeof(double) * nb2);
+    if (fast) dzg_steps::fast_state_init(host.data() + o_tmpl, *fast->opts, max_iter);
     const bh::Segments seg = bh::segments(bucket_n);
     {
         int *list = (int *)(host.data() + o_list);
@@ -564,14 +825,39 @@ int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const doubl
     g->last = a;
     g->last_count = count;
 
-    const int rc = bh::run_rounds((int *)(dev + o_list), (int *)(dev + o_list2), (int *)(dev + o_counts), seg,
-                                  bh::live_of(bucket_n), st,
-                                  [&](int b, const int *list, int n, int *next_list, int *next_count) {
-                                      MArgs ab = a;
-                                      ab.mmax = mmax[b];
-                                      launch_bucket(b, ab, list, n, next_list, next_count, st);
-                                  });
-    if (rc) return rc;
+    const auto strict_launch = [&](int b, const int *list, int n, int *next_list, int *next_count) {
+        MArgs ab = a;
+        ab.mmax = mmax[b];
+        launch_bucket(b, ab, list, n, next_list, next_count, st);
+    };
+    int *const list1 = (int *)(dev + o_list), *const list2 = (int *)(dev + o_list2);
+    int *const counts = (int *)(dev + o_counts);
+    if (!fast) {
+        const int rc = bh::run_rounds(list1, list2, counts, seg, bh::live_of(bucket_n), st, strict_launch);
+        if (rc) return rc;
+    } else {
+        // FAST slices until the lists drain; the rejected nodes collect in slist, whose counters come
+        // down with every round's.  Then k_mip_node on that list, cold (both round lists are free).
+        FNode f;
+        f.state = (dzg_bf::FState *)(dev + o_fstate);
+        f.tmpl = (const dzg_bf::FState *)(dev + o_tmpl);
+        f.nd = (NDesc *)(dev + o_nd);
+        f.ppl = dzg_steps::fast_ppl(fast->pivots_per_launch);
+        f.refactor_every = dzg_steps::fast_refactor_every(fast->refactor_every);
+        int *const slist = (int *)(dev + o_slist);
+        DZG_HIP(hipMemsetAsync(counts + kBuckets, 0, sizeof(int) * kBuckets, st));
+        std::array<int, kBuckets> rejected{};
+        const int rc = bh::run_rounds(list1, list2, counts, seg, bh::live_of(bucket_n), st,
+                                      [&](int b, const int *list, int n, int *next_list, int *next_count) {
+                                          MArgs ab = a;
+                                          ab.mmax = mmax[b];
+                                          launch_bucket_fast(b, ab, f, list, n, next_list, next_count,
+                                                             slist + seg[(size_t)b], counts + kBuckets + b, st);
+                                      }, nullptr, rejected.data());
+        if (rc) return rc;
+        const int rc2 = bh::run_rounds(slist, list1, counts, seg, rejected, st, strict_launch);
+        if (rc2) return rc2;
+    }
     DZG_HIP(hipMemcpyAsync(rec, dev + o_rec, sizeof(MipNodeRecord) * count, hipMemcpyDeviceToHost, st));
     DZG_HIP(hipStreamSynchronize(st));
     if (g->nvars > 0)

@@ -19,6 +19,11 @@
 // k_mip.hip starts it from there, restarting it cold if the attempt is not accepted.  A slot is
 // taken back once every child that names it is solved or pruned, so the pool never holds more
 // slots than there are open nodes.
+//
+// FAST node LPs (opt-in, dzg_mip_solve_nodes with node_opts.numerics = FAST): every GPU node gets an
+// attempt in FAST numerics first (k_mip_node_fast), warm from its parent's slot or cold; the attempts
+// that are not certified are solved by the STRICT kernel in the same round.  The search itself does
+// not change; a node's record says which way it went, and dzg_mip_last_fast_stats counts.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -90,7 +95,39 @@ struct NodeModel {
 
 bool bad_tol(double t) { return !(t >= 0.0); } // NaN or negative
 
+// The structure k_mip.hip keeps of a built node model; ints: the integer variables in index order.
+MipStructure make_structure(const Built &b, int nvars, const std::vector<int> &ints)
+{
+    const int nint = (int)ints.size();
+    std::vector<int> k_of((size_t)(nvars ? nvars : 1), -1);
+    for (int k = 0; k < nint; ++k) k_of[(size_t)ints[(size_t)k]] = k;
+    MipStructure s;
+    s.m = (int)b.m;
+    s.n = (int)b.n;
+    s.ns = (int)b.ns;
+    s.constant = b.constant;
+    s.a = b.a;
+    s.b0 = b.x;
+    s.c = b.c;
+    s.z0 = b.z;
+    s.var_col.assign(b.var_col.begin(), b.var_col.end());
+    s.basis0.assign(b.basis.begin(), b.basis.end());
+    s.nonbasis0.assign(b.nonbasis.begin(), b.nonbasis.end());
+    s.pos_var.assign(b.pos_var.begin(), b.pos_var.end());
+    s.neg_var.assign(b.neg_var.begin(), b.neg_var.end());
+    s.row_int.assign((size_t)b.m, -1);
+    for (int64_t r = 0; r < b.m; ++r) {
+        const int64_t tag = b.row_tag[(size_t)r];
+        if (tag < 0) continue;
+        const int k = k_of[(size_t)(tag / 2)];
+        if (k < 0) continue;                       // a continuous variable's bound row
+        s.row_int[(size_t)r] = (tag & 1) ? 2 * k : 2 * k + 1; // lb row -> lb_k, ub row -> ub_k
+    }
+    return s;
+}
+
 thread_local dzg_mip_warm_stats g_warm_stats = {0, 0, 0, 0};
+thread_local dzg_mip_fast_stats g_fast_stats = {0, 0, 0, 0};
 
 } // namespace
 
@@ -108,10 +145,37 @@ extern "C" void dzg_mip_last_warm_stats(dzg_mip_warm_stats *out)
     if (out) *out = g_warm_stats;
 }
 
+extern "C" void dzg_mip_node_opts_default(dzg_mip_node_opts *no)
+{
+    if (no) std::memset(no, 0, sizeof(*no)); // STRICT, the FAST batch's defaults, no route array
+}
+
+extern "C" void dzg_mip_last_fast_stats(dzg_mip_fast_stats *out)
+{
+    if (out) *out = g_fast_stats;
+}
+
 extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
                              const dzg_mip_opts *mip_opts, dzg_mip_result *res)
 {
+    return dzg_mip_solve_nodes(model, is_integer, opts, mip_opts, nullptr, res);
+}
+
+extern "C" int dzg_mip_solve_nodes(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
+                                   const dzg_mip_opts *mip_opts, const dzg_mip_node_opts *node_opts,
+                                   dzg_mip_result *res)
+{
     g_warm_stats = dzg_mip_warm_stats{0, 0, 0, 0};
+    g_fast_stats = dzg_mip_fast_stats{0, 0, 0, 0};
+    dzg_mip_node_opts no;
+    if (node_opts) no = *node_opts; else dzg_mip_node_opts_default(&no);
+    if (no.numerics != DZG_NUMERICS_STRICT && no.numerics != DZG_NUMERICS_FAST)
+        return dzg_set_error(DZG_E_ARG, "mip: node_opts.numerics must be STRICT or FAST");
+    if (no.pivots_per_launch < 0) return dzg_set_error(DZG_E_ARG, "mip: node_opts.pivots_per_launch < 0");
+    if (no.refactor_every < 0) return dzg_set_error(DZG_E_ARG, "mip: node_opts.refactor_every < 0");
+    if (no.route_cap < 0 || (no.route_cap > 0 && !no.route))
+        return dzg_set_error(DZG_E_ARG, "mip: node_opts.route_cap > 0 needs a route buffer (and must not be < 0)");
+    const bool fast_on = no.numerics == DZG_NUMERICS_FAST;
     // ---- argument checks, before any device work
     if (!model || !res) return dzg_set_error(DZG_E_ARG, "mip: model or res is NULL");
     if (model->nvars > 0 && !is_integer) return dzg_set_error(DZG_E_ARG, "mip: is_integer is NULL");
@@ -180,33 +244,8 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
         StructInfo info;
         info.m = b.m;
         const bool strict = dzg_opts_numerics(o, b.m) == DZG_NUMERICS_STRICT;
-        if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS) {
-            std::vector<int> k_of((size_t)(nvars ? nvars : 1), -1);
-            for (int k = 0; k < nint; ++k) k_of[(size_t)ints[(size_t)k]] = k;
-            MipStructure s;
-            s.m = (int)b.m;
-            s.n = (int)b.n;
-            s.ns = (int)b.ns;
-            s.constant = b.constant;
-            s.a = b.a;
-            s.b0 = b.x;
-            s.c = b.c;
-            s.z0 = b.z;
-            s.var_col.assign(b.var_col.begin(), b.var_col.end());
-            s.basis0.assign(b.basis.begin(), b.basis.end());
-            s.nonbasis0.assign(b.nonbasis.begin(), b.nonbasis.end());
-            s.pos_var.assign(b.pos_var.begin(), b.pos_var.end());
-            s.neg_var.assign(b.neg_var.begin(), b.neg_var.end());
-            s.row_int.assign((size_t)b.m, -1);
-            for (int64_t r = 0; r < b.m; ++r) {
-                const int64_t tag = b.row_tag[(size_t)r];
-                if (tag < 0) continue;
-                const int k = k_of[(size_t)(tag / 2)];
-                if (k < 0) continue;                       // a continuous variable's bound row
-                s.row_int[(size_t)r] = (tag & 1) ? 2 * k : 2 * k + 1; // lb row -> lb_k, ub row -> ub_k
-            }
-            info.gpu_id = mip_gpu_add_structure(gpu, std::move(s));
-        }
+        if (strict && !b.sparse && b.m <= DZG_BATCH_MAX_ROWS)
+            info.gpu_id = mip_gpu_add_structure(gpu, make_structure(b, nvars, ints));
         structs.emplace(mask, info);
         return info;
     };
@@ -313,9 +352,10 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
             const int g = (int)gpu_idx.size();
             std::vector<MipNodeRecord> grec((size_t)g);
             std::vector<double> gvals((size_t)g * nvars + 1, 0.0);
+            const MipFastRun fr{&o, no.pivots_per_launch, no.refactor_every};
             const int rc = mip_gpu_solve_round(gpu, sid.data(), warm_on ? pslot.data() : nullptr,
                                                bnd.data(), g, max_iter, eps, ppl, mo.int_tol,
-                                               grec.data(), gvals.data());
+                                               grec.data(), gvals.data(), fast_on ? &fr : nullptr);
             if (rc < 0) return rc;
             for (int j = 0; j < g; ++j) {
                 const int i = gpu_idx[(size_t)j];
@@ -340,7 +380,17 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
                     g_warm_stats.restart_iterations += r.iterations - r.warm_iterations;
                 }
             }
+            if (r.fast) {
+                g_fast_stats.nodes_fast++;
+                g_fast_stats.fast_iterations += r.fast_iterations;
+                if (r.fast == 2) {
+                    g_fast_stats.nodes_rejected++;
+                    g_fast_stats.strict_iterations += r.iterations - r.fast_iterations;
+                }
+            }
             if (res->log_count < res->log_cap) {
+                if (res->log_count < no.route_cap)
+                    no.route[res->log_count] = round_slot[(size_t)i] >= 0 ? r.fast : 3;
                 const Node &nd = nodes[(size_t)id];
                 dzg_mip_node &e = res->log[res->log_count++];
                 e.id = id;
@@ -441,4 +491,79 @@ extern "C" int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, 
         for (const OpenKey &key : open) bb = std::max(bb, key.bound);
     res->best_bound = bb;
     return final_status;
+}
+
+// Test hook: one node LP through a FAST round (include/dantzig_amd.h).
+extern "C" int dzg_debug_mip_fast_node(const dzg_model *model, const int32_t *is_integer, const double *bnd,
+                                       const int32_t *start_basis, const dzg_opts *opts,
+                                       const dzg_mip_node_opts *node_opts, int64_t cap_m, int64_t cap_q,
+                                       int32_t *basis, int32_t *nonbasis, double *x, double *z, int64_t *m_out,
+                                       int64_t *q_out, dzg_mip_debug_node *out)
+{
+    if (!model || !out || !m_out || !q_out || !basis || !nonbasis || !x || !z)
+        return dzg_set_error(DZG_E_ARG, "mip: dzg_debug_mip_fast_node: a NULL argument");
+    if (model->nvars > 0 && !is_integer) return dzg_set_error(DZG_E_ARG, "mip: is_integer is NULL");
+    if (!valid(model)) return dzg_set_error(DZG_E_ARG, "mip: the model is malformed");
+    dzg_opts o;
+    if (opts) o = *opts; else dzg_opts_default(&o);
+    if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_AUTO)
+        return dzg_set_error(DZG_E_ARG, "mip: FAST numerics is not supported for node LPs");
+    dzg_mip_node_opts no;
+    if (node_opts) no = *node_opts; else dzg_mip_node_opts_default(&no);
+    if (no.pivots_per_launch < 0 || no.refactor_every < 0)
+        return dzg_set_error(DZG_E_ARG, "mip: node_opts: a negative count");
+    const int nvars = (int)model->nvars;
+    std::vector<int> ints;
+    for (int u = 0; u < nvars; ++u)
+        if (is_integer[u]) ints.push_back(u);
+    if (!ints.empty() && !bnd) return dzg_set_error(DZG_E_ARG, "mip: bnd is NULL");
+    const std::vector<double> nb(bnd, bnd + 2 * ints.size());
+    NodeModel nm(model, ints, nb);
+    Built b;
+    build(&nm.md, b, true);
+    if (b.sparse || b.m > DZG_BATCH_MAX_ROWS || dzg_opts_numerics(o, b.m) != DZG_NUMERICS_STRICT)
+        return dzg_set_error(DZG_E_ARG, "mip: this node LP is not one k_mip.hip batches");
+    *m_out = b.m;
+    *q_out = b.n - b.m;
+    if (cap_m < b.m || cap_q < b.n - b.m) return dzg_set_error(DZG_E_ARG, "mip: cap_m or cap_q too small");
+    MipGpu *gpu = nullptr;
+    struct Guard {
+        MipGpu **g;
+        ~Guard() { mip_gpu_destroy(*g); }
+    } guard{&gpu};
+    if (const int rc = mip_gpu_create(&gpu, o.device, nvars, ints); rc < 0) return rc;
+    const int sid = mip_gpu_add_structure(gpu, make_structure(b, nvars, ints));
+    int pslot = -1;
+    if (start_basis) {
+        std::vector<char> in((size_t)b.n, 0);
+        std::vector<int> sb((size_t)b.m), sn;
+        for (int64_t p = 0; p < b.m; ++p) {
+            if (start_basis[p] < 0 || start_basis[p] >= b.n)
+                return dzg_set_error(DZG_E_ARG, "mip: start_basis names a variable out of range");
+            sb[(size_t)p] = start_basis[p];
+            in[(size_t)start_basis[p]] = 1;
+        }
+        for (int64_t j = 0; j < b.n && (int64_t)sn.size() < b.n - b.m; ++j)
+            if (!in[(size_t)j]) sn.push_back((int)j);
+        sn.resize((size_t)(b.n - b.m), 0);
+        pslot = mip_gpu_plant_slot(gpu, sid, sb.data(), sn.data());
+        if (pslot < 0) return pslot;
+    }
+    const MipFastRun fr{&o, no.pivots_per_launch, no.refactor_every};
+    MipNodeRecord rec{};
+    std::vector<double> vals((size_t)nvars + 1, 0.0);
+    const int rc = mip_gpu_solve_round(gpu, &sid, start_basis ? &pslot : nullptr, nb.data(), 1,
+                                       dzg_opts_resolved(&o).max_iter, dzg_opts_resolved(&o).epsilon, 16, 1e-6, &rec,
+                                       vals.data(), &fr);
+    if (rc < 0) return rc;
+    std::vector<int> fb((size_t)b.m + 1), fn((size_t)(b.n - b.m) + 1);
+    if (const int rc2 = mip_gpu_read_state(gpu, 0, sid, fb.data(), fn.data(), x, z); rc2 < 0) return rc2;
+    std::copy(fb.begin(), fb.begin() + b.m, basis);
+    std::copy(fn.begin(), fn.begin() + (b.n - b.m), nonbasis);
+    out->status = rec.status;
+    out->route = rec.fast;
+    out->iterations = rec.iterations;
+    out->fast_iterations = rec.fast_iterations;
+    out->objective = rec.objective;
+    return 0;
 }

@@ -54,6 +54,16 @@ struct MipNodeRecord {
     int integral;
     int warm;                  // 0: cold; 1: warm attempt accepted; 2: rejected and restarted cold
     long long warm_iterations; // the warm attempt's pivots (iterations holds both runs' sum)
+    int fast;                  // 0: STRICT only; 1: FAST attempt accepted; 2: FAST rejected, then STRICT
+    long long fast_iterations; // the FAST attempt's pivots (iterations holds both runs' sum)
+};
+
+// FAST node LPs (dzg_mip_node_opts): the options the control block starts from (tie_tol,
+// near_tie_action), pivots per FAST launch and pivots between two inversions inside a launch
+// (0: the FAST batch's defaults).
+struct MipFastRun {
+    const dzg_opts *opts;
+    int64_t pivots_per_launch, refactor_every;
 };
 
 struct MipGpu; // device arenas, reused across rounds
@@ -66,9 +76,17 @@ int mip_gpu_add_structure(MipGpu *g, MipStructure &&s);
 // pslot (NULL: every node cold): node i's parent-state slot, -1 for a cold node; a node with a
 // slot is warm-started from it and restarted cold if the attempt is not accepted.
 // rec[i] is filled for every node; values[i * nvars ...] for the integral OPTIMAL ones only.
+// fast (NULL: STRICT only): every node gets a FAST attempt first -- warm from its slot's basis and
+// nonbasis, else cold -- and the attempts that are not accepted are then solved by the STRICT kernel,
+// cold, in the same call.
 int mip_gpu_solve_round(MipGpu *g, const int *sid, const int *pslot, const double *bnd, int count,
                         long long max_iter, double eps, int ppl, double int_tol, MipNodeRecord *rec,
-                        double *values);
+                        double *values, const MipFastRun *fast);
+// Test hooks (dzg_debug_mip_fast_node): a slot that holds a given basis and nonbasis of structure sid
+// (returns the slot; before any save_states), and the final basis, nonbasis, x and z of node idx of
+// the last round.
+int mip_gpu_plant_slot(MipGpu *g, int sid, const int *basis, const int *nonbasis);
+int mip_gpu_read_state(MipGpu *g, int idx, int sid, int *basis, int *nonbasis, double *x, double *z);
 // The parent-state pool (warm starts).  A slot holds the final basis, nonbasis and z of one node of
 // structure sid; alloc returns -1 if that structure cannot use the pool.  Slots are handed out and
 // taken back on the host; save_states copies the final states of nodes of the last round into

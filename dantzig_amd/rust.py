@@ -48,10 +48,32 @@ def set_mip_options(**opts) -> None:
     """Branch-and-bound knobs for subsequent solve_mip() calls (fields of dzg_mip_opts: node_limit,
     nodes_per_round, pivots_per_launch, int_tol, abs_gap, rel_gap, and warm_start: True starts a
     child's node LP from its parent's final basis where the two share a standard form, see
-    dzg_mip_solve)."""
-    _ffi.default_mip_opts(**opts)  # validates names
+    dzg_mip_solve) and the node options of dzg_mip_solve_nodes: node_numerics="fast" solves the
+    batched node LPs in FAST numerics first, each result certified from its final basis and each
+    rejected attempt solved again in STRICT; fast_pivots_per_launch and refactor_every are that
+    kernel's knobs -- results depend on them in the last bits."""
+    search, node = _split_mip_options(opts)
+    _ffi.default_mip_opts(**search)  # validates names
+    _node_opts(node)
     _mip_options.clear()
     _mip_options.update(opts)
+
+
+_NODE_OPTION_NAMES = {"node_numerics": "numerics", "fast_pivots_per_launch": "pivots_per_launch",
+                      "refactor_every": "refactor_every"}
+
+
+def _split_mip_options(opts: dict):
+    """(fields of dzg_mip_opts, node options by their solve_mip() names)."""
+    node = {k: v for k, v in opts.items() if k in _NODE_OPTION_NAMES}
+    return {k: v for k, v in opts.items() if k not in _NODE_OPTION_NAMES}, node
+
+
+def _node_opts(node: dict):
+    """dzg_mip_node_opts of the node options, or None when none was passed."""
+    if not node:
+        return None
+    return _ffi.default_mip_node_opts(**{_NODE_OPTION_NAMES[k]: v for k, v in node.items()})
 
 
 def _opt_float(v, what: str):
@@ -160,10 +182,16 @@ class MipInfo:
     log, a list of dzg_mip_node tuples (id, parent, branch_var, direction, bound, status,
     iterations, objective) when solve_mip(..., node_log=N) asked for one.  nodes_warm counts the
     node LPs started from their parent's basis (warm_start=True), nodes_restarted those of them
-    that were discarded and solved again cold."""
+    that were discarded and solved again cold.  nodes_fast_accepted / nodes_fast_rejected count the
+    FAST node attempts that stood and those solved again in STRICT; both are None unless a node
+    option (node_numerics, fast_pivots_per_launch, refactor_every) was passed.  With
+    node_numerics="fast" nodes_warm counts only the warm attempts that FAST accepted and
+    nodes_restarted is 0: a warm node that FAST rejects is solved cold in STRICT and is counted in
+    nodes_fast_rejected instead."""
     __slots__ = ("status", "nodes", "rounds", "lp_iterations", "best_bound", "gap", "objective",
                  "nodes_batched", "nodes_sequential", "nodes_pruned", "nodes_dropped",
-                 "incumbent_node", "failed_node", "log", "nodes_warm", "nodes_restarted")
+                 "incumbent_node", "failed_node", "log", "nodes_warm", "nodes_restarted",
+                 "nodes_fast_accepted", "nodes_fast_rejected")
 
     def __init__(self, **kw):
         for k in self.__slots__:
@@ -513,14 +541,20 @@ def _mip_call(arrays: dict, is_integer, node_log: int = 0, **mip_opts):
         res.log = C.cast(log, C.c_void_p)
         res.log_cap = int(node_log)
     opts = _ffi.default_opts(**_options)
-    mo = _ffi.default_mip_opts(**{**_mip_options, **mip_opts})
+    search, node = _split_mip_options({**_mip_options, **mip_opts})
+    mo = _ffi.default_mip_opts(**search)
+    no = _node_opts(node)
     md = _c_model(arrays)
-    rc = _ffi.lib().dzg_mip_solve(C.byref(md), _ffi.ptr(is_int), C.byref(opts), C.byref(mo),
-                                  C.byref(res))
+    rc = _ffi.lib().dzg_mip_solve_nodes(C.byref(md), _ffi.ptr(is_int), C.byref(opts), C.byref(mo),
+                                        C.byref(no) if no is not None else None, C.byref(res))
     _ffi.check(rc, "dzg_mip_solve")
     stats = _ffi.mip_last_warm_stats()
     res.warm_stats = (int(stats.nodes_warm), int(stats.nodes_restarted), int(stats.warm_iterations),
                       int(stats.restart_iterations))
+    res.fast_stats = None  # not asked for
+    if no is not None:
+        fs = _ffi.mip_last_fast_stats()
+        res.fast_stats = (int(fs.nodes_fast) - int(fs.nodes_rejected), int(fs.nodes_rejected))
     entries = [(e.id, e.parent, e.branch_var, e.direction, e.bound, e.status, e.iterations,
                 e.objective) for e in log[:res.log_count]]
     return res, values, entries
@@ -536,7 +570,9 @@ def _mip_outcome(res, values, order, entries, where: str = "", stacklevel: int =
                    nodes_batched=int(res.nodes_batched), nodes_sequential=int(res.nodes_sequential),
                    nodes_pruned=int(res.nodes_pruned), nodes_dropped=int(res.nodes_dropped),
                    incumbent_node=int(res.incumbent_node), failed_node=int(res.failed_node),
-                   log=entries, nodes_warm=res.warm_stats[0], nodes_restarted=res.warm_stats[1])
+                   log=entries, nodes_warm=res.warm_stats[0], nodes_restarted=res.warm_stats[1],
+                   nodes_fast_accepted=res.fast_stats[0] if res.fast_stats else None,
+                   nodes_fast_rejected=res.fast_stats[1] if res.fast_stats else None)
     if rc == _ffi.INFEASIBLE:
         return InfeasibleError("The model is infeasible (no integral point)" + where)
     if rc == _ffi.UNBOUNDED and res.failed_node == 0:

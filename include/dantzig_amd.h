@@ -977,6 +977,79 @@ int dzg_mip_solve(const dzg_model *model, const int32_t *is_integer, const dzg_o
                   const dzg_mip_opts *mip_opts, dzg_mip_result *res);
 void dzg_mip_last_warm_stats(dzg_mip_warm_stats *out);
 
+/* ---- FAST node LPs (opt-in; DESIGN.md 7c "FAST node LPs") ------------------------------------
+ * dzg_mip_solve_nodes is dzg_mip_solve with node options; dzg_mip_solve(...) is
+ * dzg_mip_solve_nodes(..., NULL, ...), and NULL or numerics = DZG_NUMERICS_STRICT change nothing,
+ * bit for bit.  With numerics = DZG_NUMERICS_FAST every node that k_mip.hip would batch (<= 128 dense
+ * rows under the STRICT rule) gets an attempt in FAST numerics first, the loop of dzg_batch_solve_fast
+ * on a control block of the node's own; opts->tie_tol and opts->near_tie_action apply as given
+ * (default COUNT), opts->numerics keeps its meaning (STRICT or AUTO; FAST stays DZG_E_ARG).
+ *   start    a node that warm_start would start warm (warm_start = 1, a parent solved by k_mip.hip,
+ *            the same set of finite integer bounds) starts from the parent's final basis and nonbasis
+ *            with the FAST restart state of dzg_batch_solve_fast_from (W = B^-1, x = W rhs,
+ *            y = W^T c_B, z = -dz - c_N, both perturbation vectors at one; the parent's z is not
+ *            used), and its first launch pivots on that W.  Every other node starts from the slack basis.
+ *   accept   an attempt that ends DZG_OPTIMAL is certified from its final basis: the inverse is
+ *            rebuilt, x and z are recomputed by the same formulas and replace the carried ones, and
+ *            the node stands only if every one of them is >= -DZG_MIP_WARM_TOL (NaN fails).  An
+ *            accepted node is primal and dual feasible at one basis of its own LP; objective,
+ *            values, integrality and the branching choice come from the recomputed x.
+ *   reject   every other end (INFEASIBLE, UNBOUNDED, NEAR_TIE, SINGULAR, PANIC, ITER_LIMIT, a failed
+ *            sign check) discards the attempt: the node is solved in the same round by the STRICT
+ *            kernel from the slack basis, and its status, objective, values and branching are then
+ *            bit for bit dzg_model_solve's of the node model.  Its logged iterations are the pivots
+ *            of both runs.  A root that FAST ends UNBOUNDED is thus confirmed by STRICT first.
+ * Nodes on the sequential route (dzg_model_solve) are untouched.  The optimum is the cold search's;
+ * the tree may differ, as with warm_start.  The search is deterministic for a given nodes_per_round,
+ * pivots_per_launch and refactor_every of this struct -- and NOT independent of the last two: the
+ * FAST kernel rebuilds the inverse at the start of every launch and every refactor_every pivots, so
+ * they move last bits and, through ties, possibly the tree.  With FAST, dzg_mip_last_warm_stats counts
+ * the accepted warm attempts only (nodes_restarted = 0); rejected attempts are in dzg_mip_fast_stats. */
+typedef struct {
+    int32_t numerics;          /* DZG_NUMERICS_STRICT (0-filled default) or DZG_NUMERICS_FAST */
+    int32_t reserved;
+    int64_t pivots_per_launch; /* FAST node launches; 0 = 128, the FAST batch's default */
+    int64_t refactor_every;    /* 0 = 64, the FAST batch's default */
+    int32_t *route;            /* optional, caller-owned, parallel to res->log: 0 STRICT batched,
+                                  1 FAST accepted, 2 FAST rejected then STRICT, 3 sequential */
+    int64_t route_cap;
+} dzg_mip_node_opts;
+void dzg_mip_node_opts_default(dzg_mip_node_opts *no);
+/* numerics other than STRICT or FAST, negative counts, route_cap < 0 (or > 0 without route):
+ * DZG_E_ARG with a "mip:" text, before any device work. */
+int dzg_mip_solve_nodes(const dzg_model *model, const int32_t *is_integer, const dzg_opts *opts,
+                        const dzg_mip_opts *mip_opts, const dzg_mip_node_opts *node_opts,
+                        dzg_mip_result *res);
+/* What the FAST attempts did in the calling thread's last search (zeros after any other search,
+ * a failed call included). */
+typedef struct {
+    int64_t nodes_fast;        /* node LPs that got a FAST attempt                       */
+    int64_t nodes_rejected;    /* of those, the attempts discarded and solved in STRICT  */
+    int64_t fast_iterations;   /* pivots of the FAST attempts, kept or discarded         */
+    int64_t strict_iterations; /* pivots of the STRICT runs of the rejected nodes        */
+} dzg_mip_fast_stats;
+void dzg_mip_last_fast_stats(dzg_mip_fast_stats *out);
+
+/* Test hook (tests/test_gpu_mip_fast.py): one node LP of `model` through the FAST node kernel, as a
+ * round of dzg_mip_solve_nodes with numerics = FAST solves it.  bnd: lb, ub per integer variable in
+ * index order (+-inf: none).  start_basis (m variables of the standard form, or NULL for a cold
+ * node): the basis a warm node would take from its parent; the nonbasis is every other variable in
+ * ascending order.  cap_m / cap_q size basis, x / nonbasis, z, which receive the node's final state
+ * (the STRICT run's if the attempt was rejected); *m_out and *q_out the sizes.  The attempt is always
+ * FAST: node_opts->numerics is not consulted, only pivots_per_launch and refactor_every are.  The
+ * STRICT run of a rejected attempt uses the defaults of dzg_mip_opts (pivots_per_launch 16) and the
+ * epilogue int_tol = 1e-6; opts->epsilon, tie_tol and near_tie_action apply as in the search. */
+typedef struct {
+    int32_t status, route;     /* route: 1 FAST accepted, 2 FAST rejected then STRICT */
+    int64_t iterations, fast_iterations;
+    double objective;
+} dzg_mip_debug_node;
+int dzg_debug_mip_fast_node(const dzg_model *model, const int32_t *is_integer, const double *bnd,
+                            const int32_t *start_basis, const dzg_opts *opts,
+                            const dzg_mip_node_opts *node_opts, int64_t cap_m, int64_t cap_q,
+                            int32_t *basis, int32_t *nonbasis, double *x, double *z, int64_t *m_out,
+                            int64_t *q_out, dzg_mip_debug_node *out);
+
 /* Host-only: the standard-form builder alone (Simplex::new, src/simplex.rs:123-224).
  * Two-call protocol: first call with out->a == NULL fills m, n, n_struct and lda;
  * the caller allocates a[lda*n_struct], var_col[n], c[n], basis[m], nonbasis[n-m],

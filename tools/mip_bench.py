@@ -24,6 +24,14 @@ says whether the warm GPU search equals it bit for bit (status, nodes, rounds, p
 values, warm counters).  One JSON line per model to profiles/mip_bench_warm.jsonl.
 
     python tools/mip_bench.py --warm [--models 4] [--node-limit 5000] [--repeats 3]
+
+--fast measures the FAST node LPs (dzg_mip_solve_nodes, numerics = FAST): per model three modes
+alternate in one process `--repeats` times after a warm-up of each -- cold STRICT, warm STRICT and
+warm FAST -- and each reports its minimum, its spread (max - min), nodes, rounds and pivots; warm
+FAST also its accepted and rejected attempts.  The baseline is the 16-thread warm oracle of --warm.
+One JSON line per model to profiles/mip_bench_fast.jsonl.
+
+    python tools/mip_bench.py --fast [--models 4] [--node-limit 5000] [--repeats 3]
 """
 from __future__ import annotations
 
@@ -123,6 +131,45 @@ def warm_line(family, seed, md, flags, mo, repeats, pool):
     return line
 
 
+FAST_MODES = (("cold_strict", {}), ("warm_strict", {"warm_start": 1}),
+              ("warm_fast", {"warm_start": 1, "node_numerics": "fast"}))
+
+
+def fast_line(family, seed, md, flags, mo, repeats, pool):
+    """Cold STRICT, warm STRICT and warm FAST node LPs, alternating in one process."""
+    arrays = mr.c_arrays(md)
+    for _, kw in FAST_MODES:  # warm-up: device, code objects, allocator
+        rs._mip_call(arrays, flags, 0, **kw, **mo)
+    times = {name: [] for name, _ in FAST_MODES}
+    got = {}
+    for _ in range(repeats):
+        for name, kw in FAST_MODES:
+            t0 = time.perf_counter()
+            got[name] = rs._mip_call(arrays, flags, 0, **kw, **mo)[0]
+            times[name].append(time.perf_counter() - t0)
+    line = dict(family=family, seed=seed, nvars=len(flags), rows=len(md["constraints"]) + 2 * len(flags),
+                repeats=repeats)
+    for name, _ in FAST_MODES:
+        res, ts = got[name], times[name]
+        line[name] = dict(status=int(res.status), objective=res.objective if res.has_incumbent else None,
+                          nodes=int(res.nodes_solved), rounds=int(res.rounds), lp_pivots=int(res.lp_iterations),
+                          gpu_s=min(ts), spread_s=max(ts) - min(ts))
+    fast = got["warm_fast"].fast_stats
+    line["warm_fast"].update(accepted=fast[0], rejected=fast[1])
+    lp_s = [0.0]
+
+    def timed_map(fn, items):
+        t = time.perf_counter()
+        out = list(pool.map(fn, items))
+        lp_s[0] += time.perf_counter() - t
+        return out
+
+    mw.branch_and_bound_warm(md, flags, map_fn=timed_map, **mo)
+    line.update(oracle16_warm_lp_s=lp_s[0],
+                **{f"speedup_{name}": lp_s[0] / line[name]["gpu_s"] for name, _ in FAST_MODES})
+    return line
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--models", type=int, default=4)
@@ -130,19 +177,21 @@ def main() -> None:
     ap.add_argument("--nodes-per-round", type=int, default=1024)
     ap.add_argument("--no-oracle", action="store_true")
     ap.add_argument("--warm", action="store_true", help="cold vs warm-started GPU search, see above")
+    ap.add_argument("--fast", action="store_true", help="cold STRICT, warm STRICT and warm FAST node LPs")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "mip_bench_warm.jsonl" if args.warm else "mip_bench.jsonl")
+        name = "mip_bench_fast.jsonl" if args.fast else "mip_bench_warm.jsonl" if args.warm else "mip_bench.jsonl"
+        args.out = os.path.join(ROOT, "profiles", name)
     pool = ThreadPoolExecutor(max_workers=16)
     lines = []
     for family, maker in (("knap", knapsack), ("gap", gap)):
         for k in range(args.models):
             md, flags = maker(1000 + k)
             mo = dict(node_limit=args.node_limit, nodes_per_round=args.nodes_per_round)
-            if args.warm:
-                line = warm_line(family, 1000 + k, md, flags, mo, args.repeats, pool)
+            if args.warm or args.fast:
+                line = (fast_line if args.fast else warm_line)(family, 1000 + k, md, flags, mo, args.repeats, pool)
                 print(json.dumps(line), flush=True)
                 lines.append(line)
                 continue
