@@ -16,7 +16,7 @@ CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libdantzig_amd.so")
 ARCH = "gfx950"
-SOURCES = ["engine.hip", "k_vector.hip", "k_price.hip", "k_strict.hip", "k_fast.hip", "k_chain.hip", "k_sparse.hip", "k_refactor.hip", "k_rowshard.hip", "k_drift.hip", "k_restart.hip", "k_extend.hip", "k_remove.hip", "k_batch.hip", "k_batch_fast.hip",
+SOURCES = ["engine.hip", "k_vector.hip", "k_price.hip", "k_strict.hip", "k_fast.hip", "k_chain.hip", "k_sparse.hip", "k_refactor.hip", "k_rowshard.hip", "k_drift.hip", "k_restart.hip", "k_extend.hip", "k_remove.hip", "k_batch.hip", "k_batch_fast.hip", "k_batch_post.hip",
            "k_batch_restart.hip", "k_batch_resident.hip", "k_mip.hip", "k_duals.hip", "k_ranging.hip", "k_rays.hip", "model.cpp", "mip.cpp", "lpgen.cpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wall",
          "-Wno-unused-result", "-Wno-unused-value"]

@@ -54,6 +54,7 @@ EXPORTS = [
     "dzg_solver_remove",
     "dzg_batch_solve_from", "dzg_debug_batch_restart_ms",
     "dzg_batch_solve_fast_from", "dzg_debug_batch_fast_restart_ms",
+    "dzg_batch_solve_post", "dzg_debug_batch_post_ms", "dzg_batch_resolve_post",
     "dzg_batch_create", "dzg_batch_destroy", "dzg_batch_update", "dzg_batch_set_start",
     "dzg_batch_resolve", "dzg_debug_batch_traffic",
     "dzg_mip_solve_nodes", "dzg_mip_last_fast_stats", "dzg_mip_node_opts_default",
@@ -169,6 +170,10 @@ class Reopt(C.Structure):
 
 class BatchStart(C.Structure):
     _fields_ = [("basis", C.c_void_p), ("nonbasis", C.c_void_p)]
+
+
+class BatchPost(C.Structure):
+    _fields_ = [("du", C.c_void_p), ("req", C.c_void_p), ("rg", C.c_void_p), ("ry", C.c_void_p)]
 
 
 class BatchChange(C.Structure):
@@ -350,6 +355,10 @@ def lib() -> C.CDLL:
                                                    C.c_int64, C.c_void_p]
         _lib.dzg_debug_batch_fast_restart_ms.restype = C.c_double
         _lib.dzg_debug_batch_fast_restart_ms.argtypes = []
+        _lib.dzg_batch_solve_post.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                              C.c_int64, C.c_void_p, C.c_void_p]
+        _lib.dzg_debug_batch_post_ms.restype = C.c_double
+        _lib.dzg_debug_batch_post_ms.argtypes = []
         _lib.dzg_batch_create.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int64,
                                           C.c_void_p]
         _lib.dzg_batch_destroy.restype = None
@@ -357,6 +366,7 @@ def lib() -> C.CDLL:
         _lib.dzg_batch_update.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
         _lib.dzg_batch_set_start.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.dzg_batch_resolve.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        _lib.dzg_batch_resolve_post.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
         _lib.dzg_debug_batch_traffic.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.dzg_debug_matrix.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64]
         _lib.dzg_debug_matrix_rows.restype = C.c_int64

@@ -895,7 +895,8 @@ def solve_batch(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: i
 
 
 def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_launch: int = 0,
-                     refactor_every: int = 0, start=None, **opts) -> list:
+                     refactor_every: int = 0, start=None, duals: bool = False, ranging=False,
+                     pivot_tol: float = 0.0, rays: bool = False, **opts) -> list:
     """dzg_batch_solve_fast: every LP of `lps` in FAST numerics, one workgroup per LP with the
     explicit basis inverse in LDS, in one call.
 
@@ -914,7 +915,15 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
     inverse a launch builds, xbar = zbar = 1) and is pivoted on from there; iterations and pivots
     count from 0, refactors includes the restart's inversion.  A singular start basis ends
     "singular" with 0 iterations in FAST; under AUTO the STRICT batch solves it, and every other LP
-    FAST gave up on, from the same start."""
+    FAST gave up on, from the same start.
+
+    duals, ranging, pivot_tol, rays (dzg_batch_solve_post; all compose with each other and with
+    start): what solve_batch's keywords of the same names ask for, from the state each LP ended in.
+    ranging is True (every unit direction) or one (cost_dirs, rhs_dirs) per LP.  Results gain
+    `.duals`, `.ranging` and `.ray` as solve_batch sets them, None where none was computed.  A FAST
+    result's come from the inverse of its final basis, built as the batch builds it; a STRICT
+    result's (numerics=STRICT, or an LP AUTO handed over) are solve_batch's own.  Without these
+    keywords the call is exactly what it was."""
     lps = list(lps)
     allowed = {"numerics", "near_tie_action", "tie_tol", "max_iter", "epsilon", "device"}
     unknown = set(opts) - allowed
@@ -925,6 +934,24 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
     if int(pivots_per_launch) < 0 or int(refactor_every) < 0:
         raise ValueError("solve_batch_fast: pivots_per_launch and refactor_every are >= 0")
 
+    want_ranging = ranging is not False and ranging is not None
+    if not (0.0 <= float(pivot_tol)):
+        raise ValueError("solve_batch_fast: pivot_tol is >= 0 (0 selects 1e-9)")
+    if duals or want_ranging or rays:
+        starts = None if start is None else _batch_starts(lps, start)
+
+        def invoke_post(c_lps, count, o, res, c_post):
+            c_start = None
+            if starts is not None:
+                c_start = (_ffi.BatchStart * max(count, 1))()
+                for i, s in enumerate(starts):
+                    if s is not None:
+                        c_start[i].basis, c_start[i].nonbasis = ptr(s[0]), ptr(s[1])
+            return _ffi.lib().dzg_batch_solve_post(c_lps, c_start, C.c_int64(count), C.byref(o),
+                                                   C.c_int64(int(pivots_per_launch)),
+                                                   C.c_int64(int(refactor_every)), C.byref(c_post), res)
+        return _batch_fast(lps, log, log_cap, opts, "dzg_batch_solve_post", invoke_post,
+                           post=(bool(duals), ranging if want_ranging else None, float(pivot_tol), bool(rays)))
     if start is None:
         def invoke(c_lps, count, o, res):
             return _ffi.lib().dzg_batch_solve_fast(c_lps, C.c_int64(count), C.byref(o),
@@ -944,9 +971,59 @@ def solve_batch_fast(lps, log: bool = True, log_cap: int = 4096, pivots_per_laun
     return _batch_fast(lps, log, log_cap, opts, "dzg_batch_solve_fast_from", invoke_from)
 
 
-def _batch_fast(lps, log, log_cap, opts, name, invoke) -> list:
+class _PostBuffers:
+    """The dzg_batch_post of one call over `lps` and the arrays it points at; attach(i, result)
+    sets result i's .duals / .ranging / .ray as solve_batch does."""
+
+    def __init__(self, lps, duals: bool, ranging, pivot_tol: float, rays: bool):
+        count = len(lps)
+        self.mo = np.concatenate([[0], np.cumsum([lp.m for lp in lps])]).astype(np.int64)
+        self.no = np.concatenate([[0], np.cumsum([lp.n for lp in lps])]).astype(np.int64)
+        self.c_post = _ffi.BatchPost()
+        self.bufs = self.du = self.ry = None
+        if ranging is not None:
+            duals = True
+            reqs = [(None, None)] * count if ranging is True else list(ranging)
+            if len(reqs) != count:
+                raise ValueError("ranging: one (cost_dirs, rhs_dirs) request per LP")
+            self.bufs = [_ffi.RangingBuffers(_ranging_dirs(cd, lp.n), _ranging_dirs(rd, lp.m), pivot_tol)
+                         for (cd, rd), lp in zip(reqs, lps)]
+            self.c_req, self.c_rg = (_ffi.RangingReq * max(count, 1))(), (_ffi.Ranging * max(count, 1))()
+            for i, buf in enumerate(self.bufs):
+                buf.fill(self.c_req[i], self.c_rg[i])
+            self.c_post.req = C.addressof(self.c_req)
+            self.c_post.rg = C.addressof(self.c_rg)
+        if duals:
+            self.y_all, self.d_all = np.zeros(self.mo[-1] + 1), np.zeros(self.no[-1] + 1)
+            self.du = (_ffi.Duals * max(count, 1))()
+            for i in range(count):
+                self.du[i].y = self.y_all.ctypes.data + 8 * int(self.mo[i])
+                self.du[i].d = self.d_all.ctypes.data + 8 * int(self.no[i])
+            self.c_post.du = C.addressof(self.du)
+        if rays:
+            self.rd_all, self.ry_all = np.zeros(self.no[-1] + 1), np.zeros(self.mo[-1] + 1)
+            self.ry = (_ffi.Ray * max(count, 1))()
+            for i in range(count):
+                self.ry[i].d = self.rd_all.ctypes.data + 8 * int(self.no[i])
+                self.ry[i].y = self.ry_all.ctypes.data + 8 * int(self.mo[i])
+            self.c_post.ry = C.addressof(self.ry)
+
+    def attach(self, i: int, out) -> None:
+        a0, a1, v0, v1 = int(self.mo[i]), int(self.mo[i + 1]), int(self.no[i]), int(self.no[i + 1])
+        if self.du is not None:
+            out.duals = None if self.du[i].source == 0 else _core_duals(
+                self.du[i], self.y_all[a0:a1].copy(), self.d_all[v0:v1].copy())
+        if self.bufs is not None:
+            out.ranging = None if out.duals is None else _core_ranging(self.bufs[i], out.duals)
+        if self.ry is not None:
+            out.ray = None if self.ry[i].kind == 0 else _core_ray(
+                self.ry[i], self.rd_all[v0:v1].copy(), self.ry_all[a0:a1].copy())
+
+
+def _batch_fast(lps, log, log_cap, opts, name, invoke, post=None) -> list:
     """The Python-side checks, the marshalling and the results of a FAST batch entry point `name`;
-    invoke(c_lps, count, opts, res) makes the call and returns its code."""
+    invoke(c_lps, count, opts, res) makes the call and returns its code.  post = (duals, ranging,
+    pivot_tol, rays): invoke gets the dzg_batch_post as a fifth argument."""
     import time
 
     for i, lp in enumerate(lps):
@@ -979,8 +1056,9 @@ def _batch_fast(lps, log, log_cap, opts, name, invoke) -> list:
         r.margins = margins.ctypes.data + margins.strides[0] * i if cap > 0 else None
         r.log_cap = cap
     o = _ffi.default_opts(**opts)
+    pb = _PostBuffers(lps, *post) if post is not None else None
     t0 = time.perf_counter()
-    rc = invoke(c_lps, count, o, res)
+    rc = invoke(c_lps, count, o, res, pb.c_post) if pb else invoke(c_lps, count, o, res)
     wall_ms = (time.perf_counter() - t0) * 1e3
     _ffi.check(rc, name)
     out = []
@@ -998,6 +1076,8 @@ def _batch_fast(lps, log, log_cap, opts, name, invoke) -> list:
             basis=basis[a0:a1].copy(), nonbasis=nonbasis[b0:b1].copy(), x=x[a0:a1].copy(),
             xbar=xbar[a0:a1].copy(), z=z[b0:b1].copy(), zbar=zbar[b0:b1].copy(), pivots=pivots,
             solve_ms=wall_ms, margins=margins[i, :cnt].copy() if fast and log else None, **_counters(r)))
+        if pb:
+            pb.attach(i, out[-1])
     return out
 
 
@@ -1123,10 +1203,19 @@ class BatchSolver:
             raise ValueError(f"dzg_batch_set_start: {_ffi.lib().dzg_last_error().decode()}")
         _ffi.check(rc, "dzg_batch_set_start")
 
-    def solve(self, which=None, log: bool = True) -> list:
+    def solve(self, which=None, log: bool = True, duals: bool = False, ranging=False, pivot_tol: float = 0.0,
+              rays: bool = False) -> list:
         """Solve the LPs `which` lists (None: all, in index order); result k is LP which[k]'s
-        CoreResult, as solve_batch_fast reports it."""
+        CoreResult, as solve_batch_fast reports it.  duals, ranging (True, or one (cost_dirs, rhs_dirs)
+        per listed LP), pivot_tol and rays (dzg_batch_resolve_post) mean what they mean for
+        solve_batch_fast: results gain .duals, .ranging and .ray, None where none was computed.
+        Without them the call is dzg_batch_resolve, exactly as before."""
         import time
+        from types import SimpleNamespace
+
+        want_ranging = ranging is not False and ranging is not None
+        if not (0.0 <= float(pivot_tol)):
+            raise ValueError("BatchSolver.solve: pivot_tol is >= 0 (0 selects 1e-9)")
 
         h = self._handle()
         if which is None:
@@ -1157,8 +1246,16 @@ class BatchSolver:
             r.margins = margins.ctypes.data + margins.strides[0] * k if cap > 0 else None
             r.log_cap = cap
         c_which = i64(ids)
+        pb = None
+        if duals or want_ranging or rays:
+            pb = _PostBuffers([SimpleNamespace(m=self._shapes[i][0], n=self._shapes[i][1]) for i in ids], bool(duals),
+                              ranging if want_ranging else None, float(pivot_tol), bool(rays))
         t0 = time.perf_counter()
-        rc = _ffi.lib().dzg_batch_resolve(h, None if which is None else ptr(c_which), C.c_int64(count), res)
+        if pb is None:
+            rc = _ffi.lib().dzg_batch_resolve(h, None if which is None else ptr(c_which), C.c_int64(count), res)
+        else:
+            rc = _ffi.lib().dzg_batch_resolve_post(h, None if which is None else ptr(c_which), C.c_int64(count),
+                                                   C.byref(pb.c_post), res)
         wall_ms = (time.perf_counter() - t0) * 1e3
         if rc == _ffi.E_ARG:
             raise ValueError(f"dzg_batch_resolve: {_ffi.lib().dzg_last_error().decode()}")
@@ -1178,6 +1275,8 @@ class BatchSolver:
                 basis=basis[a0:a1].copy(), nonbasis=nonbasis[b0:b1].copy(), x=x[a0:a1].copy(),
                 xbar=xbar[a0:a1].copy(), z=z[b0:b1].copy(), zbar=zbar[b0:b1].copy(), pivots=pivots,
                 solve_ms=wall_ms, margins=margins[k, :cnt].copy() if fast and log else None, **_counters(r)))
+            if pb:
+                pb.attach(k, out[-1])
         return out
 
     def traffic(self) -> tuple[int, int, float]:

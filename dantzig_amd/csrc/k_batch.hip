@@ -668,4 +668,19 @@ extern "C" int dzg_batch_solve_from(const dzg_lp *lps, const dzg_batch_start *st
     return batch_solve(lps, count, opts, pivots_per_launch, res, ex, start);
 }
 
+int dzg_steps::strict_post(const dzg_lp *lps, const dzg_batch_start *start, int64_t count, const dzg_opts *opts,
+                           int64_t pivots_per_launch, dzg_result *res, dzg_duals *du, const dzg_ranging_req *req,
+                           dzg_ranging *rg, dzg_ray *ry)
+{
+    BatchExtras ex;
+    ex.ranging = req != nullptr;
+    ex.duals = du != nullptr || ex.ranging;
+    ex.rays = ry != nullptr;
+    ex.du = du;
+    ex.req = req;
+    ex.rg = rg;
+    ex.ry = ry;
+    return batch_solve(lps, count, opts, pivots_per_launch, res, ex, start);
+}
+
 extern "C" double dzg_debug_batch_restart_ms(void) { return t_restart_ms; }

@@ -5,7 +5,8 @@
 // what they mean in the single-LP FAST solver.  dzg_batch_solve_fast with AUTO numerics runs STOP and
 // hands every LP that ends DZG_NEAR_TIE, DZG_SINGULAR or DZG_PANIC to the STRICT batch (k_batch.hip).
 // dzg_batch_solve_fast_from starts the LPs that come with a basis from that basis: k_batch_fast_restart
-// (below) gives each of them its restart state before the first round.
+// (below) gives each of them its restart state before the first round.  dzg_batch_solve_post adds, behind
+// the rounds, the duals, ranges and rays of the states the LPs ended in (k_batch_post.hip).
 //
 //   layout      W[p * ld + r] = (B^-1)[basis position p][constraint row r], ld = m | 1.  BTRAN reads
 //               row p with lanes along r (contiguous); FTRAN gives every thread a row and walks the
@@ -49,6 +50,7 @@
 #include "common.h"
 #include "fast_decide.h"
 #include "opts.h"
+#include "ranging.h" // dzg_ranging_req_valid
 
 namespace {
 
@@ -399,7 +401,7 @@ long long dzg_steps::fast_state_iter(const void *block) { return ((const FState 
 // c (by variable) goes up behind the solve's sections, for those launches alone.
 static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int64_t count, const dzg_opts &o,
                             int64_t pivots_per_launch, int64_t refactor_every_arg, dzg_result *res,
-                            double *w_out = nullptr)
+                            double *w_out = nullptr, const dzg_batch_post *post = nullptr)
 {
     const bool dump = w_out != nullptr;
     const bool warm = bh::any_warm(start, (int)count);
@@ -420,6 +422,8 @@ static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int
     const size_t s_w = L.ar.add(dump ? sizeof(double) * (size_t)w_off[(size_t)N] : 0);
     L.end_download();
     const size_t s_c = L.ar.add(warm ? sizeof(double) * (size_t)P.nvc : 0);
+    dzg_steps::PostSections PSec; // the post-solve's sections, behind everything the solve has
+    if (post) dzg_steps::post_layout(L.ar, PSec, P.nvc, P.nm, P.nq, N);
 
     std::vector<unsigned char> host(L.download_end, 0);
     bh::fill_upload(host.data(), L, P, lps, start);
@@ -457,35 +461,69 @@ static int batch_solve_fast(const dzg_lp *lps, const dzg_batch_start *start, int
                                res[i]);
     }
     if (dump) std::memcpy(w_out, host.data() + s_w, sizeof(double) * (size_t)w_off[(size_t)N]);
-    return 0;
+    if (!post) return 0;
+    // ---- what the LPs can say about where they ended: c and the right-hand sides go up, then
+    // batch_steps.h's pass.  A warm LP's right-hand side goes by constraint row, as fill_upload sent
+    // it; a cold LP's starting x is taken as it is (dzg_duals: "the batch calls take the starting x")
+    std::vector<double> cr((size_t)(P.nvc + P.nm), 0.0);
+    for (int i = 0; i < N; ++i) {
+        const dzg_lp &lp = lps[i];
+        const DzgBatchLp &d = P.desc[(size_t)i];
+        std::copy(lp.c, lp.c + lp.n, cr.begin() + d.vc_off);
+        const bool by_row = start && start[i].basis;
+        for (int64_t k = 0; k < lp.m; ++k)
+            cr[(size_t)(P.nvc + d.m_off + (by_row ? -1 - bh::var_code(lp, lp.basis[k]) : k))] = lp.x[k];
+    }
+    DZG_HIP(hipMemcpyAsync(dev + PSec.c, cr.data(), sizeof(double) * (size_t)P.nvc, hipMemcpyHostToDevice, D.st));
+    DZG_HIP(hipMemcpyAsync(dev + PSec.rhs0, cr.data() + P.nvc, sizeof(double) * (size_t)P.nm, hipMemcpyHostToDevice,
+                           D.st));
+    dzg_steps::PostRun PR;
+    PR.dev = dev;
+    PR.L = &L;
+    PR.state = s_state;
+    PR.S = PSec;
+    PR.st = D.st;
+    double ms = 0.0;
+    const int rc_post = dzg_steps::post_pass(PR, false, P, N, nullptr, res, *post, nullptr, nullptr, &ms);
+    dzg_steps::post_ms() = ms;
+    return rc_post;
 }
 
-extern "C" int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
-                                         const dzg_opts *opts, int64_t pivots_per_launch,
-                                         int64_t refactor_every, dzg_result *res)
+// dzg_batch_solve_fast_from, and behind it what `post` (NULL or empty: nothing) asks for.
+static int solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count, const dzg_opts *opts,
+                           int64_t pivots_per_launch, int64_t refactor_every, const dzg_batch_post *post,
+                           dzg_result *res)
 {
     t_restart_ms = 0.0;
+    dzg_steps::post_ms() = 0.0;
+    if (post && !post->du && !post->req && !post->rg && !post->ry) post = nullptr;
     // ---- host checks first: malformed input is DZG_E_ARG on any machine
     if (const int rc = bh::check_batch(lps, count, res, pivots_per_launch)) return rc;
     if (refactor_every < 0) return dzg_set_error(DZG_E_ARG, "batch: refactor_every < 0");
+    if (count > 0 && post && (post->req != nullptr) != (post->rg != nullptr))
+        return dzg_set_error(DZG_E_ARG, "batch: req and rg go together (one of them is NULL)");
     dzg_opts o;
     if (opts) o = *opts; else dzg_opts_default(&o);
     if (o.numerics != DZG_NUMERICS_STRICT && o.numerics != DZG_NUMERICS_FAST && o.numerics != DZG_NUMERICS_AUTO)
         return dzg_set_error(DZG_E_ARG, "batch: opts.numerics");
-    if (o.numerics == DZG_NUMERICS_STRICT)
-        return dzg_batch_solve_from(lps, start, count, &o, pivots_per_launch, res, nullptr);
+    if (o.numerics == DZG_NUMERICS_STRICT) {
+        if (!post) return dzg_batch_solve_from(lps, start, count, &o, pivots_per_launch, res, nullptr);
+        return dzg_steps::strict_post(lps, start, count, &o, pivots_per_launch, res, post->du, post->req, post->rg,
+                                      post->ry);
+    }
     const int rc_lps = bh::check_batch(lps, count, [&](int64_t i, std::string &why) {
-        return !start || bh::start_valid(lps[i], start[i], why);
+        if (start && !bh::start_valid(lps[i], start[i], why)) return false;
+        return !post || !post->req || dzg_ranging_req_valid(&post->req[i], lps[i].m, lps[i].n, why);
     });
     if (rc_lps) return rc_lps;
     if (count == 0) return 0;
     const bool is_auto = o.numerics == DZG_NUMERICS_AUTO;
     if (is_auto) o.near_tie_action = DZG_NEAR_TIE_STOP;
-    const int rc = batch_solve_fast(lps, start, count, o, pivots_per_launch, refactor_every, res);
+    const int rc = batch_solve_fast(lps, start, count, o, pivots_per_launch, refactor_every, res, nullptr, post);
     if (rc < 0 || !is_auto) return rc;
     // ---- AUTO: only the reference's own arithmetic can arbitrate a tie -- the LPs FAST gave up on
     // are solved again by the STRICT batch, each from the start it had here (a cold one from its
-    // first pivot), into the same result slots
+    // first pivot), into the same result slots; their post-solve is the STRICT batch's too
     std::vector<int64_t> redo;
     for (int64_t i = 0; i < count; ++i)
         if (res[i].status == DZG_NEAR_TIE || res[i].status == DZG_SINGULAR || res[i].status == DZG_PANIC)
@@ -494,17 +532,47 @@ extern "C" int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_star
     std::vector<dzg_lp> lps2(redo.size());
     std::vector<dzg_result> res2(redo.size());
     std::vector<dzg_batch_start> start2(redo.size(), dzg_batch_start{nullptr, nullptr});
+    std::vector<dzg_duals> du2;
+    std::vector<dzg_ranging_req> req2;
+    std::vector<dzg_ranging> rg2;
+    std::vector<dzg_ray> ry2;
     for (size_t k = 0; k < redo.size(); ++k) {
         lps2[k] = lps[redo[k]];
         res2[k] = res[redo[k]];
         if (start) start2[k] = start[redo[k]];
+        if (post && post->du) du2.push_back(post->du[redo[k]]); // (the caller's arrays are written in place)
+        if (post && post->req) req2.push_back(post->req[redo[k]]);
+        if (post && post->req) rg2.push_back(post->rg[redo[k]]);
+        if (post && post->ry) ry2.push_back(post->ry[redo[k]]);
     }
     dzg_opts os = o;
     os.numerics = DZG_NUMERICS_STRICT;
-    const int rc2 = dzg_batch_solve_from(lps2.data(), start2.data(), (int64_t)redo.size(), &os, 0, res2.data(), nullptr);
+    const int rc2 =
+        post ? dzg_steps::strict_post(lps2.data(), start2.data(), (int64_t)redo.size(), &os, 0, res2.data(),
+                                      du2.empty() ? nullptr : du2.data(), req2.empty() ? nullptr : req2.data(),
+                                      rg2.empty() ? nullptr : rg2.data(), ry2.empty() ? nullptr : ry2.data())
+             : dzg_batch_solve_from(lps2.data(), start2.data(), (int64_t)redo.size(), &os, 0, res2.data(), nullptr);
     if (rc2 < 0) return rc2;
-    for (size_t k = 0; k < redo.size(); ++k) res[redo[k]] = res2[k];
+    for (size_t k = 0; k < redo.size(); ++k) {
+        res[redo[k]] = res2[k];
+        if (!du2.empty()) post->du[redo[k]] = du2[k];
+        if (!ry2.empty()) post->ry[redo[k]] = ry2[k];
+    }
     return 0;
+}
+
+extern "C" int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                                         const dzg_opts *opts, int64_t pivots_per_launch,
+                                         int64_t refactor_every, dzg_result *res)
+{
+    return solve_fast_from(lps, start, count, opts, pivots_per_launch, refactor_every, nullptr, res);
+}
+
+extern "C" int dzg_batch_solve_post(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                                    const dzg_opts *opts, int64_t pivots_per_launch, int64_t refactor_every,
+                                    const dzg_batch_post *post, dzg_result *res)
+{
+    return solve_fast_from(lps, start, count, opts, pivots_per_launch, refactor_every, post, res);
 }
 
 extern "C" int dzg_batch_solve_fast(const dzg_lp *lps, int64_t count, const dzg_opts *opts,

@@ -28,6 +28,7 @@
 #include "batch_steps.h"
 #include "common.h"
 #include "opts.h"
+#include "ranging.h" // dzg_ranging_req_valid
 
 namespace {
 
@@ -162,6 +163,9 @@ struct dzg_batch {
     size_t s_c = 0, s_rhs = 0, s_basis0 = 0, s_nonbasis0 = 0, s_z0 = 0, s_sbasis = 0, s_snonbasis = 0, s_fstate0 = 0;
     size_t s_items = 0, s_list = 0, s_wlist = 0, s_sd = 0, s_si = 0, s_end = 0; // the staging buffer
     size_t fstate_bytes = 0;
+    dzg_steps::PostSections post; // dzg_batch_resolve_post: c and rhs0 are the resident sections
+    unsigned char *rarena = nullptr; // ... and its ranging arena, made at the first use, grown when needed
+    size_t rarena_bytes = 0;
     unsigned char *stage = nullptr;  // pinned: the staging buffer as it goes up, offsets from s_items
     unsigned char *mirror = nullptr; // pinned: the state sections [state0, upload_end) as they come down
     int *h_lk = nullptr, *h_le = nullptr, *h_ll = nullptr; // the log as it comes down (made at the first use)
@@ -173,8 +177,9 @@ struct dzg_batch {
 
     ~dzg_batch()
     {
-        if (arena || st) (void)hipSetDevice(device);
+        if (arena || st || rarena) (void)hipSetDevice(device);
         if (arena) (void)hipFree(arena);
+        if (rarena) (void)hipFree(rarena);
         if (stage) (void)hipHostFree(stage);
         if (mirror) (void)hipHostFree(mirror);
         if (e0) (void)hipEventDestroy(e0);
@@ -237,6 +242,9 @@ int create_device(dzg_batch *b, const dzg_lp *lps)
     b->s_sd = L.ar.add(sizeof(double) * (P.nm + P.nvc));
     b->s_si = L.ar.add(sizeof(int) * (P.nm + P.nq));
     b->s_end = L.ar.top;
+    b->post.c = b->s_c;
+    b->post.rhs0 = b->s_rhs;
+    steps::post_layout_out(L.ar, b->post, P.nvc, P.nm, P.nq, N);
 
     DZG_HIP(hipStreamCreateWithFlags(&b->st, hipStreamNonBlocking));
     DZG_HIP(hipEventCreate(&b->e0));
@@ -745,9 +753,12 @@ extern "C" int dzg_batch_set_start(dzg_batch *b, int64_t lp, const int64_t *basi
     return 0;
 }
 
-extern "C" int dzg_batch_resolve(dzg_batch *b, const int64_t *which, int64_t nwhich, dzg_result *res)
+// dzg_batch_resolve, and behind it what `post` (NULL or empty: nothing) asks for.
+static int resolve_post(dzg_batch *b, const int64_t *which, int64_t nwhich, const dzg_batch_post *post,
+                        dzg_result *res)
 {
     if (const int rc = usable(b, "dzg_batch_resolve")) return rc;
+    if (post && !post->du && !post->req && !post->rg && !post->ry) post = nullptr;
     if (which && nwhich < 0) return dzg_set_error(DZG_E_ARG, "dzg_batch_resolve: nwhich < 0");
     const int64_t n = which ? nwhich : b->N;
     if (n > 0 && !res) return dzg_set_error(DZG_E_ARG, "dzg_batch_resolve: res is NULL");
@@ -761,10 +772,51 @@ extern "C" int dzg_batch_resolve(dzg_batch *b, const int64_t *which, int64_t nwh
         seen[(size_t)i] = 1;
         ids.push_back((int)i);
     }
+    if (n > 0 && post && (post->req != nullptr) != (post->rg != nullptr))
+        return dzg_set_error(DZG_E_ARG, "dzg_batch_resolve: req and rg go together (one of them is NULL)");
+    for (int64_t k = 0; post && post->req && k < n; ++k) {
+        std::string why;
+        const dzg_lp &lp = b->lp[(size_t)ids[(size_t)k]];
+        if (!dzg_ranging_req_valid(&post->req[k], lp.m, lp.n, why))
+            return dzg_set_error(DZG_E_ARG, "dzg_batch_resolve: which[" + std::to_string(k) + "]: lp " +
+                                                std::to_string(ids[(size_t)k]) + ": " + why);
+    }
     b->h2d = b->d2h = 0;
     b->ms = 0.0;
+    steps::post_ms() = 0.0;
     if (ids.empty()) return 0;
-    return fail_if_device(b, resolve(b, ids, res));
+    if (const int rc = fail_if_device(b, resolve(b, ids, res))) return rc;
+    if (!post) return 0;
+    // ---- what the listed LPs can say about where they ended, on the handle's own arena: a FAST
+    // result through k_batch_fast_post, a STRICT one through the STRICT batch's kernels
+    steps::PostRun R;
+    R.dev = b->arena;
+    R.L = b->L;
+    R.state = b->s_fstate;
+    R.status = b->s_status;
+    R.S = b->post;
+    R.rkeep = &b->rarena;
+    R.rkeep_bytes = &b->rarena_bytes;
+    R.st = b->st;
+    std::vector<int64_t> ids64(ids.begin(), ids.end());
+    double ms = 0.0;
+    for (int strict = b->strict ? 1 : 0; strict <= (b->strict || b->is_auto ? 1 : 0); ++strict)
+        if (const int rc = fail_if_device(b, steps::post_pass(R, strict != 0, b->P, (int)n, ids64.data(), res, *post,
+                                                              &b->h2d, &b->d2h, &ms)))
+            return rc;
+    steps::post_ms() = ms;
+    return 0;
+}
+
+extern "C" int dzg_batch_resolve(dzg_batch *b, const int64_t *which, int64_t nwhich, dzg_result *res)
+{
+    return resolve_post(b, which, nwhich, nullptr, res);
+}
+
+extern "C" int dzg_batch_resolve_post(dzg_batch *b, const int64_t *which, int64_t nwhich,
+                                      const dzg_batch_post *post, dzg_result *res)
+{
+    return resolve_post(b, which, nwhich, post, res);
 }
 
 extern "C" int dzg_debug_batch_traffic(const dzg_batch *b, int64_t bytes[2], double ms[1])

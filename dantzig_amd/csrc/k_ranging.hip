@@ -28,88 +28,7 @@ typedef double double4_t __attribute__((ext_vector_type(4)));
 
 namespace {
 
-__device__ __forceinline__ DzgRangePart range_none()
-{
-    DzgRangePart a;
-    a.lo = -__builtin_inf();
-    a.hi = __builtin_inf();
-    a.lo_k = DZG_RANGE_NONE;
-    a.hi_k = DZG_RANGE_NONE;
-    return a;
-}
-
-__device__ __forceinline__ void range_take_lo(DzgRangePart &a, double r, int k)
-{
-    if (k == DZG_RANGE_NONE) return;
-    if (a.lo_k == DZG_RANGE_NONE || r > a.lo || (r == a.lo && k < a.lo_k)) {
-        a.lo = r;
-        a.lo_k = k;
-    }
-}
-
-__device__ __forceinline__ void range_take_hi(DzgRangePart &a, double r, int k)
-{
-    if (k == DZG_RANGE_NONE) return;
-    if (a.hi_k == DZG_RANGE_NONE || r < a.hi || (r == a.hi && k < a.hi_k)) {
-        a.hi = r;
-        a.hi_k = k;
-    }
-}
-
-__device__ __forceinline__ void range_merge(DzgRangePart &a, const DzgRangePart &b)
-{
-    range_take_lo(a, b.lo, b.lo_k);
-    range_take_hi(a, b.hi, b.hi_k);
-}
-
-// the candidate rule for one position: one division, one negation
-__device__ __forceinline__ void range_elem(DzgRangePart &a, double clamped, double delta, double tol, int k)
-{
-    if (!(fabs(delta) > tol)) return; // (a NaN delta is no candidate)
-    const double r = -dzg_div(clamped, delta);
-    if (delta > 0.0)
-        range_take_lo(a, r, k);
-    else
-        range_take_hi(a, r, k);
-}
-
-__device__ __forceinline__ DzgRangePart range_shfl_xor(const DzgRangePart &a, int off)
-{
-    DzgRangePart o;
-    o.lo = __shfl_xor(a.lo, off, DZG_WAVE);
-    o.hi = __shfl_xor(a.hi, off, DZG_WAVE);
-    o.lo_k = __shfl_xor(a.lo_k, off, DZG_WAVE);
-    o.hi_k = __shfl_xor(a.hi_k, off, DZG_WAVE);
-    return o;
-}
-
-// over the whole workgroup: a wave shuffle of (value, position), then across waves in wave order;
-// thread 0 holds the result.  Every thread of the workgroup calls it.
-template <int BLOCK>
-__device__ DzgRangePart range_block(DzgRangePart a, DzgRangePart *s_red)
-{
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-        const DzgRangePart o = range_shfl_xor(a, off);
-        range_merge(a, o);
-    }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) s_red[wave] = a;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        for (int w = 1; w < BLOCK / 64; ++w) range_merge(a, s_red[w]);
-    return a;
-}
-
-// the value direction [e0, e1) holds for index `want`, 0.0 if it has none (indices are distinct)
-__device__ __forceinline__ double dir_value(const int *e_idx, const double *e_val, long long e0, long long e1,
-                                            int want)
-{
-    double v = 0.0;
-    for (long long e = e0; e < e1; ++e)
-        if (e_idx[e] == want) v = e_val[e];
-    return v;
-}
+using namespace dzg_rg; // ranging.h: the candidate rule and its reductions
 
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_ranging_small(DzgRangingArgs g, const DzgRangeItem *__restrict__ items)

@@ -10,6 +10,7 @@ Solution.objective_range(variable)."""
 from __future__ import annotations
 
 import abc
+import ctypes as C
 from dataclasses import dataclass
 from typing import Union
 
@@ -648,7 +649,8 @@ def solve_many(problems, *, duals: bool = False, ranging: bool = False, rays: bo
     ranging=True: p.solve(ranging=True)'s; rays=True: every exception is p.solve(rays=True)'s, `.ray`
     included.  fast=True: the shared batch runs FAST numerics and falls back to STRICT, model by
     model, where a decision of the pivot rule comes within rounding of a tie (rust.solve_many); not
-    yet together with duals, ranging or rays (ValueError)."""
+    together with duals, ranging or rays (ValueError): sessions(problems, fast=True).solve(duals=True,
+    ranging=True, rays=True) has them behind the FAST batch."""
     problems = list(problems)
     for i, p in enumerate(problems):
         if not isinstance(p, Optimize):
@@ -675,7 +677,7 @@ def solve_many(problems, *, duals: bool = False, ranging: bool = False, rays: bo
 
 class _BatchModel:
     """One model of a SessionBatch: what it holds now and where its last solve ended."""
-    __slots__ = ("problem", "objective", "rhs", "form", "order", "last")
+    __slots__ = ("problem", "objective", "rhs", "form", "order", "last", "arrays")
 
 
 def sessions(problems, fast: bool = False, resident: bool = False, **core_opts) -> "SessionBatch":
@@ -736,7 +738,7 @@ class SessionBatch:
         for i, p in enumerate(problems):
             st = _BatchModel()
             st.problem, st.objective, st.rhs, st.last = p, p.objective, {}, None
-            st.form, st.order = self._lower(i, p, st.objective, st.rhs)
+            st.form, st.order, st.arrays = self._lower_full(i, p, st.objective, st.rhs)
             self._models.append(st)
         self.pivots: list = []
         self.cold: list = []
@@ -747,6 +749,11 @@ class SessionBatch:
 
     @staticmethod
     def _lower(i: int, p: "Optimize", objective, rhs: dict):
+        return SessionBatch._lower_full(i, p, objective, rhs)[:2]
+
+    @staticmethod
+    def _lower_full(i: int, p: "Optimize", objective, rhs: dict):
+        """(form, order, the lowered arrays dzg_model_map_duals / _ray read)."""
         problem, arrays, order = _lower_model(p.sense, objective, _model_rows(p.constraints, rhs))
         if rs._has_integer(*problem):
             raise ValueError(f"problems[{i}]: re-optimisation is not defined for a model with integer variables")
@@ -754,7 +761,7 @@ class SessionBatch:
         if form.m > _ffi.BATCH_MAX_ROWS:
             raise ValueError(f"problems[{i}]: {form.m} rows in standard form; the batch takes at most "
                              f"{_ffi.BATCH_MAX_ROWS}")
-        return form, order
+        return form, order, arrays
 
     def __len__(self) -> int:
         return len(self._models)
@@ -767,8 +774,69 @@ class SessionBatch:
             raise ValueError(f"{name}: {len(what)} entries for {len(self._models)} models (None = unchanged)")
         return what
 
-    def solve(self, objectives=None, rhs=None, return_exceptions: bool = False) -> list:
-        """Solve every model with objectives[i] (a new expression in model i's sense) and rhs[i]
+    @staticmethod
+    def _core_request(problem, form, order):
+        """Model i's ranging request in terms of its standard form: one cost direction per user
+        variable (+1 on x+, -1 on x-), one right-hand-side direction per constraint (_row_groups)."""
+        cost = []
+        for u in range(len(order)):
+            d = {}
+            if form.pos_var[u] >= 0:
+                d[int(form.pos_var[u])] = 1.0
+            if form.neg_var[u] >= 0:
+                d[int(form.neg_var[u])] = -1.0
+            cost.append(d)
+        return cost, [{int(r): float(k) for r, k in g} for g in problem._row_groups()]
+
+    @staticmethod
+    def _model_duals(res, arrays, form, order):
+        """rs.PyDuals / rs.PyRanging of a core result, as solve_many maps them (dzg_model_map_duals)."""
+        du = res.duals
+        if du is None:
+            return None, None
+        md, buf, cm = _ffi.ModelDuals(), rs._DualBuffers(arrays), rs._c_model(arrays)
+        buf.fill(md)
+        y = _ffi.f64(du.y)
+        _ffi.check(_ffi.lib().dzg_model_map_duals(C.byref(cm), _ffi.ptr(y), C.c_int64(form.m), C.byref(md)),
+                   "dzg_model_map_duals")
+        md.core.source, md.core.primal_obj, md.core.dual_obj = du.source_code, du.primal_obj, du.dual_obj
+        md.core.primal_infeas, md.core.dual_infeas, md.core.z_diff = du.primal_infeas, du.dual_infeas, du.z_diff
+        rg = res.ranging
+        if rg is None:
+            return buf.pyduals(md, order), None
+        by_id = lambda a, cast: {v.id: cast(a[i]) for i, v in enumerate(order)}  # noqa: E731
+        return buf.pyduals(md, order), rs.PyRanging(
+            var_lo=by_id(rg.cost_lo, float), var_hi=by_id(rg.cost_hi, float), var_lo_var=by_id(rg.cost_lo_var, int),
+            var_hi_var=by_id(rg.cost_hi_var, int), group_lo=[float(v) for v in rg.rhs_lo],
+            group_hi=[float(v) for v in rg.rhs_hi], group_lo_var=[int(v) for v in rg.rhs_lo_var],
+            group_hi_var=[int(v) for v in rg.rhs_hi_var])
+
+    @staticmethod
+    def _model_ray(res, arrays, form, order):
+        """rs.PyRay of a core result's ray (dzg_model_map_ray), None without one."""
+        ray = res.ray
+        if ray is None:
+            return None
+        mr, buf, cm = _ffi.ModelRay(), rs._RayBuffers(arrays), rs._c_model(arrays)
+        buf.fill(mr)
+        d, y = _ffi.f64(ray.d), _ffi.f64(ray.y)
+        _ffi.check(_ffi.lib().dzg_model_map_ray(C.byref(cm), C.c_int32(ray.kind_code), _ffi.ptr(d), _ffi.ptr(y),
+                                                C.c_int64(form.m), C.c_int64(form.n), C.byref(mr)),
+                   "dzg_model_map_ray")
+        mr.core.kind, mr.core.proven, mr.core.value = ray.kind_code, int(ray.proven), ray.value
+        mr.core.violation, mr.core.mu = ray.violation, ray.mu
+        return buf.pyray(mr, order)
+
+    def solve(self, objectives=None, rhs=None, return_exceptions: bool = False, duals: bool = False,
+              ranging: bool = False, rays: bool = False) -> list:
+        """duals=True: every Solution answers dual(), reduced_cost() and certificate; ranging=True (implies
+        duals): also rhs_range() and objective_range(); rays=True: the UnboundedError / InfeasibleError of
+        a model carries `.ray` -- each as solve_many maps them, computed behind the batch from the state
+        the model ended in (core.solve_batch_fast / core.BatchSolver.solve with the same keywords; a
+        STRICT session goes through solve_batch_fast(numerics=STRICT, start=...)).  All three compose,
+        with each other and with a warm start.
+
+        Solve every model with objectives[i] (a new expression in model i's sense) and rhs[i]
         ({constraint: new b}, as Session.solve takes it) replacing what the batch holds for it; None,
         for one model or for the whole argument, means unchanged.  Returns one Solution per model,
         values mapped as Session.solve maps them.  A model that ends unbounded or infeasible raises
@@ -787,32 +855,49 @@ class SessionBatch:
                 if not isinstance(b, (int, float)):
                     raise TypeError("rhs maps a constraint to the number its normal form compares with")
                 new_rhs[id(constraint)] = _normal_b(b)
-            form, order = self._lower(i, st.problem, objective, new_rhs)
+            form, order, arrays = self._lower_full(i, st.problem, objective, new_rhs)
             warm = (st.last is not None and st.last.status not in ("singular", "panic")
                     and form.same_shape_as(st.form) and [v.id for v in order] == [v.id for v in st.order])
-            staged.append((objective, new_rhs, form, order, warm))
+            staged.append((objective, new_rhs, form, order, warm, arrays))
         lps = [core.CoreLP(a=f.a, c=f.c, basis=f.basis, nonbasis=f.nonbasis, x=f.x, z=f.z, var_col=f.var_col,
-                           constant=f.constant) for _, _, f, _, _ in staged]
-        start = [st.last if warm else None for st, (_, _, _, _, warm) in zip(self._models, staged)]
+                           constant=f.constant) for _, _, f, _, _, _ in staged]
+        start = [st.last if warm else None for st, (_, _, _, _, warm, _) in zip(self._models, staged)]
+        duals = bool(duals or ranging)
+        post = {}
+        if duals or rays:
+            post = dict(duals=duals, rays=bool(rays))
+            if ranging:
+                post["ranging"] = [self._core_request(st.problem, f, o)
+                                   for st, (_, _, f, o, _, _) in zip(self._models, staged)]
         if self._resident:
-            results = self._solve_resident(lps, [f for _, _, f, _, _ in staged], start)
+            results = self._solve_resident(lps, [f for _, _, f, _, _, _ in staged], start, post)
         else:
-            solve = core.solve_batch_fast if self._fast else core.solve_batch
-            results = solve(lps, log=False, start=start if any(s is not None for s in start) else None, **self._opts)
+            opts = dict(self._opts)
+            solve = core.solve_batch_fast if self._fast or post else core.solve_batch
+            if post and not self._fast:
+                opts["numerics"] = core.STRICT
+            results = solve(lps, log=False, start=start if any(s is not None for s in start) else None, **post, **opts)
         out = []
-        for i, (st, (objective, new_rhs, form, order, _), res) in enumerate(zip(self._models, staged, results)):
-            st.objective, st.rhs, st.form, st.order, st.last = objective, new_rhs, form, order, res
-            if res.status_code == _ffi.UNBOUNDED:
-                out.append(UnboundedError(f"The objective is unbounded (model {i})"))
-            elif res.status_code == _ffi.INFEASIBLE:
-                out.append(InfeasibleError(f"The model is infeasible (model {i})"))
+        for i, (st, (objective, new_rhs, form, order, _, arrays), res) in enumerate(zip(self._models, staged, results)):
+            st.objective, st.rhs, st.form, st.order, st.last, st.arrays = objective, new_rhs, form, order, res, arrays
+            if res.status_code in (_ffi.UNBOUNDED, _ffi.INFEASIBLE):
+                exc = (UnboundedError(f"The objective is unbounded (model {i})") if res.status_code == _ffi.UNBOUNDED
+                       else InfeasibleError(f"The model is infeasible (model {i})"))
+                if rays:
+                    exc.ray = self._model_ray(res, arrays, form, order)
+                    exc = st.problem._wrap_ray(exc)
+                out.append(exc)
             elif res.status_code != _ffi.OPTIMAL:
                 out.append(RuntimeError(f"simplex terminated with status {res.status!r} after "
                                         f"{res.iterations} iterations (model {i})"))
             else:
-                out.append(Solution(solution=rs.PySolution(res.objective, _user_values(res, form, order),
-                                                           res.iterations, res.numerics, (form.m, form.n)),
-                                    sense=st.problem.sense))
+                sol = rs.PySolution(res.objective, _user_values(res, form, order), res.iterations, res.numerics,
+                                    (form.m, form.n))
+                if duals:
+                    sol.duals, sol.ranging = self._model_duals(res, arrays, form, order)
+                out.append(Solution(solution=sol, sense=st.problem.sense,
+                                    constraints=list(st.problem.constraints) if duals else None,
+                                    objective=objective if ranging else None))
         self.pivots.append([r.iterations for r in results])
         self.cold.append(sum(s is None for s in start))
         if self._fast:
@@ -823,7 +908,7 @@ class SessionBatch:
                     raise o
         return out
 
-    def _solve_resident(self, lps, forms, start) -> list:
+    def _solve_resident(self, lps, forms, start, post=None) -> list:
         """This call on the resident handle: start[i] is what the stateless call would hand model i
         (None: cold).  The handle is built from `lps` when there is none or when a model's standard
         form no longer fits the one it holds; otherwise only what moved is sent."""
@@ -841,7 +926,7 @@ class SessionBatch:
             for i, s in enumerate(start):
                 if s is not None:
                     self._handle.set_start(i, s)
-            return self._handle.solve(log=False)
+            return self._handle.solve(log=False, **(post or {}))
         changes = []
         for i, (f, st) in enumerate(zip(forms, self._models)):
             old = st.form
@@ -858,7 +943,7 @@ class SessionBatch:
                 self._handle.set_start(i, None)
         if changes:
             self._handle.update_many(changes)
-        return self._handle.solve(log=False)
+        return self._handle.solve(log=False, **(post or {}))
 
     def close(self) -> None:
         """Frees the resident handle (resident=True); the models' last bases stay on the host, so the

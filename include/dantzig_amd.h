@@ -834,6 +834,60 @@ int dzg_batch_solve_fast_from(const dzg_lp *lps, const dzg_batch_start *start, i
  * LP. */
 double dzg_debug_batch_fast_restart_ms(void);
 
+/* ---- Duals, ranging and rays behind a FAST batch (csrc/k_batch_post.hip) ------------------ */
+
+/* What a batch call computes beside the solve, from the state every LP ended in: du, (req, rg) and
+ * ry hold `count` entries each and mean what they mean for dzg_batch_solve_duals / _ranging / _rays.
+ * Every pointer is optional and all four compose in one call; req needs rg and rg needs req; ranging
+ * computes the duals whether du is given or not. */
+typedef struct {
+    dzg_duals *du;
+    const dzg_ranging_req *req;
+    dzg_ranging *rg;
+    dzg_ray *ry;
+} dzg_batch_post;
+/* dzg_batch_solve_fast_from(lps, start, count, opts, pivots_per_launch, refactor_every, res) -- res
+ * is bit for bit what that call fills, and post == NULL, or a post whose four pointers are NULL, is
+ * exactly that call -- and then, after the rounds and after AUTO's second attempt, per LP by
+ * res[i].numerics_used and res[i].status:
+ *   a FAST result: k_batch_fast_post, one workgroup per LP.  W = B^-1 of the final basis as a launch
+ *     of the FAST batch builds it (an all-slack basis is a permutation; no refinement step), then
+ *     OPTIMAL:  y = W^T c_B, d[N_k] = -dz_k - c[N_k] with dz one pricing pass over y (stored entries
+ *       only), d[B_p] = 0.0, dual_obj = constant + rhs0 . y, source DZG_DUALS_FRESH; with ranging, a
+ *       right-hand-side direction h gives delta_p = sum_e W[p][r_e] h_e over its entries in the order
+ *       given, a cost direction g gives Y = sum over its basic entries of g_e (row pos(e) of W) and
+ *       delta_k = -dz_k(Y) - g[N_k] (no basic entry: Y = 0 and no pricing pass); candidates, clamping,
+ *       pivot_tol, ties and *_var as dzg_ranging defines them.
+ *     UNBOUNDED / INFEASIBLE:  pos = the first-pivot winner over (z, zbar) / (x, xbar) as the FAST
+ *       iteration finds it; PRIMAL: dx = W a_j;  FARKAS: y = row pos of W, dz one pricing pass;
+ *       d, value, violation and proven as dzg_ray defines them.
+ *     Every sum's order depends on m alone (four interleaved partial sums, j ascending; pricing as in
+ *     the solve), the reductions are min / max with the position as tie-break and there are no
+ *     atomics: an LP's post-solve does not depend on its place in the batch, and asking twice gives
+ *     the same bits.  rhs0 is the right-hand side by constraint row for an LP with a start basis and
+ *     the starting x as it is for a cold one.  The carried state, the pivot count, refactors and the
+ *     log are not touched.  If the final basis does not invert (a zero or non-finite pivot) the LP
+ *     reports nothing -- source = 0, kind = 0, NaN ranges, *_var = -1 -- and its result stands.
+ *   a STRICT result (opts->numerics STRICT, or an LP AUTO handed over): k_duals_small,
+ *     k_ranging_small and k_rays_small on the final state of the STRICT batch.  For a cold LP that is
+ *     bit for bit what dzg_batch_solve_duals / _ranging / _rays return; a warm LP gets the same
+ *     kernels on its final state, so through this call a start basis composes with ranging and rays.
+ *   any other status (DZG_NEAR_TIE, DZG_SINGULAR, DZG_PANIC or DZG_ITER_LIMIT under pure FAST): no
+ *     post-solve, source = 0, kind = 0, NaN ranges.
+ * Host checks, before any device work: every check of dzg_batch_solve_fast_from, req without rg or
+ * rg without req, and the checks of dzg_ranging_req per LP (indices in range and distinct per
+ * direction, pivot_tol negative or NaN); DZG_E_ARG with the LP's index in dzg_last_error. */
+int dzg_batch_solve_post(const dzg_lp *lps, const dzg_batch_start *start, int64_t count,
+                         const dzg_opts *opts, int64_t pivots_per_launch, int64_t refactor_every,
+                         const dzg_batch_post *post, dzg_result *res);
+/* Device time (ms, between two events on the call's stream) of the post-solve launches of post_pass
+ * (csrc/batch_steps.h) in the calling thread's last dzg_batch_solve_post or dzg_batch_resolve_post:
+ * k_batch_fast_post for the FAST results and, on a handle, k_duals_small / k_ranging_small /
+ * k_rays_small for the STRICT ones, added up.  0 when the call launched none, and after
+ * dzg_batch_solve_post with numerics = STRICT, whose post-solve is dzg_batch_solve_ranging's own and
+ * is not timed. */
+double dzg_debug_batch_post_ms(void);
+
 /* ---- A batch kept resident on the device between solves (csrc/k_batch_resident.hip) ------- */
 
 /* The batched sibling of dzg_solver_reoptimize: the matrices, var_col and the descriptors of `count`
@@ -845,8 +899,9 @@ double dzg_debug_batch_fast_restart_ms(void);
  * a stateless call's (the log sections sized by log_cap) plus rhs, c and three copies of a basis.
  * A HIP failure inside any call leaves the handle failed: every later call returns DZG_E_DEVICE;
  * dzg_batch_destroy still frees everything.
- * Out of scope: duals, ranging and rays on the handle; adding or removing rows, columns or LPs;
- * the node LPs of dzg_mip_solve; folding the restart into the first launch. */
+ * On the handle too: duals, ranging and rays: dzg_batch_resolve_post (below).
+ * Out of scope: adding or removing rows, columns or LPs; the node LPs of dzg_mip_solve;
+ * folding the restart into the first launch. */
 typedef struct dzg_batch dzg_batch;
 
 /* lps[0..count): dense, m <= DZG_BATCH_MAX_ROWS, in slack-basis form (own basis all slack, one
@@ -890,6 +945,19 @@ int dzg_batch_set_start(dzg_batch *b, int64_t lp, const int64_t *basis, const in
  * listed are not touched: their state on the device, their pending updates and last_i stay.
  * DZG_E_ARG, nothing changed: res == NULL, an index out of range or listed twice, nwhich < 0. */
 int dzg_batch_resolve(dzg_batch *b, const int64_t *which, int64_t nwhich, dzg_result *res);
+
+/* dzg_batch_resolve(b, which, nwhich, res) -- res has that call's bits, last_i moves as there, and
+ * post == NULL or a post whose four pointers are NULL is exactly that call -- and then the post-solve
+ * dzg_batch_solve_post defines, on the handle's own arena, from the resident c and the resident
+ * right-hand sides by constraint row: a FAST result through k_batch_fast_post, a STRICT result (a
+ * STRICT handle, or an LP AUTO handed over) through k_duals_small / k_ranging_small / k_rays_small on
+ * its final state.  post's arrays hold one entry per listed LP: entry k belongs to which[k].  The
+ * outputs come down for the listed LPs only; the carried state is not touched, so the next solve is
+ * what it would have been.  Host checks, DZG_E_ARG and nothing changed: those of dzg_batch_resolve,
+ * req without rg or rg without req, a ranging request that dzg_ranging_req refuses (which[k] named).
+ * The bytes join dzg_debug_batch_traffic's; dzg_debug_batch_post_ms gives the launches' time. */
+int dzg_batch_resolve_post(dzg_batch *b, const int64_t *which, int64_t nwhich,
+                           const dzg_batch_post *post, dzg_result *res);
 
 /* Test and measurement hook: bytes[0] / bytes[1] = host-to-device / device-to-host bytes of the
  * handle's last dzg_batch_resolve (every copy it enqueued, staged updates included);
